@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: rays/s of ``VectorFieldNerf.render`` (forward, eval mode) on 4096-ray chunks with
 128 samples per ray (S_c = N_f = 64), one process per GPU, on the synthetic random-weight scene BASELINE.json's north_star names
-(`value`, `roofline`); the same path on weights the reference's own trainer arrived at (tests/golden/trained_far.npz: data, not code)
-is timed beside it (`value_trained_weights`, `roofline_trained_weights`); --weights trained swaps the two.
+(`value`, `roofline`); with --full, the same path on weights the reference's own trainer arrived at (tests/golden/trained_far.npz:
+data, not code) is timed beside it (`value_trained_weights`, `roofline_trained_weights`); --weights trained swaps the two.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full   # + every leg beside the headline (traffic passes, other scene, CPU, parity, train)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
     python bench.py --gpus 8 --steps 20 --warmup 3          # starts its own 8 ranks (torch.distributed.run as a CHILD process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus 8 --steps 20 --warmup 3             # ... or is started as a rank by the caller's launcher
@@ -12,19 +14,20 @@ is timed beside it (`value_trained_weights`, `roofline_trained_weights`); --weig
 A step = one render() of one 4096-ray chunk per rank (rays shard embarrassingly: no data-path collective,
 weak scaling).  The timed region is bracketed by barrier + torch.cuda.synchronize() on both sides; the time is
 the max over ranks; rank 0 prints ONE JSON line.  Inputs (uv / pose / intrinsics) are resident in HBM before
-the timed region; random numbers come from the device Philox stream inside the timed region.
+the timed region; random numbers come from the device Philox stream inside the timed region, the timed steps' draws at the
+stream offset the warm-up left (the run-in between them does not move it), so the same arguments give the same inputs on every run.
 
-Extra objects on the line:
+Extra objects on the line (those marked --full only with --full):
   roofline          the dominant kernel class of the step (largest share of the timed region; with the defaults the VF
                     MLP launch of the split inference pipeline, two launches per step): ALGORITHMIC fp32-equivalent FLOPs
                     of one launch (SURVEY.md §8d per-point figures x its points) / its average duration measured with
                     HIP events on the launch stream inside the timed region; peak = dense f16 MFMA 2500 TFLOP/s / 3 (three
                     f16 products per fp32-equivalent product), or 157.3 TFLOP/s fp32 matrix with --precision fp32;
-                    traffic = FETCH_SIZE x 2 + WRITE_SIZE of that kernel from two rocprofv3 --pmc child runs of this command made on
-                    this box before the timed run (live_hbm_traffic; the committed passes of profiles/ are the fallback);
+                    traffic = FETCH_SIZE x 2 + WRITE_SIZE of that kernel from the committed passes of profiles/, or with --full from
+                    two rocprofv3 --pmc child runs of this command made before the timed run (live_hbm_traffic);
                     effective_clock_ghz from in-kernel s_memtime / s_memrealtime stamps.
-  cpu_baseline      the CPU oracle (torch fp32, 32 host threads) on a bounded sample of the same workload.
-  parity_vs_oracle  the "PSNR vs ref" half of the metric: the HIP path against the oracle on those sample rays.
+  cpu_baseline      --full: the CPU oracle (torch fp32, 32 host threads) on a bounded sample of the same workload.
+  parity_vs_oracle  --full: the "PSNR vs ref" half of the metric: the HIP path against the oracle on those sample rays.
 
 Other workloads (not the headline line): --workload view | grid | train (BASELINE.json configs[1], [4], [2]);
 --no-reuse evaluates the VF net on the proposal samples twice, as the reference does (one fused launch).
@@ -1163,6 +1166,35 @@ def dry_run(args, rank: int, world: int, dist) -> None:
         dist.destroy_process_group()
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out, n_rays: int, path: str) -> None:
+    """--dump-outputs DIR: every tensor a caller of render() receives from the last timed step, as DIR/<name>.npy (float32; float64 stays
+    float64).  Past 64 MB in all, the same seeded sample of rays is kept from every per-ray array and DIR/sampled_rays.npy lists them."""
+    import dataclasses
+
+    import numpy as np
+    arrays = {}
+    for f in dataclasses.fields(out):
+        v = getattr(out, f.name)                         # (materialises the lazily built fields, as a caller's access does)
+        if isinstance(v, torch.Tensor):
+            arrays[f.name] = v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32)
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        rows = torch.randperm(n_rays, generator=torch.Generator().manual_seed(0))[:int(n_rays * DUMP_CAP_BYTES / total)].sort().values
+
+        def per_ray(a):                                  # [n_rays, ...] or flattened [n_rays * per_ray, ...]
+            if a.dim() == 0 or a.shape[0] % n_rays:
+                return a
+            return a.reshape(n_rays, -1, *a.shape[1:])[rows].reshape(-1, *a.shape[1:])
+        arrays = {k: per_ray(a) for k, a in arrays.items()}
+        arrays["sampled_rays"] = rows.to(torch.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1241,7 +1273,20 @@ def main() -> None:
     ap.add_argument("--train", action="store_true",
                     help="time a training step instead (render with autograd + 2 supervision VF forwards + loss + "
                          "backward + clip + Adam, train/vector_field_nerf_train.py:177-260); not the headline metric")
+    ap.add_argument("--full", action="store_true",
+                    help="render workload: everything the line can carry beside the headline figure — the live HBM-traffic passes "
+                         "(rocprofv3 child runs), the two-product and other-scene legs, the shipped-conf rows, the CPU baseline and the "
+                         "parity legs, the training sub-object.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="render workload: after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, "
+                         "64 MB at most); the same arguments give the same inputs on every run")
     args = ap.parse_args()
+    if args.dump_outputs and (args.train or args.dry_run or args.workload != "render"):
+        ap.error("--dump-outputs: render workload only")
+    if not args.full and args.workload == "render":
+        # a plain run: the headline figure and nothing else
+        args.no_live_traffic = args.no_two_product_leg = args.no_other_scene_leg = True
+        args.no_shipped_rows = args.no_cpu_baseline = args.no_train = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not started by a launcher: start the ranks ourselves (children; this process never touches the GPU)
@@ -1350,11 +1395,14 @@ def main() -> None:
         for _ in range(warmup):
             mdl.render(pose, uv, K, epoch=0)
         torch.cuda.synchronize()
+        rng_offset = mdl._rng_offset
         t_burn = time.perf_counter()
         while time.perf_counter() - t_burn < sustain:
             for _ in range(16):
                 mdl.render(pose, uv, K, epoch=0)
             torch.cuda.synchronize()
+        # the timed steps draw what they would right after the warm-up: their inputs do not depend on how many renders the run-in fitted
+        mdl._rng_offset = rng_offset
         sync()
         t_a = time.perf_counter()
         for i in range(steps):
@@ -1378,6 +1426,8 @@ def main() -> None:
         # per-workgroup clock stamps of the fused launches (csrc/vfn_mlp16.hip, vfn_f16x3_set_clock_probe): [workgroup][cycles, ticks]
         probe = torch.zeros((args.rays * max(s_c, n_f) + 127) // 128, 2, dtype=torch.int64, device=dev) if args.precision == "f16x3" else None
         local_elapsed, elapsed, out = timed_region(model, args.steps, args.warmup, args.sustain_seconds, events, probe)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(out, args.rays, args.dump_outputs)
         clock = None
         from vf_nerf_amd import lib as vlib
         if probe is not None:

@@ -271,7 +271,9 @@ def test_training_loop_tracks_the_cpu_path():
     the two trajectories are the same trajectory: Adam's normalised steps amplify rounding differences, and as soon as
     one proposal argmax (a discrete event) differs between the paths the fine samples of that ray differ and the
     curves part (observed around step 6-10 with this deliberately jumpy synthetic setup) — so the first six steps are
-    asserted and the rest is reported."""
+    asserted and the rest is reported.  The CPU side runs in float64: an fp32 CPU trajectory is itself one rounding sample
+    whose path depends on the host's BLAS kernels (by step 5, fp32 runs on different CPUs lie up to 8e-4 from the float64
+    curve and 1e-3 from each other), while the float64 curve is the same on every host."""
     from helpers import oracle_settings
     from oracle import vfnerf_oracle as O
     fx, d = load_fixture("c1_perturb")
@@ -285,11 +287,15 @@ def test_training_loop_tracks_the_cpu_path():
     draws = [dict(u_coarse=torch.rand(n, s_c, generator=gen), u_fine=torch.rand(n, n_f, generator=gen),
                   u_add=torch.rand(n, n_f, generator=gen)) for _ in range(steps)]
     w = O.LossWeights()
+    f64 = torch.Tensor.double
 
     def run(device):
         model = build_model(fx, d, device=device)
         if device != "cpu":
             model.precision = "fp32"     # a trajectory comparison: keep every discrete event (ReLU kinks) on the CPU's side
+        else:
+            for net in (model.vector_field_network, model.rendering_network, model.density):
+                net.double()
         lr = model.config.scheduler_config.lr
         if device == "cpu":
             model.optimizer = torch.optim.Adam(model.parameters(), lr=lr, foreach=False)  # PyTorch's sequential loop
@@ -299,12 +305,12 @@ def test_training_loop_tracks_the_cpu_path():
         for t in range(steps):
             if device == "cpu":
                 live = lambda net: {**dict(net.named_parameters()), **dict(net.named_buffers())}
-                out = O.render(uv, pose, K, live(model.vector_field_network), live(model.rendering_network),
+                out = O.render(f64(uv), f64(pose), f64(K), live(model.vector_field_network), live(model.rendering_network),
                                oracle_settings(fx), beta=model.density.beta, mean=model.density.mean,
-                               scale=model.density.scale, **draws[t])
+                               scale=model.density.scale, **{k: f64(v) for k, v in draws[t].items()})
                 rgb, depth, normals = out["rgb"], out["depth"], out["normals"]
-                sup = O.vf_mlp(sup_pts, live(model.vector_field_network))[:, :3]
-                tgt = (rgb_gt, depth_gt, sup_gt)
+                sup = O.vf_mlp(f64(sup_pts), live(model.vector_field_network))[:, :3]
+                tgt = (f64(rgb_gt), f64(depth_gt), f64(sup_gt))
             else:
                 dev = torch.device(device)
                 o = model.render(pose.to(dev), uv.to(dev), K.to(dev), 0, uniforms={k: v.to(dev) for k, v in draws[t].items()})

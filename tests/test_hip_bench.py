@@ -20,7 +20,7 @@ def _run(*args, timeout=600):
 
 
 def test_default_line_has_the_contract_keys_and_consistent_arithmetic():
-    d = _run("--gpus", "1", "--steps", "8", "--warmup", "2", "--sustain-seconds", "0.3", "--train-steps", "3")
+    d = _run("--gpus", "1", "--steps", "8", "--warmup", "2", "--sustain-seconds", "0.3", "--train-steps", "3", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -74,6 +74,29 @@ def test_default_line_has_the_contract_keys_and_consistent_arithmetic():
     assert seq["ms_per_step"] < 1.25 * tr["ms_per_step"] and abs(seq["running_loss_mean_read_at_the_end"]) < 10.0
     # bytes of the step that ran (sparse colour branch) next to the dense step's accounting
     assert tr["workspace_gb_per_step"] < 0.8 * tr["workspace_gb_per_step_dense_step"]
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) carries the headline and none of the legs beside it; --dump-outputs writes the last timed step's outputs, and
+    the same arguments give the same outputs whatever the length of the run-in before the timed steps."""
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    lines = [_run("--gpus", "1", "--steps", "5", "--warmup", "2", "--rays", "1024", "--sustain-seconds", s, "--dump-outputs", str(p))
+             for s, p in (("0.2", dirs[0]), ("0.8", dirs[1]))]
+    for d in lines:
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["unit"] == "rays/s" and d["higher_is_better"] is True and d["dtype"] == "f16x3+f32acc"
+        assert abs(d["value"] - 1024 * 1000.0 / d["ms_per_step"]) < 2e-3 * d["value"]
+        assert "cpu_baseline" not in d and "train" not in d and d["value_trained_weights"] is None and d["value_shipped_conf"] is None
+    import numpy as np
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == sorted(p.name for p in dirs[1].iterdir())
+    for need in ("coarse_rgb_values.npy", "coarse_depth_map.npy", "coarse_normals.npy", "points_coarse.npy", "z_vals.npy"):
+        assert need in names, names
+    assert sum((dirs[0] / n).stat().st_size for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape, n
+        assert np.allclose(a, b, rtol=0.0, atol=1e-5, equal_nan=True), (n, float(np.nanmax(np.abs(a - b))))   # (other draws: O(0.1) apart)
+    assert np.load(dirs[0] / "coarse_rgb_values.npy").shape == (1024, 3)
 
 
 def test_rccl_process_group_with_one_rank_keeps_stdout_to_the_json_line():

@@ -659,18 +659,46 @@ def test_live_traffic_pass_reports_why_it_could_not_run(monkeypatch):
     assert bench.under_profiler() in (False, True)
 
 
+def test_dump_outputs_writes_float_arrays_and_samples_rays_past_the_cap(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs DIR): every tensor field of the render output as DIR/<name>.npy in float32; past the size cap
+    the same seeded rays are kept from every per-ray array (flattened per-sample ones included) and listed in sampled_rays.npy."""
+    import sys
+
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    from vf_nerf_amd.render_output import NerfOutput
+    n, s = 64, 8
+    g = torch.Generator().manual_seed(5)
+    out = NerfOutput(points_coarse=torch.rand(n * s, 3, generator=g), coarse_normals=torch.rand(n * s, 3, generator=g),
+                     coarse_rgb_values=torch.rand(n, 3, generator=g), coarse_depth_map=torch.rand(n, 1, generator=g),
+                     mask=torch.rand(n, 1, generator=g) > 0.5, z_vals=torch.rand(n, s, generator=g).double())
+    bench.dump_outputs(out, n, str(tmp_path / "all"))
+    got = {p.stem: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert set(got) == {"points_coarse", "coarse_normals", "coarse_rgb_values", "coarse_depth_map", "mask", "z_vals"}
+    assert got["mask"].dtype == np.float32 and got["z_vals"].dtype == np.float64 and got["points_coarse"].dtype == np.float32
+    assert np.array_equal(got["points_coarse"], out.points_coarse.numpy())
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 4096)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(out, n, str(tmp_path / d))
+    part = {p.stem: np.load(p) for p in (tmp_path / "s1").iterdir()}
+    rows = part["sampled_rays"].astype(np.int64)
+    assert 0 < len(rows) < n and sum(a.nbytes for a in part.values()) <= 4096 + rows.nbytes
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "sampled_rays.npy").astype(np.int64))
+    assert np.array_equal(part["coarse_rgb_values"], got["coarse_rgb_values"][rows])
+    assert np.array_equal(part["points_coarse"], got["points_coarse"].reshape(n, s, 3)[rows].reshape(-1, 3))
+
+
 def test_reference_sequence_is_the_reference_trainers_call_sequence():
     """tools/reference_sequence.py (what the GPU tests, tools/host_profile.py and bench.py's ``train.drop_in_sequence`` run as "the
     reference trainer's own call sequence") against the REFERENCE'S OWN ``VectorFieldNerfRunner.train_epoch``: both are run on the same
-    recording stand-ins (tests/trace_reference_loop.py, in a subprocess: it imports /root/reference) and must make the same calls with the
-    same argument shapes and scalars in the same order — render, sample_border_points, vector_field_network, get_center_indices_and_gt,
-    sample_center_points, vector_field_network, the loss, zero_grad, parameters, clip_grad_norm_, optimizer.step, scheduler.step.
-    Skipped where the reference is not present (the GPU box)."""
+    recording stand-ins (tests/trace_reference_loop.py, in a subprocess; the reference's trace is the recorded fixture
+    tests/golden/reference_loop_trace.json) and must make the same calls with the same argument shapes and scalars in the same order —
+    render, sample_border_points, vector_field_network, get_center_indices_and_gt, sample_center_points, vector_field_network, the loss,
+    zero_grad, parameters, clip_grad_norm_, optimizer.step, scheduler.step."""
     import json
     import subprocess
     import sys
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("no /root/reference here")
     r = subprocess.run([sys.executable, os.path.join(REPO, "tests", "trace_reference_loop.py")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads(r.stdout.strip().splitlines()[-1])

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""Is tools/reference_sequence.py the reference trainer's loop body CALL FOR CALL?  Checked mechanically, in the build container (needs
-/root/reference, read-only): the reference's OWN ``VectorFieldNerfRunner.train_epoch`` (train/vector_field_nerf_train.py:161-292, imported
-with the host-only modules it pulls in stubbed, as tests/golden/make_train_golden.py does) and ``reference_sequence.ReferenceLoop`` are
-both run on the SAME recording stand-ins — a model whose ``render`` / ``vector_field_network`` / ``parameters`` / optimizer / scheduler
-record their calls, a recording loss, recording ``functions.*`` helpers, a recording ``clip_grad_norm_`` — and the two call traces
-(names, argument shapes and scalar arguments, in order) must be identical.  Prints one JSON line; run by
-tests/test_host_logic.py::test_reference_sequence_is_the_reference_trainers_call_sequence in a subprocess (it changes the working
-directory and stubs modules)."""
+"""Is tools/reference_sequence.py the reference trainer's loop body CALL FOR CALL?  Checked mechanically: the reference's OWN
+``VectorFieldNerfRunner.train_epoch`` (train/vector_field_nerf_train.py:161-292) and ``reference_sequence.ReferenceLoop`` are both run on
+the SAME recording stand-ins — a model whose ``render`` / ``vector_field_network`` / ``parameters`` / optimizer / scheduler record their
+calls, a recording loss, recording ``functions.*`` helpers, a recording ``clip_grad_norm_`` — and the two call traces (names, argument
+shapes and scalar arguments, in order) must be identical.
+
+    python tests/trace_reference_loop.py                          # the restatement against tests/golden/reference_loop_trace.json
+    python tests/trace_reference_loop.py --record REFERENCE_DIR   # re-record that fixture from a checkout of the reference
+
+The fixture is the reference's trace on these stand-ins (data only; recording imports the reference's trainer with the host-only modules
+it pulls in stubbed, as tests/golden/make_train_golden.py does).  Prints one JSON line; run by
+tests/test_host_logic.py::test_reference_sequence_is_the_reference_trainers_call_sequence in a subprocess (it stubs modules)."""
 import json
 import os
 import sys
@@ -16,10 +20,7 @@ from types import SimpleNamespace
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-if not os.path.isdir(REF):
-    print(json.dumps({"skipped": "no /root/reference"}))
-    sys.exit(0)
+FIXTURE = os.path.join(REPO, "tests", "golden", "reference_loop_trace.json")
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
@@ -42,21 +43,22 @@ class _StubModule(types.ModuleType):
         return _Anything
 
 
-for _name in ("cv2", "imageio", "open3d", "skimage", "skimage.metrics", "skimage.transform", "skimage.io", "lpips", "trimesh", "wandb", "GPUtil",
-              "configargparse", "pyhocon", "torchvision", "torchvision.transforms"):
-    if _name not in sys.modules:
-        m = _StubModule(_name)
-        m.__path__ = []
-        sys.modules[_name] = m
-sys.path.insert(0, REF)
-os.chdir(REF)                                   # the trainer does sys.path.append('.')
-_ds = types.ModuleType("datasets.normal_datasets")
-_ds.__path__ = []
-_ds.dataset_dict = {}
-sys.modules["datasets.normal_datasets"] = _ds
-import train.vector_field_nerf_train as ref_train  # noqa: E402  (the REFERENCE's module)
+def import_reference_trainer(ref_dir):
+    for name in ("cv2", "imageio", "open3d", "skimage", "skimage.metrics", "skimage.transform", "skimage.io", "lpips", "trimesh", "wandb",
+                 "GPUtil", "configargparse", "pyhocon", "torchvision", "torchvision.transforms"):
+        if name not in sys.modules:
+            m = _StubModule(name)
+            m.__path__ = []
+            sys.modules[name] = m
+    sys.path.insert(0, ref_dir)
+    os.chdir(ref_dir)                               # the trainer does sys.path.append('.')
+    ds = types.ModuleType("datasets.normal_datasets")
+    ds.__path__ = []
+    ds.dataset_dict = {}
+    sys.modules["datasets.normal_datasets"] = ds
+    import train.vector_field_nerf_train as ref_train  # (the REFERENCE's module)
+    return ref_train
 
-import reference_sequence  # noqa: E402  (installs the drop-in aliases; the restatement under test)
 
 N, S = 40, 16
 DEV = torch.device("cpu")
@@ -163,7 +165,7 @@ def make_world(trace):
     return SimpleNamespace(model=model, loss=loss, functions=functions, clip=clip_grad_norm_, dataset=Dataset(), batch=batch, nerf_cfg=nerf_cfg)
 
 
-def run_reference(steps=2):
+def run_reference(ref_train, steps=2):
     trace = []
     wd = make_world(trace)
     runner = SimpleNamespace(model=wd.model, loss=wd.loss, dataset=wd.dataset, dataloader=[wd.batch] * steps,
@@ -182,6 +184,7 @@ def run_reference(steps=2):
 
 
 def run_restatement(steps=2):
+    import reference_sequence  # (installs the drop-in aliases; the restatement under test)
     trace = []
     wd = make_world(trace)
     keep_fn, keep_clip = reference_sequence.functions, torch.nn.utils.clip_grad_norm_
@@ -195,7 +198,16 @@ def run_restatement(steps=2):
     return trace
 
 
-a, b = run_reference(), run_restatement()
+if len(sys.argv) == 3 and sys.argv[1] == "--record":
+    trace = run_reference(import_reference_trainer(os.path.abspath(sys.argv[2])))
+    with open(FIXTURE, "w") as f:          # one call per line
+        f.write('{"what": "call trace of the reference\'s VectorFieldNerfRunner.train_epoch, two iterations on the stand-ins of '
+                'tests/trace_reference_loop.py",\n "trace": [\n  ' + ",\n  ".join(json.dumps(c) for c in trace) + "\n]}\n")
+    print(json.dumps({"recorded": len(trace)}))
+    sys.exit(0)
+with open(FIXTURE) as f:
+    a = json.load(f)["trace"]
+b = run_restatement()
 first = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), None)
 print(json.dumps({"calls_reference": len(a), "calls_restatement": len(b), "identical": a == b,
                   "first_difference": None if a == b else {"index": first if first is not None else min(len(a), len(b)),

@@ -5,7 +5,7 @@ set -u
 OUT=${1:-gpurun_out/measure}
 mkdir -p "$OUT"
 last() { tail -1; }
-python bench.py 2> "$OUT/bench_default.err" | last > "$OUT/bench_default.json"
+python bench.py --full 2> "$OUT/bench_default.err" | last > "$OUT/bench_default.json"
 python bench.py --workload train --steps 30 2>/dev/null | last > "$OUT/bench_train.json"
 python bench.py --workload train --rays 1024 --steps 60 2>/dev/null | last > "$OUT/bench_train_1024.json"
 python bench.py --workload train --batch-statistics --train-weights random --steps 10 --warmup 3 2>/dev/null | last > "$OUT/bench_train_batch_statistics.json"
