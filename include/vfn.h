@@ -672,6 +672,51 @@ int vfn_grid_comb_format_sides(const uint8_t* sides, const float* norms, int32_t
                                void* stream);
 
 /* =============================================================================================
+ * Mesh triangulation: contrastive marching cubes (evaluation/utils/marching_cubes_vt.py:186-315 with combs_to_verts :62-101 and
+ * vertex_interpolate :9-16), the stage after make_comb_format in evaluation/methods.py:256-291.  Four stream-ordered calls:
+ *   vfn_mesh_count   per cell POSITION p < m: triangle count counts[p]; offsets[p] = inclusive scan of counts; info[0] = triangles T,
+ *                    info[1] |= 1 (a non-finite corner value / norm, see below) | 2 (a cell index outside [0, res)).  The caller
+ *                    zero-fills info[4] first and reads it back once to size the outputs.
+ *   vfn_mesh_emit    tri_verts[3 T, 3] (double): the corners of every triangle at slot 3 (offsets[p] - counts[p] + t) + corner.
+ *   vfn_mesh_dedup   vertices with equal (x, y, z) — compared as doubles: 0.0 == -0.0 — share one id, owned by the smallest slot;
+ *                    table / owner: table_size (a power of two >= 2 x n_slots) int32 each, bucket / flags / vid: n_slots int32 each;
+ *                    info[2] = unique vertices V.  Result independent of the order in which the device's atomics arrive.
+ *   vfn_mesh_number  vertices[V, 3] (double, the first occurrence's bits) in order of first appearance and faces[n_slots] (int64,
+ *                    0-based ids: the reference's fs - 1).
+ * Cell positions, the reference's visiting order:
+ *   VFN_MESH_GENERAL comb[m, 28] (+ udf[m, 28, 2] or NULL: corner values 0 / 1), fp32 (f64 = 0) or fp64 (f64 = 1), position p = the
+ *                    cell cells[p] (int64 [m, 3]) or, cells == NULL, the dense raster (m = res^3, p = (i res + j) res + k).  Any comb
+ *                    table: anchors by first argmax, strict comparisons, as combs_to_verts.  A NaN in a comb row: no triangles (np.max
+ *                    is NaN).  Corner values from udf that are not finite in a cell with cut edges set info[1] bit 1.
+ *   VFN_MESH_FUSED   sides[res^3] (the side byte per cell of vfn_grid_unify_direction_sides) + norms[res^3] (fp32): the positions
+ *                    are the (res/2)^3 blocks of 2x2x2 cells of methods.py:184-188 in raster order, cells inside a block in corner
+ *                    order; value of corner v = (bit_v != bit_0 ? +1 : -1) x norm(corner v), norm 0 outside the grid — what
+ *                    make_comb_format's XOR table and pair norms give combs_to_verts.  res even, <= 1024; any non-finite norm in the
+ *                    grid sets info[1] bit 1.
+ * Corner positions (i / res) x size - size / 2 in fp64; all arithmetic fp64 without contraction.  Limits: m < 2^31, 3 T < 2^31.
+ * ============================================================================================= */
+#define VFN_MESH_GENERAL 0
+#define VFN_MESH_FUSED 1
+/* Host copies of the embedded tables: edge_table[256] (cut-edge masks), edge_vertex[12 x 2] (marching_cubes_lookup.EDGE_VERTEX order),
+ * tri_table[256 x 16] (int8, -1 padded). */
+int vfn_mesh_tables(int32_t* edge_table, int32_t* edge_vertex, int8_t* tri_table);
+/* Device workspace (bytes) of the scan over n int32 values that vfn_mesh_count / vfn_mesh_dedup run; -1 on error. */
+int64_t vfn_mesh_scan_workspace_bytes(int64_t n);
+int vfn_mesh_count(int32_t form, const void* comb, const void* udf, int32_t f64, const int64_t* cells, const uint8_t* sides,
+                   const float* norms, int64_t m, int32_t res, double size, double isovalue, int32_t* counts, int32_t* offsets,
+                   int64_t* info, void* scan_ws, int64_t scan_ws_bytes, void* stream);
+int vfn_mesh_emit(int32_t form, const void* comb, const void* udf, int32_t f64, const int64_t* cells, const uint8_t* sides,
+                  const float* norms, int64_t m, int32_t res, double size, double isovalue, const int32_t* counts,
+                  const int32_t* offsets, double* tri_verts, void* stream);
+int vfn_mesh_dedup(const double* tri_verts, int64_t n_slots, int32_t* table, int32_t* owner, int64_t table_size, int32_t* bucket,
+                   int32_t* flags, int32_t* vid, int64_t* info, void* scan_ws, int64_t scan_ws_bytes, void* stream);
+int vfn_mesh_number(const double* tri_verts, int64_t n_slots, const int32_t* owner, const int32_t* bucket, const int32_t* vid,
+                    double* vertices, int64_t* faces, void* stream);
+/* evaluation/methods.py:223-226 for field[n, 3]: norms[n] = torch.norm(field, dim=1) bit for bit with torch's CPU kernel
+ * (sqrt(fma(z, z, fma(y, y, x x))), correctly rounded) and, unit != NULL, unit[n, 3] = F.normalize(field, dim=1) = field / max(norm, 1e-12). */
+int vfn_mesh_field_norms(const float* field, int64_t n, float* norms, float* unit, void* stream);
+
+/* =============================================================================================
  * Optimizer side of a training step over ONE flat fp32 buffer (train/vector_field_nerf_train.py:254-260:
  * torch.nn.utils.clip_grad_norm_(model.parameters(), clip); optimizer.step()).  The unique parameters — and their gradients
  * and Adam moments — are laid out contiguously, sorted into up to four REGIONS [start, end) of equal multiplicity `mult` =

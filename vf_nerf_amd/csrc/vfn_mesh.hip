@@ -1,0 +1,494 @@
+// vfn_mesh.hip — contrastive marching cubes on the device: evaluation/utils/marching_cubes_vt.py:186-315
+// (contrastive_marching_cubes, combs_to_verts :62-101, vertex_interpolate :9-16), the last host stage of the evaluator's mesh
+// pipeline (evaluation/methods.py:140-322).  The reference visits every surface cell in a Python loop and deduplicates vertices
+// in a dict; here:
+//   count     one lane per cell POSITION in the reference's order: it evaluates the cell's eight corner values and case and writes
+//             its triangle count; an ordered device scan (rocPRIM through hipCUB) gives every triangle its output slot.
+//   emit      the same lanes again: the float64 corner positions of the cell's triangles at their slots (3 vertices per triangle,
+//             slot = 3 x triangle + corner: the reference's order of first appearance).
+//   dedup     one lane per vertex slot: an open-addressing table keyed on the canonical 24-byte position (-0.0 folded onto +0.0,
+//             as a Python dict's float equality does).  The bucket is claimed with a 32-bit CAS, full keys are compared (never
+//             hashes alone), and the bucket's owner is the MINIMUM slot (atomicMin), so the result does not depend on the order in
+//             which the atomics arrive.
+//   number    a flag (slot == owner) and a scan give every owner its vertex id (ids in order of first appearance); the owner's raw
+//             bits (the first occurrence's) become vertices[V,3] and every slot's owner id becomes faces[F,3].
+// Two input forms feed the same code: GENERAL (comb [M,28] + udf [M,28,2] + cell indices [M,3] or the dense raster, fp32 or fp64:
+// what the reference's call site hands over, any comb table) and FUSED (the side byte per cell of vfn_grid_unify_direction_sides
+// + the field norms [res^3]: the 28 + 56 values per cell of make_comb_format are never written).  Integer atomics at device
+// scope only; no float atomics.  All arithmetic in fp64 with -ffp-contract=off (build.sh): the reference's numpy expressions,
+// operation for operation.
+#include "vfn_common.h"
+#include <hipcub/hipcub.hpp>
+
+// The classic marching-cubes triangle table (Lorensen & Cline 1987, in the public form of P. Bourke's "Polygonising a scalar field"):
+// edges of up to five triangles per case, -1 terminated.  Corner / edge numbering: corners (0,0,0) (0,1,0) (1,1,0) (1,0,0) (0,0,1)
+// (0,1,1) (1,1,1) (1,0,1) (dimensions i, j, k), edge e joins EDGE_A[e] and EDGE_B[e].  The edge table is not stored: edge e of case c
+// is cut iff its two corners lie on different sides, which is what the classic 256-entry edge table lists.
+#define VFN_MC_TRI_ROWS                                                                                                           \
+    {-1}, {0, 8, 3, -1}, {0, 1, 9, -1}, {1, 8, 3, 9, 8, 1, -1}, {1, 2, 10, -1}, {0, 8, 3, 1, 2, 10, -1}, {9, 2, 10, 0, 2, 9, -1},  \
+    {2, 8, 3, 2, 10, 8, 10, 9, 8, -1}, {3, 11, 2, -1}, {0, 11, 2, 8, 11, 0, -1}, {1, 9, 0, 2, 3, 11, -1},                          \
+    {1, 11, 2, 1, 9, 11, 9, 8, 11, -1}, {3, 10, 1, 11, 10, 3, -1}, {0, 10, 1, 0, 8, 10, 8, 11, 10, -1},                            \
+    {3, 9, 0, 3, 11, 9, 11, 10, 9, -1}, {9, 8, 10, 10, 8, 11, -1}, {4, 7, 8, -1}, {4, 3, 0, 7, 3, 4, -1}, {0, 1, 9, 8, 4, 7, -1},  \
+    {4, 1, 9, 4, 7, 1, 7, 3, 1, -1}, {1, 2, 10, 8, 4, 7, -1}, {3, 4, 7, 3, 0, 4, 1, 2, 10, -1}, {9, 2, 10, 9, 0, 2, 8, 4, 7, -1},  \
+    {2, 10, 9, 2, 9, 7, 2, 7, 3, 7, 9, 4, -1}, {8, 4, 7, 3, 11, 2, -1}, {11, 4, 7, 11, 2, 4, 2, 0, 4, -1},                         \
+    {9, 0, 1, 8, 4, 7, 2, 3, 11, -1}, {4, 7, 11, 9, 4, 11, 9, 11, 2, 9, 2, 1, -1}, {3, 10, 1, 3, 11, 10, 7, 8, 4, -1},             \
+    {1, 11, 10, 1, 4, 11, 1, 0, 4, 7, 11, 4, -1}, {4, 7, 8, 9, 0, 11, 9, 11, 10, 11, 0, 3, -1},                                    \
+    {4, 7, 11, 4, 11, 9, 9, 11, 10, -1}, {9, 5, 4, -1}, {9, 5, 4, 0, 8, 3, -1}, {0, 5, 4, 1, 5, 0, -1},                            \
+    {8, 5, 4, 8, 3, 5, 3, 1, 5, -1}, {1, 2, 10, 9, 5, 4, -1}, {3, 0, 8, 1, 2, 10, 4, 9, 5, -1}, {5, 2, 10, 5, 4, 2, 4, 0, 2, -1},  \
+    {2, 10, 5, 3, 2, 5, 3, 5, 4, 3, 4, 8, -1}, {9, 5, 4, 2, 3, 11, -1}, {0, 11, 2, 0, 8, 11, 4, 9, 5, -1},                         \
+    {0, 5, 4, 0, 1, 5, 2, 3, 11, -1}, {2, 1, 5, 2, 5, 8, 2, 8, 11, 4, 8, 5, -1}, {10, 3, 11, 10, 1, 3, 9, 5, 4, -1},               \
+    {4, 9, 5, 0, 8, 1, 8, 10, 1, 8, 11, 10, -1}, {5, 4, 0, 5, 0, 11, 5, 11, 10, 11, 0, 3, -1},                                     \
+    {5, 4, 8, 5, 8, 10, 10, 8, 11, -1}, {9, 7, 8, 5, 7, 9, -1}, {9, 3, 0, 9, 5, 3, 5, 7, 3, -1}, {0, 7, 8, 0, 1, 7, 1, 5, 7, -1},  \
+    {1, 5, 3, 3, 5, 7, -1}, {9, 7, 8, 9, 5, 7, 10, 1, 2, -1}, {10, 1, 2, 9, 5, 0, 5, 3, 0, 5, 7, 3, -1},                           \
+    {8, 0, 2, 8, 2, 5, 8, 5, 7, 10, 5, 2, -1}, {2, 10, 5, 2, 5, 3, 3, 5, 7, -1}, {7, 9, 5, 7, 8, 9, 3, 11, 2, -1},                 \
+    {9, 5, 7, 9, 7, 2, 9, 2, 0, 2, 7, 11, -1}, {2, 3, 11, 0, 1, 8, 1, 7, 8, 1, 5, 7, -1}, {11, 2, 1, 11, 1, 7, 7, 1, 5, -1},       \
+    {9, 5, 8, 8, 5, 7, 10, 1, 3, 10, 3, 11, -1}, {5, 7, 0, 5, 0, 9, 7, 11, 0, 1, 0, 10, 11, 10, 0, -1},                            \
+    {11, 10, 0, 11, 0, 3, 10, 5, 0, 8, 0, 7, 5, 7, 0, -1}, {11, 10, 5, 7, 11, 5, -1}, {10, 6, 5, -1}, {0, 8, 3, 5, 10, 6, -1},     \
+    {9, 0, 1, 5, 10, 6, -1}, {1, 8, 3, 1, 9, 8, 5, 10, 6, -1}, {1, 6, 5, 2, 6, 1, -1}, {1, 6, 5, 1, 2, 6, 3, 0, 8, -1},            \
+    {9, 6, 5, 9, 0, 6, 0, 2, 6, -1}, {5, 9, 8, 5, 8, 2, 5, 2, 6, 3, 2, 8, -1}, {2, 3, 11, 10, 6, 5, -1},                           \
+    {11, 0, 8, 11, 2, 0, 10, 6, 5, -1}, {0, 1, 9, 2, 3, 11, 5, 10, 6, -1}, {5, 10, 6, 1, 9, 2, 9, 11, 2, 9, 8, 11, -1},            \
+    {6, 3, 11, 6, 5, 3, 5, 1, 3, -1}, {0, 8, 11, 0, 11, 5, 0, 5, 1, 5, 11, 6, -1}, {3, 11, 6, 0, 3, 6, 0, 6, 5, 0, 5, 9, -1},      \
+    {6, 5, 9, 6, 9, 11, 11, 9, 8, -1}, {5, 10, 6, 4, 7, 8, -1}, {4, 3, 0, 4, 7, 3, 6, 5, 10, -1}, {1, 9, 0, 5, 10, 6, 8, 4, 7, -1}, \
+    {10, 6, 5, 1, 9, 7, 1, 7, 3, 7, 9, 4, -1}, {6, 1, 2, 6, 5, 1, 4, 7, 8, -1}, {1, 2, 5, 5, 2, 6, 3, 0, 4, 3, 4, 7, -1},          \
+    {8, 4, 7, 9, 0, 5, 0, 6, 5, 0, 2, 6, -1}, {7, 3, 9, 7, 9, 4, 3, 2, 9, 5, 9, 6, 2, 6, 9, -1},                                   \
+    {3, 11, 2, 7, 8, 4, 10, 6, 5, -1}, {5, 10, 6, 4, 7, 2, 4, 2, 0, 2, 7, 11, -1}, {0, 1, 9, 4, 7, 8, 2, 3, 11, 5, 10, 6, -1},     \
+    {9, 2, 1, 9, 11, 2, 9, 4, 11, 7, 11, 4, 5, 10, 6, -1}, {8, 4, 7, 3, 11, 5, 3, 5, 1, 5, 11, 6, -1},                             \
+    {5, 1, 11, 5, 11, 6, 1, 0, 11, 7, 11, 4, 0, 4, 11, -1}, {0, 5, 9, 0, 6, 5, 0, 3, 6, 11, 6, 3, 8, 4, 7, -1},                    \
+    {6, 5, 9, 6, 9, 11, 4, 7, 9, 7, 11, 9, -1}, {10, 4, 9, 6, 4, 10, -1}, {4, 10, 6, 4, 9, 10, 0, 8, 3, -1},                       \
+    {10, 0, 1, 10, 6, 0, 6, 4, 0, -1}, {8, 3, 1, 8, 1, 6, 8, 6, 4, 6, 1, 10, -1}, {1, 4, 9, 1, 2, 4, 2, 6, 4, -1},                 \
+    {3, 0, 8, 1, 2, 9, 2, 4, 9, 2, 6, 4, -1}, {0, 2, 4, 4, 2, 6, -1}, {8, 3, 2, 8, 2, 4, 4, 2, 6, -1},                             \
+    {10, 4, 9, 10, 6, 4, 11, 2, 3, -1}, {0, 8, 2, 2, 8, 11, 4, 9, 10, 4, 10, 6, -1}, {3, 11, 2, 0, 1, 6, 0, 6, 4, 6, 1, 10, -1},   \
+    {6, 4, 1, 6, 1, 10, 4, 8, 1, 2, 1, 11, 8, 11, 1, -1}, {9, 6, 4, 9, 3, 6, 9, 1, 3, 11, 6, 3, -1},                               \
+    {8, 11, 1, 8, 1, 0, 11, 6, 1, 9, 1, 4, 6, 4, 1, -1}, {3, 11, 6, 3, 6, 0, 0, 6, 4, -1}, {6, 4, 8, 11, 6, 8, -1},                \
+    {7, 10, 6, 7, 8, 10, 8, 9, 10, -1}, {0, 7, 3, 0, 10, 7, 0, 9, 10, 6, 7, 10, -1}, {10, 6, 7, 1, 10, 7, 1, 7, 8, 1, 8, 0, -1},   \
+    {10, 6, 7, 10, 7, 1, 1, 7, 3, -1}, {1, 2, 6, 1, 6, 8, 1, 8, 9, 8, 6, 7, -1}, {2, 6, 9, 2, 9, 1, 6, 7, 9, 0, 9, 3, 7, 3, 9, -1}, \
+    {7, 8, 0, 7, 0, 6, 6, 0, 2, -1}, {7, 3, 2, 6, 7, 2, -1}, {2, 3, 11, 10, 6, 8, 10, 8, 9, 8, 6, 7, -1},                          \
+    {2, 0, 7, 2, 7, 11, 0, 9, 7, 6, 7, 10, 9, 10, 7, -1}, {1, 8, 0, 1, 7, 8, 1, 10, 7, 6, 7, 10, 2, 3, 11, -1},                    \
+    {11, 2, 1, 11, 1, 7, 10, 6, 1, 6, 7, 1, -1}, {8, 9, 6, 8, 6, 7, 9, 1, 6, 11, 6, 3, 1, 3, 6, -1}, {0, 9, 1, 11, 6, 7, -1},      \
+    {7, 8, 0, 7, 0, 6, 3, 11, 0, 11, 6, 0, -1}, {7, 11, 6, -1}, {7, 6, 11, -1}, {3, 0, 8, 11, 7, 6, -1}, {0, 1, 9, 11, 7, 6, -1},  \
+    {8, 1, 9, 8, 3, 1, 11, 7, 6, -1}, {10, 1, 2, 6, 11, 7, -1}, {1, 2, 10, 3, 0, 8, 6, 11, 7, -1}, {2, 9, 0, 2, 10, 9, 6, 11, 7, -1}, \
+    {6, 11, 7, 2, 10, 3, 10, 8, 3, 10, 9, 8, -1}, {7, 2, 3, 6, 2, 7, -1}, {7, 0, 8, 7, 6, 0, 6, 2, 0, -1},                         \
+    {2, 7, 6, 2, 3, 7, 0, 1, 9, -1}, {1, 6, 2, 1, 8, 6, 1, 9, 8, 8, 7, 6, -1}, {10, 7, 6, 10, 1, 7, 1, 3, 7, -1},                  \
+    {10, 7, 6, 1, 7, 10, 1, 8, 7, 1, 0, 8, -1}, {0, 3, 7, 0, 7, 10, 0, 10, 9, 6, 10, 7, -1}, {7, 6, 10, 7, 10, 8, 8, 10, 9, -1},   \
+    {6, 8, 4, 11, 8, 6, -1}, {3, 6, 11, 3, 0, 6, 0, 4, 6, -1}, {8, 6, 11, 8, 4, 6, 9, 0, 1, -1},                                   \
+    {9, 4, 6, 9, 6, 3, 9, 3, 1, 11, 3, 6, -1}, {6, 8, 4, 6, 11, 8, 2, 10, 1, -1}, {1, 2, 10, 3, 0, 11, 0, 6, 11, 0, 4, 6, -1},     \
+    {4, 11, 8, 4, 6, 11, 0, 2, 9, 2, 10, 9, -1}, {10, 9, 3, 10, 3, 2, 9, 4, 3, 11, 3, 6, 4, 6, 3, -1},                             \
+    {8, 2, 3, 8, 4, 2, 4, 6, 2, -1}, {0, 4, 2, 4, 6, 2, -1}, {1, 9, 0, 2, 3, 4, 2, 4, 6, 4, 3, 8, -1},                             \
+    {1, 9, 4, 1, 4, 2, 2, 4, 6, -1}, {8, 1, 3, 8, 6, 1, 8, 4, 6, 6, 10, 1, -1}, {10, 1, 0, 10, 0, 6, 6, 0, 4, -1},                 \
+    {4, 6, 3, 4, 3, 8, 6, 10, 3, 0, 3, 9, 10, 9, 3, -1}, {10, 9, 4, 6, 10, 4, -1}, {4, 9, 5, 7, 6, 11, -1},                        \
+    {0, 8, 3, 4, 9, 5, 11, 7, 6, -1}, {5, 0, 1, 5, 4, 0, 7, 6, 11, -1}, {11, 7, 6, 8, 3, 4, 3, 5, 4, 3, 1, 5, -1},                 \
+    {9, 5, 4, 10, 1, 2, 7, 6, 11, -1}, {6, 11, 7, 1, 2, 10, 0, 8, 3, 4, 9, 5, -1}, {7, 6, 11, 5, 4, 10, 4, 2, 10, 4, 0, 2, -1},    \
+    {3, 4, 8, 3, 5, 4, 3, 2, 5, 10, 5, 2, 11, 7, 6, -1}, {7, 2, 3, 7, 6, 2, 5, 4, 9, -1}, {9, 5, 4, 0, 8, 6, 0, 6, 2, 6, 8, 7, -1}, \
+    {3, 6, 2, 3, 7, 6, 1, 5, 0, 5, 4, 0, -1}, {6, 2, 8, 6, 8, 7, 2, 1, 8, 4, 8, 5, 1, 5, 8, -1},                                   \
+    {9, 5, 4, 10, 1, 6, 1, 7, 6, 1, 3, 7, -1}, {1, 6, 10, 1, 7, 6, 1, 0, 7, 8, 7, 0, 9, 5, 4, -1},                                 \
+    {4, 0, 10, 4, 10, 5, 0, 3, 10, 6, 10, 7, 3, 7, 10, -1}, {7, 6, 10, 7, 10, 8, 5, 4, 10, 4, 8, 10, -1},                          \
+    {6, 9, 5, 6, 11, 9, 11, 8, 9, -1}, {3, 6, 11, 0, 6, 3, 0, 5, 6, 0, 9, 5, -1}, {0, 11, 8, 0, 5, 11, 0, 1, 5, 5, 6, 11, -1},     \
+    {6, 11, 3, 6, 3, 5, 5, 3, 1, -1}, {1, 2, 10, 9, 5, 11, 9, 11, 8, 11, 5, 6, -1},                                                \
+    {0, 11, 3, 0, 6, 11, 0, 9, 6, 5, 6, 9, 1, 2, 10, -1}, {11, 8, 5, 11, 5, 6, 8, 0, 5, 10, 5, 2, 0, 2, 5, -1},                    \
+    {6, 11, 3, 6, 3, 5, 2, 10, 3, 10, 5, 3, -1}, {5, 8, 9, 5, 2, 8, 5, 6, 2, 3, 8, 2, -1}, {9, 5, 6, 9, 6, 0, 0, 6, 2, -1},        \
+    {1, 5, 8, 1, 8, 0, 5, 6, 8, 3, 8, 2, 6, 2, 8, -1}, {1, 5, 6, 2, 1, 6, -1}, {1, 3, 6, 1, 6, 10, 3, 8, 6, 5, 6, 9, 8, 9, 6, -1}, \
+    {10, 1, 0, 10, 0, 6, 9, 5, 0, 5, 6, 0, -1}, {0, 3, 8, 5, 6, 10, -1}, {10, 5, 6, -1}, {11, 5, 10, 7, 5, 11, -1},                \
+    {11, 5, 10, 11, 7, 5, 8, 3, 0, -1}, {5, 11, 7, 5, 10, 11, 1, 9, 0, -1}, {10, 7, 5, 10, 11, 7, 9, 8, 1, 8, 3, 1, -1},           \
+    {11, 1, 2, 11, 7, 1, 7, 5, 1, -1}, {0, 8, 3, 1, 2, 7, 1, 7, 5, 7, 2, 11, -1}, {9, 7, 5, 9, 2, 7, 9, 0, 2, 2, 11, 7, -1},       \
+    {7, 5, 2, 7, 2, 11, 5, 9, 2, 3, 2, 8, 9, 8, 2, -1}, {2, 5, 10, 2, 3, 5, 3, 7, 5, -1}, {8, 2, 0, 8, 5, 2, 8, 7, 5, 10, 2, 5, -1}, \
+    {9, 0, 1, 5, 10, 3, 5, 3, 7, 3, 10, 2, -1}, {9, 8, 2, 9, 2, 1, 8, 7, 2, 10, 2, 5, 7, 5, 2, -1}, {1, 3, 5, 3, 7, 5, -1},        \
+    {0, 8, 7, 0, 7, 1, 1, 7, 5, -1}, {9, 0, 3, 9, 3, 5, 5, 3, 7, -1}, {9, 8, 7, 5, 9, 7, -1}, {5, 8, 4, 5, 10, 8, 10, 11, 8, -1},  \
+    {5, 0, 4, 5, 11, 0, 5, 10, 11, 11, 3, 0, -1}, {0, 1, 9, 8, 4, 10, 8, 10, 11, 10, 4, 5, -1},                                    \
+    {10, 11, 4, 10, 4, 5, 11, 3, 4, 9, 4, 1, 3, 1, 4, -1}, {2, 5, 1, 2, 8, 5, 2, 11, 8, 4, 5, 8, -1},                              \
+    {0, 4, 11, 0, 11, 3, 4, 5, 11, 2, 11, 1, 5, 1, 11, -1}, {0, 2, 5, 0, 5, 9, 2, 11, 5, 4, 5, 8, 11, 8, 5, -1},                   \
+    {9, 4, 5, 2, 11, 3, -1}, {2, 5, 10, 3, 5, 2, 3, 4, 5, 3, 8, 4, -1}, {5, 10, 2, 5, 2, 4, 4, 2, 0, -1},                          \
+    {3, 10, 2, 3, 5, 10, 3, 8, 5, 4, 5, 8, 0, 1, 9, -1}, {5, 10, 2, 5, 2, 4, 1, 9, 2, 9, 4, 2, -1}, {8, 4, 5, 8, 5, 3, 3, 5, 1, -1}, \
+    {0, 4, 5, 1, 0, 5, -1}, {8, 4, 5, 8, 5, 3, 9, 0, 5, 0, 3, 5, -1}, {9, 4, 5, -1}, {4, 11, 7, 4, 9, 11, 9, 10, 11, -1},          \
+    {0, 8, 3, 4, 9, 7, 9, 11, 7, 9, 10, 11, -1}, {1, 10, 11, 1, 11, 4, 1, 4, 0, 7, 4, 11, -1},                                     \
+    {3, 1, 4, 3, 4, 8, 1, 10, 4, 7, 4, 11, 10, 11, 4, -1}, {4, 11, 7, 9, 11, 4, 9, 2, 11, 9, 1, 2, -1},                            \
+    {9, 7, 4, 9, 11, 7, 9, 1, 11, 2, 11, 1, 0, 8, 3, -1}, {11, 7, 4, 11, 4, 2, 2, 4, 0, -1}, {11, 7, 4, 11, 4, 2, 8, 3, 4, 3, 2, 4, -1}, \
+    {2, 9, 10, 2, 7, 9, 2, 3, 7, 7, 4, 9, -1}, {9, 10, 7, 9, 7, 4, 10, 2, 7, 8, 7, 0, 2, 0, 7, -1},                                \
+    {3, 7, 10, 3, 10, 2, 7, 4, 10, 1, 10, 0, 4, 0, 10, -1}, {1, 10, 2, 8, 7, 4, -1}, {4, 9, 1, 4, 1, 7, 7, 1, 3, -1},              \
+    {4, 9, 1, 4, 1, 7, 0, 8, 1, 8, 7, 1, -1}, {4, 0, 3, 7, 4, 3, -1}, {4, 8, 7, -1}, {9, 10, 8, 10, 11, 8, -1},                    \
+    {3, 0, 9, 3, 9, 11, 11, 9, 10, -1}, {0, 1, 10, 0, 10, 8, 8, 10, 11, -1}, {3, 1, 10, 11, 3, 10, -1},                            \
+    {1, 2, 11, 1, 11, 9, 9, 11, 8, -1}, {3, 0, 9, 3, 9, 11, 1, 2, 9, 2, 11, 9, -1}, {0, 2, 11, 8, 0, 11, -1}, {3, 2, 11, -1},      \
+    {2, 3, 8, 2, 8, 10, 10, 8, 9, -1}, {9, 10, 2, 0, 9, 2, -1}, {2, 3, 8, 2, 8, 10, 0, 1, 8, 1, 10, 8, -1}, {1, 10, 2, -1},        \
+    {1, 3, 8, 9, 1, 8, -1}, {0, 9, 1, -1}, {0, 3, 8, -1}, {-1}
+
+namespace {
+
+// (entries after a row's -1 are never read; the host copy pads them with -1 for vfn_mesh_tables)
+const signed char TRI_HOST[256][16] = {VFN_MC_TRI_ROWS};
+__device__ __constant__ signed char TRI[256][16] = {VFN_MC_TRI_ROWS};
+// marching_cubes_lookup.EDGE_VERTEX order: edge 3 is (0, 3), edge 7 is (4, 7)
+const int EDGE_A_HOST[12] = {0, 1, 2, 0, 4, 5, 6, 4, 0, 1, 2, 3};
+const int EDGE_B_HOST[12] = {1, 2, 3, 3, 5, 6, 7, 7, 4, 5, 6, 7};
+__device__ __constant__ int EDGE_A[12] = {0, 1, 2, 0, 4, 5, 6, 4, 0, 1, 2, 3};
+__device__ __constant__ int EDGE_B[12] = {1, 2, 3, 3, 5, 6, 7, 7, 4, 5, 6, 7};
+// marching_cubes_vt.inc: corner q of cell (i, j, k) is (i, j, k) + INC[q]
+__device__ __constant__ int INC[8][3] = {{0, 0, 0}, {0, 1, 0}, {1, 1, 0}, {1, 0, 0}, {0, 0, 1}, {0, 1, 1}, {1, 1, 1}, {1, 0, 1}};
+// the 28 corner pairs (a < b) in the order of marching_cubes_vt.combs, and pair index of (a, b) for a < b
+__device__ __constant__ unsigned char PA[28] = {0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 5, 5, 6};
+__device__ __constant__ unsigned char PB[28] = {1, 2, 3, 4, 5, 6, 7, 2, 3, 4, 5, 6, 7, 3, 4, 5, 6, 7, 4, 5, 6, 7, 5, 6, 7, 6, 7, 7};
+
+__device__ __forceinline__ int pair_index(int a, int b) {     // a < b
+    return a * 7 - a * (a - 1) / 2 + (b - a - 1);
+}
+
+constexpr unsigned STATUS_NONFINITE = 1u, STATUS_INDEX = 2u;
+
+struct MeshArgs {
+    int form;                     // VFN_MESH_GENERAL | VFN_MESH_FUSED
+    const void* comb;             // general: [m, 28]
+    const void* udf;              // general: [m, 28, 2] or NULL
+    int f64;                      // general: comb / udf are double (else float)
+    const long long* cells;       // general: [m, 3] or NULL (the dense raster: m == res^3)
+    const unsigned char* sides;   // fused: [res^3]
+    const float* norms;           // fused: [res^3]
+    long long m;                  // cell positions
+    int res;
+    double size, iso;
+};
+
+__device__ __forceinline__ double grid_pos(int i, int res, double size) {
+    return (double)i / (double)res * size - size / 2.0;     // mgrid / res * size - size / 2 (no contraction: -ffp-contract=off)
+}
+
+__device__ __forceinline__ bool finite(double x) { return x - x == 0.0; }
+
+// combs_to_verts (:62-101) on one row of the general form: the corner values, and whether they came from udf (max comb > 0.5)
+template <typename T>
+__device__ bool general_values(const T* __restrict__ comb, const T* __restrict__ udf, double v[8]) {
+    T mx = comb[0];
+    int am = 0;
+    bool nan = comb[0] != comb[0];
+    for (int q = 1; q < 28; ++q) {
+        const T x = comb[q];
+        nan |= x != x;
+        if (x > mx) { mx = x; am = q; }                           // first maximum (np.argmax)
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = 0.0;
+    if (nan || !(mx > (T)0.5)) return false;                     // (np.max of a row holding a NaN is NaN: not > 0.5)
+    const int a0 = PA[am], a1 = PB[am];
+    unsigned cls1 = 1u << a1;
+    for (int q = 0; q < 8; ++q) {
+        if (q == a0 || q == a1) continue;
+        const T c0 = comb[pair_index(min(q, a0), max(q, a0))], c1 = comb[pair_index(min(q, a1), max(q, a1))];
+        if (c0 > c1) cls1 |= 1u << q;
+    }
+    for (int q = 0; q < 8; ++q) {
+        const bool one = (cls1 >> q) & 1u;
+        if (!udf) v[q] = one ? 1.0 : 0.0;
+        else v[q] = (one ? 1.0 : -1.0) * (double)udf[q == 0 ? 0 : 2 * (q - 1) + 1];   // idx_in_combs: [0,0] [0,1] [1,1] .. [6,1]
+    }
+    return true;
+}
+
+// one cell position: its grid coordinates, corner values and case.  Returns false for a position that yields nothing.
+__device__ bool eval_cell(const MeshArgs& a, long long p, int c[3], double v[8], int& top, unsigned& status) {
+    const long long r = a.res;
+    bool from_norms;
+    if (a.form == VFN_MESH_FUSED) {
+        // evaluation/methods.py:184-188: (res/2)^3 blocks of 2x2x2 cells in raster order, corner order inside a block
+        const long long blk = p >> 3, h = r >> 1;
+        const int q = (int)(p & 7);
+        c[0] = (int)(blk / (h * h)) * 2 + INC[q][0];
+        c[1] = (int)((blk / h) % h) * 2 + INC[q][1];
+        c[2] = (int)(blk % h) * 2 + INC[q][2];
+        const long long cell = ((long long)c[0] * r + c[1]) * r + c[2];
+        if (!finite((double)a.norms[cell])) status |= STATUS_NONFINITE;      // every grid point is corner 0 of one position
+        const unsigned bits = a.sides[cell];
+        if (bits == 0u || bits == 0xffu) return false;           // comb all zero: max 0 <= 0.5, no triangles
+        // comb(a, b) = bit_a ^ bit_b: the anchor pair is (0, first corner unlike 0), and corner v sides with the second anchor iff
+        // its bit differs from corner 0's: value = (bit_v != bit_0 ? +1 : -1) x norm(corner v), norm 0 outside the grid
+        const unsigned b0 = bits & 1u;
+#pragma unroll
+        for (int q2 = 0; q2 < 8; ++q2) {
+            const int ii = c[0] + INC[q2][0], jj = c[1] + INC[q2][1], kk = c[2] + INC[q2][2];
+            const float nv = (ii < r && jj < r && kk < r) ? a.norms[((long long)ii * r + jj) * r + kk] : 0.f;
+            v[q2] = (((bits >> q2) & 1u) != b0 ? 1.0 : -1.0) * (double)nv;
+        }
+        from_norms = true;
+    } else {
+        if (a.cells) {
+            for (int d = 0; d < 3; ++d) {
+                const long long x = a.cells[p * 3 + d];
+                if (x < 0 || x >= r) { status |= STATUS_INDEX; return false; }
+                c[d] = (int)x;
+            }
+        } else {
+            c[0] = (int)(p / (r * r)); c[1] = (int)((p / r) % r); c[2] = (int)(p % r);
+        }
+        if (a.f64) from_norms = general_values<double>((const double*)a.comb + p * 28, a.udf ? (const double*)a.udf + p * 56 : nullptr, v);
+        else from_norms = general_values<float>((const float*)a.comb + p * 28, a.udf ? (const float*)a.udf + p * 56 : nullptr, v);
+    }
+    int t = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) t |= (v[q] < a.iso ? 1 : 0) << q;
+    top = t;
+    if (t == 0 || t == 255) return false;                      // EDGE_TABLE[0] = EDGE_TABLE[255] = 0: no edge is cut
+    if (from_norms && a.form != VFN_MESH_FUSED)
+        for (int q = 0; q < 8; ++q)
+            if (!finite(v[q])) status |= STATUS_NONFINITE;
+    return true;
+}
+
+__device__ __forceinline__ int tri_count(int top) {
+    int n = 0;
+    while (n < 5 && TRI[top][3 * n] >= 0) ++n;
+    return n;
+}
+
+__global__ __launch_bounds__(256) void vfn_mesh_count_kernel(MeshArgs a, int* __restrict__ counts, long long* __restrict__ info) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned status = 0;
+    if (p < a.m) {
+        int c[3], top = 0;
+        double v[8];
+        counts[p] = eval_cell(a, p, c, v, top, status) ? tri_count(top) : 0;
+    }
+    // (one atomic per wave that saw a bad input)
+    const unsigned long long any = __ballot(status != 0u);
+    if (any) {
+        unsigned all = status;
+        for (int o = 32; o > 0; o >>= 1) all |= (unsigned)__shfl_xor((int)all, o, 64);
+        if ((threadIdx.x & 63) == (unsigned)__builtin_ctzll(any)) atomicOr((unsigned long long*)&info[1], (unsigned long long)all);
+    }
+}
+
+__global__ void vfn_mesh_total_kernel(const int* __restrict__ incl, long long last, long long* __restrict__ info, int slot) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) info[slot] = last >= 0 ? (long long)incl[last] : 0ll;
+}
+
+// vertex_interpolate (:9-16): swap when p1 > p2 in any component, interpolate only when |v1 - v2| > 1e-5
+__device__ __forceinline__ void edge_vertex(const double P[8][3], const double v[8], int e, double iso, double out[3]) {
+    int e1 = EDGE_A[e], e2 = EDGE_B[e];
+    if (P[e1][0] > P[e2][0] || P[e1][1] > P[e2][1] || P[e1][2] > P[e2][2]) { const int t = e1; e1 = e2; e2 = t; }
+    const double v1 = v[e1], v2 = v[e2];
+    if (fabs(v1 - v2) > 1e-5) {
+        for (int d = 0; d < 3; ++d) out[d] = P[e1][d] + (P[e2][d] - P[e1][d]) * (iso - v1) / (v2 - v1);
+    } else {
+        for (int d = 0; d < 3; ++d) out[d] = P[e1][d];
+    }
+}
+
+__global__ __launch_bounds__(256) void vfn_mesh_emit_kernel(MeshArgs a, const int* __restrict__ counts, const int* __restrict__ incl,
+                                                            double* __restrict__ tri_verts) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.m) return;
+    const int n = counts[p];
+    if (n == 0) return;
+    int c[3], top = 0;
+    double v[8];
+    unsigned status = 0;
+    if (!eval_cell(a, p, c, v, top, status)) return;
+    double P[8][3];
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+        for (int d = 0; d < 3; ++d) P[q][d] = grid_pos(c[d] + INC[q][d], a.res, a.size);
+    const long long slot0 = (long long)(incl[p] - n) * 3;
+    for (int t = 0; t < n; ++t)
+        for (int k = 0; k < 3; ++k) {
+            double x[3];
+            edge_vertex(P, v, TRI[top][3 * t + k], a.iso, x);
+            double* o = tri_verts + (slot0 + 3 * t + k) * 3;
+            o[0] = x[0]; o[1] = x[1]; o[2] = x[2];
+        }
+}
+
+// ---- deduplication ----------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long canon(double x) {
+    return x == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(x);     // 0.0 == -0.0 in a dict: one key
+}
+
+__device__ __forceinline__ unsigned long long mix(unsigned long long h) {
+    h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
+    return h;
+}
+
+__global__ void vfn_mesh_table_init_kernel(int* __restrict__ table, int* __restrict__ owner, long long n) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { table[i] = -1; owner[i] = 0x7fffffff; }
+}
+
+__global__ __launch_bounds__(256) void vfn_mesh_dedup_kernel(const double* __restrict__ tv, long long n_slots, int* __restrict__ table,
+                                                             int* __restrict__ owner, long long mask, int* __restrict__ bucket) {
+    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_slots) return;
+    const unsigned long long k0 = canon(tv[s * 3]), k1 = canon(tv[s * 3 + 1]), k2 = canon(tv[s * 3 + 2]);
+    long long h = (long long)(mix(k0 ^ mix(k1 ^ mix(k2))) & (unsigned long long)mask);
+    for (;;) {
+        int cur = __hip_atomic_load(&table[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur < 0) {
+            const int prev = atomicCAS(&table[h], -1, (int)s);
+            if (prev < 0) break;                                  // claimed: this slot's key lives in bucket h
+            cur = prev;
+        }
+        // the bucket holds some slot's key (written by the emit launch, complete before this one started): compare all 24 bytes
+        if (canon(tv[(long long)cur * 3]) == k0 && canon(tv[(long long)cur * 3 + 1]) == k1 && canon(tv[(long long)cur * 3 + 2]) == k2) break;
+        h = (h + 1) & mask;
+    }
+    bucket[s] = (int)h;
+    atomicMin(&owner[h], (int)s);                                  // the first appearance owns the key, whoever claimed the bucket
+}
+
+__global__ __launch_bounds__(256) void vfn_mesh_flag_kernel(const int* __restrict__ owner, const int* __restrict__ bucket, long long n_slots,
+                                                            int* __restrict__ flag) {
+    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < n_slots) flag[s] = owner[bucket[s]] == (int)s ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void vfn_mesh_number_kernel(const double* __restrict__ tv, long long n_slots, const int* __restrict__ owner,
+                                                              const int* __restrict__ bucket, const int* __restrict__ vid_incl,
+                                                              double* __restrict__ vertices, long long* __restrict__ faces) {
+    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_slots) return;
+    const int o = owner[bucket[s]];
+    const int id = vid_incl[o] - 1;                                // the owner is flagged: its inclusive count includes itself
+    faces[s] = id;
+    if (o == (int)s) {
+        vertices[(long long)id * 3] = tv[s * 3];
+        vertices[(long long)id * 3 + 1] = tv[s * 3 + 1];
+        vertices[(long long)id * 3 + 2] = tv[s * 3 + 2];
+    }
+}
+
+// evaluation/methods.py:223-226 on the device: norms = torch.norm(x, dim=1) as torch's CPU kernel evaluates it (the FMA chain
+// fma(z, z, fma(y, y, x x)), then a correctly rounded sqrt) and unit = F.normalize(x, dim=1) = x / max(norm, 1e-12)
+__global__ __launch_bounds__(256) void vfn_mesh_field_norms_kernel(const float* __restrict__ x, long long n, float* __restrict__ norms,
+                                                                   float* __restrict__ unit) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float a = x[i * 3], b = x[i * 3 + 1], c = x[i * 3 + 2];
+    const float nr = sqrtf(fmaf(c, c, fmaf(b, b, a * a)));
+    norms[i] = nr;
+    if (unit) {
+        const float d = fmaxf(nr, 1e-12f);
+        unit[i * 3] = a / d; unit[i * 3 + 1] = b / d; unit[i * 3 + 2] = c / d;
+    }
+}
+
+inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
+
+int scan_bytes(long long n, size_t* bytes) {
+    *bytes = 0;
+    const hipError_t e = hipcub::DeviceScan::InclusiveSum(nullptr, *bytes, (const int*)nullptr, (int*)nullptr, (int)n);
+    return e == hipSuccess ? VFN_OK : VFN_ERR_LAUNCH;
+}
+
+int inclusive_scan(const int* in, int* out, long long n, void* ws, long long ws_bytes, hipStream_t s, const char* what) {
+    size_t need = 0;
+    VFN_REQUIRE(scan_bytes(n, &need) == VFN_OK, "%s: scan size query failed", what);
+    VFN_REQUIRE(ws && (long long)need <= ws_bytes, "%s: scan workspace of %lld bytes < %lld needed", what, ws_bytes, (long long)need);
+    const hipError_t e = hipcub::DeviceScan::InclusiveSum(ws, need, in, out, (int)n, s);
+    if (e != hipSuccess) {
+        vfn_set_error("%s: scan failed: %s", what, hipGetErrorString(e));
+        return VFN_ERR_LAUNCH;
+    }
+    return VFN_OK;
+}
+
+int make_args(MeshArgs& a, int32_t form, const void* comb, const void* udf, int32_t f64, const int64_t* cells, const uint8_t* sides,
+              const float* norms, int64_t m, int32_t res, double size, double isovalue, const char* what) {
+    a = MeshArgs{};
+    a.form = form; a.comb = comb; a.udf = udf; a.f64 = f64; a.cells = (const long long*)cells; a.sides = sides; a.norms = norms;
+    a.m = m; a.res = res; a.size = size; a.iso = isovalue;
+    VFN_REQUIRE(res >= 1 && res <= 2048 && m >= 0 && m < (1ll << 31), "%s: bad res %d / m %lld", what, res, (long long)m);
+    if (form == VFN_MESH_FUSED) {
+        VFN_REQUIRE(sides && norms, "%s: fused form needs sides and norms", what);
+        VFN_REQUIRE(res % 2 == 0 && res <= 1024 && m == (int64_t)res * res * res, "%s: fused form needs an even res <= 1024 and m = res^3", what);
+    } else {
+        VFN_REQUIRE(form == VFN_MESH_GENERAL, "%s: unknown form %d", what, form);
+        VFN_REQUIRE(m == 0 || comb, "%s: NULL comb", what);
+        VFN_REQUIRE(cells || m == (int64_t)res * res * res, "%s: dense form needs m = res^3", what);
+    }
+    return VFN_OK;
+}
+
+}  // namespace
+
+extern "C" int vfn_mesh_tables(int32_t* edge_table, int32_t* edge_vertex, int8_t* tri_table) {
+    VFN_REQUIRE(edge_table && edge_vertex && tri_table, "vfn_mesh_tables: NULL argument");
+    for (int c = 0; c < 256; ++c) {
+        int m = 0;
+        for (int e = 0; e < 12; ++e)
+            if (((c >> EDGE_A_HOST[e]) ^ (c >> EDGE_B_HOST[e])) & 1) m |= 1 << e;
+        edge_table[c] = m;
+        bool ended = false;
+        for (int t = 0; t < 16; ++t) {
+            ended = ended || TRI_HOST[c][t] < 0;
+            tri_table[c * 16 + t] = ended ? (int8_t)-1 : (int8_t)TRI_HOST[c][t];
+        }
+    }
+    for (int e = 0; e < 12; ++e) { edge_vertex[2 * e] = EDGE_A_HOST[e]; edge_vertex[2 * e + 1] = EDGE_B_HOST[e]; }
+    return VFN_OK;
+}
+
+extern "C" int64_t vfn_mesh_scan_workspace_bytes(int64_t n) {
+    size_t b = 0;
+    if (n < 1) n = 1;
+    if (scan_bytes(n, &b) != VFN_OK) return -1;
+    return (int64_t)b;
+}
+
+extern "C" int vfn_mesh_count(int32_t form, const void* comb, const void* udf, int32_t f64, const int64_t* cells, const uint8_t* sides,
+                              const float* norms, int64_t m, int32_t res, double size, double isovalue, int32_t* counts, int32_t* offsets,
+                              int64_t* info, void* scan_ws, int64_t scan_ws_bytes, void* stream) {
+    MeshArgs a;
+    const int rc = make_args(a, form, comb, udf, f64, cells, sides, norms, m, res, size, isovalue, "vfn_mesh_count");
+    if (rc != VFN_OK) return rc;
+    VFN_REQUIRE(info && (m == 0 || (counts && offsets)), "vfn_mesh_count: NULL output");
+    hipStream_t s = (hipStream_t)stream;
+    if (m > 0) {
+        hipLaunchKernelGGL(vfn_mesh_count_kernel, dim3(blocks_for(m)), dim3(256), 0, s, a, (int*)counts, (long long*)info);
+        const int r2 = inclusive_scan(counts, offsets, m, scan_ws, scan_ws_bytes, s, "vfn_mesh_count");
+        if (r2 != VFN_OK) return r2;
+    }
+    hipLaunchKernelGGL(vfn_mesh_total_kernel, dim3(1), dim3(64), 0, s, (const int*)offsets, (long long)(m - 1), (long long*)info, 0);
+    return vfn_check_launch("vfn_mesh_count");
+}
+
+extern "C" int vfn_mesh_emit(int32_t form, const void* comb, const void* udf, int32_t f64, const int64_t* cells, const uint8_t* sides,
+                             const float* norms, int64_t m, int32_t res, double size, double isovalue, const int32_t* counts,
+                             const int32_t* offsets, double* tri_verts, void* stream) {
+    MeshArgs a;
+    const int rc = make_args(a, form, comb, udf, f64, cells, sides, norms, m, res, size, isovalue, "vfn_mesh_emit");
+    if (rc != VFN_OK) return rc;
+    if (m == 0) return VFN_OK;
+    VFN_REQUIRE(counts && offsets && tri_verts, "vfn_mesh_emit: NULL argument");
+    hipLaunchKernelGGL(vfn_mesh_emit_kernel, dim3(blocks_for(m)), dim3(256), 0, (hipStream_t)stream, a, (const int*)counts, (const int*)offsets,
+                       tri_verts);
+    return vfn_check_launch("vfn_mesh_emit");
+}
+
+extern "C" int vfn_mesh_dedup(const double* tri_verts, int64_t n_slots, int32_t* table, int32_t* owner, int64_t table_size, int32_t* bucket,
+                              int32_t* flags, int32_t* vid, int64_t* info, void* scan_ws, int64_t scan_ws_bytes, void* stream) {
+    VFN_REQUIRE(info && n_slots >= 0 && n_slots < (1ll << 31), "vfn_mesh_dedup: bad argument (n_slots %lld)", (long long)n_slots);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_slots > 0) {
+        VFN_REQUIRE(tri_verts && table && owner && bucket && flags && vid, "vfn_mesh_dedup: NULL argument");
+        VFN_REQUIRE(table_size >= 2 * n_slots && (table_size & (table_size - 1)) == 0, "vfn_mesh_dedup: table size %lld is not a power of two "
+                    ">= 2 x %lld slots", (long long)table_size, (long long)n_slots);
+        hipLaunchKernelGGL(vfn_mesh_table_init_kernel, dim3(blocks_for(table_size)), dim3(256), 0, s, (int*)table, (int*)owner, (long long)table_size);
+        hipLaunchKernelGGL(vfn_mesh_dedup_kernel, dim3(blocks_for(n_slots)), dim3(256), 0, s, tri_verts, (long long)n_slots, (int*)table,
+                           (int*)owner, (long long)(table_size - 1), (int*)bucket);
+        hipLaunchKernelGGL(vfn_mesh_flag_kernel, dim3(blocks_for(n_slots)), dim3(256), 0, s, (const int*)owner, (const int*)bucket,
+                           (long long)n_slots, (int*)flags);
+        const int rc = inclusive_scan(flags, vid, n_slots, scan_ws, scan_ws_bytes, s, "vfn_mesh_dedup");
+        if (rc != VFN_OK) return rc;
+    }
+    hipLaunchKernelGGL(vfn_mesh_total_kernel, dim3(1), dim3(64), 0, s, (const int*)vid, (long long)(n_slots - 1), (long long*)info, 2);
+    return vfn_check_launch("vfn_mesh_dedup");
+}
+
+extern "C" int vfn_mesh_number(const double* tri_verts, int64_t n_slots, const int32_t* owner, const int32_t* bucket, const int32_t* vid,
+                               double* vertices, int64_t* faces, void* stream) {
+    if (n_slots <= 0) return VFN_OK;
+    VFN_REQUIRE(tri_verts && owner && bucket && vid && vertices && faces && n_slots < (1ll << 31), "vfn_mesh_number: bad argument");
+    hipLaunchKernelGGL(vfn_mesh_number_kernel, dim3(blocks_for(n_slots)), dim3(256), 0, (hipStream_t)stream, tri_verts, (long long)n_slots,
+                       (const int*)owner, (const int*)bucket, (const int*)vid, vertices, (long long*)faces);
+    return vfn_check_launch("vfn_mesh_number");
+}
+
+extern "C" int vfn_mesh_field_norms(const float* field, int64_t n, float* norms, float* unit, void* stream) {
+    if (n <= 0) return VFN_OK;
+    VFN_REQUIRE(field && norms, "vfn_mesh_field_norms: NULL argument");
+    hipLaunchKernelGGL(vfn_mesh_field_norms_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, field, (long long)n, norms, unit);
+    return vfn_check_launch("vfn_mesh_field_norms");
+}

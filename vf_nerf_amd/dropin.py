@@ -13,7 +13,7 @@ import importlib
 import sys
 import types
 
-from . import density, evaluator, grid, loss, nerf, networks, render_output, samplers, supervision
+from . import density, evaluator, grid, loss, mesh, nerf, networks, render_output, samplers, supervision
 
 _ALIASES = {
     "models.nerf.vector_field_nerf": nerf,
@@ -36,7 +36,7 @@ def _ensure_package(name: str) -> None:
         sys.modules[name] = pkg
 
 
-def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scalars=None) -> None:
+def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scalars=None, patch_mesh: bool = True) -> None:
     """``patch_clip=False`` leaves ``torch.nn.utils.clip_grad_norm_`` PyTorch's own function (no process-wide replacement): a step session then
     parks its gradient in the optimizer's flat buffer with every ``param.grad`` None, the trainer's clip call finds nothing to scale, and
     ``optimizer.step()`` all-reduces (more than one rank), clips with the model's ``scheduler_config.clip_norm`` — the value the trainer
@@ -46,7 +46,9 @@ def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scal
     ``vf_nerf_amd.deferred.resolve(payload)`` converts at the logger instead.
     ``patch_evaluator=False`` leaves ``evaluation.methods.render_images`` the reference's own loop (one upload, one ``model.render`` and
     six ``.cpu()`` read-backs per 512-ray chunk): every call of it still lands on the HIP ``render()``; what it gives up is the grouping
-    into chip-filling chunks and the single download per image (profiles/r05/bench_view_as_evaluator.json: both loops timed)."""
+    into chip-filling chunks and the single download per image (profiles/r05/bench_view_as_evaluator.json: both loops timed).
+    ``patch_mesh`` replaces ``evaluation.utils.marching_cubes_vt.contrastive_marching_cubes`` with ``mesh.contrastive_marching_cubes``
+    (the device triangulation, same (vs, fs)); ``patch_mesh=False`` restores the reference's function."""
     for dotted, module in _ALIASES.items():
         parts = dotted.split(".")
         for i in range(1, len(parts)):
@@ -75,6 +77,18 @@ def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scal
             methods.render_images = evaluator.render_images
         elif hasattr(methods, "_reference_render_images"):
             methods.render_images = methods._reference_render_images
+    except Exception:
+        pass
+    # evaluation/utils/marching_cubes_vt.contrastive_marching_cubes (a Python loop over every surface cell) -> the device triangulation;
+    # same arguments and (vs, fs).  patch_mesh=False puts the reference's function back.
+    try:
+        mcv = importlib.import_module("evaluation.utils.marching_cubes_vt")
+        if patch_mesh:
+            if not hasattr(mcv, "_reference_contrastive_marching_cubes"):
+                mcv._reference_contrastive_marching_cubes = mcv.contrastive_marching_cubes
+            mcv.contrastive_marching_cubes = mesh.contrastive_marching_cubes
+        elif hasattr(mcv, "_reference_contrastive_marching_cubes"):
+            mcv.contrastive_marching_cubes = mcv._reference_contrastive_marching_cubes
     except Exception:
         pass
     # models.helpers.functions stays the reference's module (the trainer uses more of it); only the two host-side numpy

@@ -38,6 +38,8 @@ EXPORTS = (
     "vfn_train_step_workspace_layout", "vfn_train_step_supervision_points", "vfn_train_step_supervision_forward", "vfn_train_step_supervision_backward",
     "vfn_linear_rows_dx_sums", "vfn_weight_grad_partials_bf16_ld", "vfn_linear_rows_ws", "vfn_linear_rows_wplanes_bytes",
     "vfn_select_samples", "vfn_grid_lattice_points", "vfn_linear_rows_fold", "vfn_weight_grad_partials_bf16_fold",
+    "vfn_mesh_tables", "vfn_mesh_scan_workspace_bytes", "vfn_mesh_count", "vfn_mesh_emit", "vfn_mesh_dedup", "vfn_mesh_number",
+    "vfn_mesh_field_norms",
 )
 
 
@@ -1227,6 +1229,87 @@ def grid_comb_format(choice: torch.Tensor, norms: torch.Tensor, n: int):
                                        _ptr(different, "different_side"), _ptr(pair_norms, "pair_norms"), _stream()),
            "vfn_grid_comb_format")
     return different, pair_norms
+
+
+# ------------------------------------------------------------------------------------------------
+# mesh triangulation (csrc/vfn_mesh.hip; vf_nerf_amd/mesh.py is the public surface)
+# ------------------------------------------------------------------------------------------------
+MESH_GENERAL, MESH_FUSED = 0, 1
+MESH_STATUS_NONFINITE, MESH_STATUS_INDEX = 1, 2
+
+
+def mesh_tables():
+    """-> (edge_table[256] int32, edge_vertex[12,2] int32, tri_table[256,16] int8): host copies of the tables the kernels use."""
+    import numpy as np
+    et, ev, tt = (C.c_int32 * 256)(), (C.c_int32 * 24)(), (C.c_int8 * 4096)()
+    _check(load().vfn_mesh_tables(et, ev, tt), "vfn_mesh_tables")
+    return (np.frombuffer(et, dtype=np.int32).copy(), np.frombuffer(ev, dtype=np.int32).reshape(12, 2).copy(),
+            np.frombuffer(tt, dtype=np.int8).reshape(256, 16).copy())
+
+
+def mesh_field_norms(field: torch.Tensor, want_unit: bool = True):
+    """field[n,3] -> (norms[n], unit[n,3] | None): torch.norm(field, dim=1) as torch's CPU kernel rounds it, F.normalize(field, dim=1)."""
+    n = field.shape[0]
+    norms = torch.empty(n, device=field.device)
+    unit = torch.empty(n, 3, device=field.device) if want_unit else None
+    _check(load().vfn_mesh_field_norms(_ptr(field, "field"), C.c_int64(n), _ptr(norms, "norms"), _ptr(unit, "unit"), _stream()),
+           "vfn_mesh_field_norms")
+    return norms, unit
+
+
+def _scan_ws(n: int, dev) -> torch.Tensor:
+    b = int(load().vfn_mesh_scan_workspace_bytes(C.c_int64(max(n, 1))))
+    if b < 0:
+        raise VfnError(f"vfn_mesh_scan_workspace_bytes failed: {load().vfn_last_error().decode()}")
+    return torch.empty(max(b, 1), dtype=torch.uint8, device=dev)
+
+
+def mesh_triangulate(form: int, m: int, res: int, size: float, isovalue: float, comb: Optional[torch.Tensor] = None,
+                     udf: Optional[torch.Tensor] = None, cells: Optional[torch.Tensor] = None, sides: Optional[torch.Tensor] = None,
+                     norms: Optional[torch.Tensor] = None, device=None):
+    """count -> emit -> dedup -> number on the current stream -> (vertices[V,3] float64, faces[F,3] int64, 0-based).  Two values cross to
+    the host: the triangle count (with the input status) and the vertex count, each to size the next outputs."""
+    dev = torch.device(device) if device is not None else (norms.device if norms is not None else comb.device)
+    f64 = int(comb is not None and comb.dtype == torch.float64)
+    dt = torch.float64 if f64 else torch.float32
+    ptrs = (C.c_int32(form), _ptr(comb, "comb", dt), _ptr(udf, "udf", dt), C.c_int32(f64), _ptr(cells, "cells", torch.int64),
+            _ptr(sides, "sides", torch.uint8), _ptr(norms, "norms"), C.c_int64(m), C.c_int32(res), C.c_double(size), C.c_double(isovalue))
+    info = torch.zeros(4, dtype=torch.int64, device=dev)
+    counts = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+    offsets = torch.empty_like(counts)
+    ws = _scan_ws(m, dev)
+    _check(load().vfn_mesh_count(*ptrs, _ptr(counts, "counts", torch.int32), _ptr(offsets, "offsets", torch.int32), _ptr(info, "info", torch.int64),
+                                 _ptr(ws, "scan_ws", torch.uint8), C.c_int64(ws.numel()), _stream()), "vfn_mesh_count")
+    n_tri, status = (int(x) for x in info[:2].cpu())
+    if status & MESH_STATUS_INDEX:
+        raise VfnError(f"mesh triangulation: a cell index lies outside [0, {res})")
+    if status & MESH_STATUS_NONFINITE:
+        raise VfnError("mesh triangulation: a non-finite norm / udf value in a triangulated cell (NaN vertices cannot be deduplicated "
+                       "meaningfully; the reference's dict would keep every one of them)")
+    n_slots = 3 * n_tri
+    if n_tri < 0 or n_slots >= (1 << 31):
+        raise VfnError(f"mesh triangulation: {n_tri} triangles exceed the 2^31 / 3 limit")
+    tri_verts = torch.empty(max(n_slots, 1), 3, dtype=torch.float64, device=dev)
+    _check(load().vfn_mesh_emit(*ptrs, _ptr(counts, "counts", torch.int32), _ptr(offsets, "offsets", torch.int32),
+                                _ptr(tri_verts, "tri_verts", torch.float64), _stream()), "vfn_mesh_emit")
+    table_size = 1 << max(6, (2 * n_slots - 1).bit_length())
+    table = torch.empty(table_size, dtype=torch.int32, device=dev)
+    owner = torch.empty_like(table)
+    bucket = torch.empty(max(n_slots, 1), dtype=torch.int32, device=dev)
+    flags, vid = torch.empty_like(bucket), torch.empty_like(bucket)
+    ws = _scan_ws(n_slots, dev)
+    _check(load().vfn_mesh_dedup(_ptr(tri_verts, "tri_verts", torch.float64), C.c_int64(n_slots), _ptr(table, "table", torch.int32),
+                                 _ptr(owner, "owner", torch.int32), C.c_int64(table_size), _ptr(bucket, "bucket", torch.int32),
+                                 _ptr(flags, "flags", torch.int32), _ptr(vid, "vid", torch.int32), _ptr(info, "info", torch.int64),
+                                 _ptr(ws, "scan_ws", torch.uint8), C.c_int64(ws.numel()), _stream()), "vfn_mesh_dedup")
+    n_vert = int(info[2].cpu())
+    vertices = torch.empty(n_vert, 3, dtype=torch.float64, device=dev)
+    faces = torch.empty(n_tri, 3, dtype=torch.int64, device=dev)
+    _check(load().vfn_mesh_number(_ptr(tri_verts, "tri_verts", torch.float64), C.c_int64(n_slots), _ptr(owner, "owner", torch.int32),
+                                  _ptr(bucket, "bucket", torch.int32), _ptr(vid, "vid", torch.int32),
+                                  _ptr(vertices, "vertices", torch.float64) if n_vert else None,
+                                  _ptr(faces, "faces", torch.int64) if n_tri else None, _stream()), "vfn_mesh_number")
+    return vertices, faces
 
 
 # ------------------------------------------------------------------------------------------------
