@@ -206,3 +206,60 @@ def narrow_checkpoint_model(d, device="cpu"):
 
 
 REF_CHECKPOINT = os.path.join(GOLDEN_DIR, "ref_checkpoint_latest.pth")
+
+
+# ------------------------------------------------------------------------------------------------
+# dense-grid test fields (tests/test_hip_parity.py, tests/test_grid_margins_host.py, tests/test_hip_grid_margins.py)
+# ------------------------------------------------------------------------------------------------
+def surface_field(n: int, seed=None, device="cpu") -> torch.Tensor:
+    """[n^3,3] fp32: points towards the nearest of two spheres' shells with a random magnitude in [0.2, 1.2), plus noise; every 997th
+    vector exactly zero.  Seeded with ``n`` unless ``seed`` is given.  On another device the same construction with that device's
+    generator (other numbers, the same kind of field)."""
+    dev = torch.device(device)
+    gen = torch.Generator(device=dev).manual_seed(n if seed is None else seed)
+    ax = torch.linspace(-1, 1, n, device=dev)
+    p = torch.stack(torch.meshgrid(ax, ax, ax, indexing="ij"), dim=-1).reshape(-1, 3)
+    d1, d2 = p - torch.tensor([0.3, 0.0, 0.0], device=dev), p + torch.tensor([0.4, 0.2, 0.1], device=dev)
+    r1, r2 = d1.norm(dim=1, keepdim=True), d2.norm(dim=1, keepdim=True)
+    f1, f2 = -d1 / r1.clamp_min(1e-6) * torch.sign(r1 - 0.45), -d2 / r2.clamp_min(1e-6) * torch.sign(r2 - 0.3)
+    pred = torch.where((r1 - 0.45).abs() < (r2 - 0.3).abs(), f1, f2) * (0.2 + torch.rand(n ** 3, 1, generator=gen, device=dev)) + \
+        0.05 * torch.randn(n ** 3, 3, generator=gen, device=dev)
+    pred[::997] = 0.0
+    return pred.contiguous()
+
+
+def per_point_scale(m: int, seed: int, lo: float = -6.0, hi: float = 3.0) -> torch.Tensor:
+    """[m,1] fp32 factors 10^U(lo, hi): a field scaled by them keeps every direction and spans nine decades of magnitude."""
+    gen = torch.Generator().manual_seed(seed)
+    return (10.0 ** (lo + (hi - lo) * torch.rand(m, 1, generator=gen, dtype=torch.float64))).float()
+
+
+def synthetic_field(res, seed):
+    """Several converging shells and planes, noise, and exact zero vectors: surfaces in many cell configurations."""
+    g = torch.Generator().manual_seed(seed)
+    ax = torch.linspace(-1, 1, res)
+    p = torch.stack(torch.meshgrid(ax, ax, ax, indexing="ij"), dim=-1).reshape(-1, 3)
+    d = p - torch.tensor([0.05, -0.1, 0.02])
+    r = d.norm(dim=1, keepdim=True).clamp_min(1e-6)
+    v = -torch.sign(r - 0.5) * d / r * (0.2 + (r - 0.5).abs())
+    v = v + 0.6 * torch.sign(torch.sin(6.0 * p[:, :1])) * torch.tensor([[1.0, 0.0, 0.0]]) * (p[:, 1:2] > 0.3)
+    v = v + 0.08 * torch.randn(res ** 3, 3, generator=g)
+    v[torch.randperm(res ** 3, generator=g)[: res ** 3 // 200]] = 0
+    return v.float()
+
+
+def divergence_seg_len(n: int) -> int:
+    """Planes per workgroup of vfn_grid_divergence (csrc/vfn_grid.hip): segment s covers planes [s seg_len, (s + 1) seg_len)."""
+    blocks = ((n + 63) // 64) * ((n + 7) // 8)
+    segs = max(1, min((8192 + blocks - 1) // blocks, (n + 15) // 16))
+    return (n + segs - 1) // segs
+
+
+def smooth_seg_len(n: int, k: int, axis: int) -> int:
+    """Positions per march segment of vfn_grid_smooth_axis for axes 0 / 1 with k in (3, 9) (launch_smooth in csrc/vfn_grid.hip)."""
+    inner = 3 * n * n if axis == 0 else 3 * n
+    lanes = inner // (4 if inner % 4 == 0 else 1) * (1 if axis == 0 else n)
+    cap = (n + 4 * k - 1) // (4 * k)
+    segs = max(1, min((2048 * 64 + lanes - 1) // lanes, cap))
+    seg = (n + segs - 1) // segs
+    return (seg + k - 1) // k * k

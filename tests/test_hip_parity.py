@@ -10,7 +10,8 @@ import os
 import pytest
 import torch
 
-from helpers import FIXTURE_NAMES, build_model, load_fixture, oracle_settings, rel_err
+from helpers import FIXTURE_NAMES, build_model, load_fixture, oracle_settings, rel_err, surface_field
+import grid_margins as GM
 from oracle import vfnerf_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -521,6 +522,8 @@ def test_grid_stages_on_hip():
         assert choice.dtype == torch.int64 and choice.shape == (n ** 3, 8)
         mism = (choice.cpu() != g[f"n{n}.choice"]).sum()
         assert int(mism) == 0, int(mism)
+        for rep in (GM.explain_divergence(div.cpu(), g[f"n{n}.pred"], n), GM.explain_sides(choice.cpu(), div.cpu(), vt.reshape(-1, 3).cpu(), n)):
+            assert rep.ok, str(rep)                          # equal to the reference's AND explained by float64
         norms = torch.norm(g[f"n{n}.pred"], dim=1).to(dev())          # as the reference computes them (CPU), then a pure gather
         comb, pair_norms = grid.make_comb_format(choice, norms, n)
         assert torch.equal(comb.cpu(), g[f"n{n}.comb"]) and torch.equal(pair_norms.cpu(), g[f"n{n}.pair_norms"])
@@ -531,6 +534,9 @@ def test_grid_stages_on_hip():
     div = grid.extract_divergence(pred.to(dev()), n).cpu()
     want = O.grid_divergence(pred, n)
     assert float((div != want).float().mean()) < 1e-3
+    rep = GM.explain_divergence(div, pred, n)                # ... and every differing cell sits within fp32 rounding of the threshold
+    print(rep)
+    assert rep.ok, str(rep)
     with pytest.raises(Exception):
         grid.extract_divergence(pred, n)      # host tensors are refused: no CPU fallback
 
@@ -544,23 +550,16 @@ def test_grid_stages_tiled_kernels_at_larger_sizes(n):
     order): bounded as a fraction; everything that is a pure gather or comparison of integers is exact."""
     from oracle import vfnerf_oracle as O
     from vf_nerf_amd import grid, lib
-    gen = torch.Generator().manual_seed(n)
-    ax = torch.linspace(-1, 1, n)
-    p = torch.stack(torch.meshgrid(ax, ax, ax, indexing="ij"), dim=-1).reshape(-1, 3)
-    # a field with surfaces: points towards the nearest of two spheres' shells, plus noise; a few exactly-zero vectors
-    d1, d2 = p - torch.tensor([0.3, 0.0, 0.0]), p + torch.tensor([0.4, 0.2, 0.1])
-    r1, r2 = d1.norm(dim=1, keepdim=True), d2.norm(dim=1, keepdim=True)
-    f1, f2 = -d1 / r1.clamp_min(1e-6) * torch.sign(r1 - 0.45), -d2 / r2.clamp_min(1e-6) * torch.sign(r2 - 0.3)
-    pred = torch.where((r1 - 0.45).abs() < (r2 - 0.3).abs(), f1, f2) * (0.2 + torch.rand(n ** 3, 1, generator=gen)) + \
-        0.05 * torch.randn(n ** 3, 3, generator=gen)
-    pred[::997] = 0.0
-    pred = pred.contiguous()
+    pred = surface_field(n)      # surfaces of two spheres' shells, noise, a few exactly-zero vectors (tests/helpers.py)
     dp = pred.to(dev())
     div = grid.extract_divergence(dp, n)
     want_div = O.grid_divergence(pred, n)
     frac = float((div.cpu() != want_div).float().mean())
     print(f"n={n}: surface cells {float(want_div.mean()):.4f}, divergence mask mismatches {frac:.2e}")
     assert float(want_div.mean()) > 0.005 and frac < 2e-4
+    rep = GM.explain_divergence(div.cpu(), pred, n)          # the fraction is a fence; the reason is the float64 margin of every differing cell
+    print(rep)
+    assert rep.ok and rep.band_share <= GM.CAP_DIV_BAND, str(rep)
     assert float(div[-1].abs().max()) == 0 and float(div[:, -1].abs().max()) == 0 and float(div[:, :, -1].abs().max()) == 0
     for k, sigma in ((3, 1.0), (9, 2.0), (5, 1.5)):                      # 5: the generic per-voxel kernel
         sm = grid.smooth_vf(dp.reshape(n, n, n, 3), k=k, sigma=sigma)
@@ -574,6 +573,9 @@ def test_grid_stages_tiled_kernels_at_larger_sizes(n):
     cell_diff = float((choice.cpu() != want_choice).any(dim=1).float().sum() / max(1.0, float(div.sum())))
     print(f"n={n}: surface cells whose corner sides differ from the oracle's: {cell_diff:.2e}")
     assert choice.shape == (n ** 3, 8) and choice.dtype == torch.int64 and cell_diff < 2e-3
+    rep = GM.explain_sides(choice.cpu(), div.cpu(), vt, n)
+    print(rep)
+    assert rep.ok and rep.band_share <= GM.CAP_SIDES_AMBIGUOUS, str(rep)
     assert int(choice.min()) == 0 and int(choice.max()) == 1 and int(choice[div.reshape(-1) != 1].abs().sum()) == 0
     sides, table = lib.grid_unify_direction_sides(div.reshape(-1).contiguous(), dvt.reshape(-1, 3).contiguous(), n)
     assert torch.equal(table, choice)

@@ -1292,6 +1292,22 @@ def mesh_triangulate(form: int, m: int, res: int, size: float, isovalue: float, 
     tri_verts = torch.empty(max(n_slots, 1), 3, dtype=torch.float64, device=dev)
     _check(load().vfn_mesh_emit(*ptrs, _ptr(counts, "counts", torch.int32), _ptr(offsets, "offsets", torch.int32),
                                 _ptr(tri_verts, "tri_verts", torch.float64), _stream()), "vfn_mesh_emit")
+    vertices, ids = mesh_dedup(tri_verts[:n_slots], info=info)
+    return vertices, ids.view(n_tri, 3)
+
+
+def mesh_dedup(tri_verts: torch.Tensor, info: Optional[torch.Tensor] = None):
+    """tri_verts[S,3] float64 (finite) -> (vertices[V,3] float64, ids[S] int64): the distinct positions in order of first appearance (float
+    equality: -0.0 and +0.0 are one key, the first occurrence's bits are kept) and every slot's vertex id; three consecutive slots are
+    one face.  Table sizing, vfn_mesh_dedup and vfn_mesh_number on the current stream; the vertex count crosses to the host."""
+    dev = tri_verts.device
+    n_slots = tri_verts.shape[0]
+    if n_slots >= (1 << 31):
+        raise VfnError(f"mesh deduplication: {n_slots} slots exceed the 2^31 limit")
+    if info is None:
+        info = torch.zeros(4, dtype=torch.int64, device=dev)
+    if n_slots == 0:
+        tri_verts = torch.empty(1, 3, dtype=torch.float64, device=dev)
     table_size = 1 << max(6, (2 * n_slots - 1).bit_length())
     table = torch.empty(table_size, dtype=torch.int32, device=dev)
     owner = torch.empty_like(table)
@@ -1304,12 +1320,12 @@ def mesh_triangulate(form: int, m: int, res: int, size: float, isovalue: float, 
                                  _ptr(ws, "scan_ws", torch.uint8), C.c_int64(ws.numel()), _stream()), "vfn_mesh_dedup")
     n_vert = int(info[2].cpu())
     vertices = torch.empty(n_vert, 3, dtype=torch.float64, device=dev)
-    faces = torch.empty(n_tri, 3, dtype=torch.int64, device=dev)
+    ids = torch.empty(n_slots, dtype=torch.int64, device=dev)
     _check(load().vfn_mesh_number(_ptr(tri_verts, "tri_verts", torch.float64), C.c_int64(n_slots), _ptr(owner, "owner", torch.int32),
                                   _ptr(bucket, "bucket", torch.int32), _ptr(vid, "vid", torch.int32),
                                   _ptr(vertices, "vertices", torch.float64) if n_vert else None,
-                                  _ptr(faces, "faces", torch.int64) if n_tri else None, _stream()), "vfn_mesh_number")
-    return vertices, faces
+                                  _ptr(ids, "faces", torch.int64) if n_slots else None, _stream()), "vfn_mesh_number")
+    return vertices, ids
 
 
 # ------------------------------------------------------------------------------------------------
