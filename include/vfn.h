@@ -717,6 +717,51 @@ int vfn_mesh_number(const double* tri_verts, int64_t n_slots, const int32_t* own
 int vfn_mesh_field_norms(const float* field, int64_t n, float* norms, float* unit, void* stream);
 
 /* =============================================================================================
+ * Scoring a mesh against a mesh (csrc/vfn_metrics.hip): the geometry of evaluation/methods.py:747-801 (metrics_3d_no_vf) with
+ * utils/utils.py:327-367 (get_chamfer_distance) — area-weighted surface samples, every sample's nearest neighbour in the other set,
+ * statistics of the distances.  Everything is float64, evaluated without contraction in the association written here, and no result
+ * depends on the order in which workgroups or atomics arrive.  `info` words are zero-filled by the caller and only ever OR-ed into:
+ * bit 1 = a non-finite value, bit 2 = a face index outside [0, V).  Limits: every count < 2^31.
+ *   vfn_nn_sqdist     reads queries[n, 3], targets[m, 3] (row-major); writes best[n] = min over j of ((dx dx + dy dy) + dz dz) with
+ *                     dx = q.x - t_j.x, dy = q.y - t_j.y, dz = q.z - t_j.z — the SQUARED distance to the nearest target; the caller
+ *                     takes sqrt (monotone and correctly rounded: sqrt of the minimum is the minimum of the sqrts).  All n x m pairs
+ *                     are evaluated (no spatial structure, no index output).  best is filled with +inf by the same call; the target
+ *                     slices of one query merge with an integer atomicMin on the bits of the non-negative double.  info[0] |= 1 when
+ *                     a coordinate of either set is not finite (best is then meaningless).  1 <= n, m < 2^31.
+ *   vfn_tri_areas     reads vertices[V, 3], faces[F, 3] (int64); writes areas[F] = 0.5 sqrt((c.x c.x + c.y c.y) + c.z c.z) with
+ *                     e1 = v1 - v0, e2 = v2 - v0, c = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z, e1.x e2.y - e1.y e2.x), both
+ *                     products of a component rounded.  A face with an index outside [0, V): info[0] |= 2, area 0.  A non-finite
+ *                     area: info[0] |= 1.
+ *   vfn_cumsum_f64    out[i] = x[0] + ... + x[i] as a FIXED tree: blocks of 1024 values (a lane adds 4 values serially, a
+ *                     Kogge-Stone scan over the 256 lane totals, one addition of the lane's own prefix), the block totals scanned
+ *                     the same way, one addition per level on the way down — a prefix is at most 12 x levels additions deep,
+ *                     levels = 1 for n <= 1024, 2 for n <= 1024^2, 3 for n <= 1024^3, 4 above.  The bits are a function of n and the data alone (a
+ *                     look-back scan's are not), so equal uniforms always select equal faces.  Neighbouring prefixes are rounded
+ *                     along different paths: the output may step down by an ulp (the caller that needs a monotone table takes a
+ *                     running maximum, which is exact).  x and out may be the same array.
+ *                     workspace: vfn_cumsum_workspace_bytes(n) bytes of device memory (0 for n <= 1024); -1 on error.
+ *   vfn_sample_surface  reads vertices, faces, cum[F] (the inclusive cumulative areas, non-decreasing) and uniforms[count, 3] in [0, 1);
+ *                     point i: t = u[i,0] cum[F-1]; face = the smallest index with cum[face] > t (binary search), clamped to F - 1 — a
+ *                     zero-area face is never chosen; a = u[i,1], b = u[i,2], and if a + b > 1 then a = 1 - a, b = 1 - b;
+ *                     points[i, c] = (v0[c] + a e1[c]) + b e2[c] with e1 = v1 - v0, e2 = v2 - v0.  Writes points[count, 3] and
+ *                     face_index[count] (int64).  A chosen face with an index outside [0, V): info[0] |= 2, point 0.
+ *   vfn_reduce_stats  reads x[n]; writes stats[4] = sum, min, max, number of x[i] < threshold (as a double: exact).  A fixed two-level
+ *                     tree without floating-point atomics: block b joins x[4096 b, 4096 (b + 1)) — 16 values per lane as a balanced
+ *                     tree (4 levels), 256 lanes as a balanced tree (8 levels) — into one partial; one block of 1024 lanes joins the
+ *                     P = ceil(n / 4096) partials, a lane its partials l, l + 1024, ... serially, then a balanced tree (10 levels).
+ *                     workspace: vfn_reduce_stats_workspace_bytes(n) bytes (the partials); -1 on error.
+ * ============================================================================================= */
+int vfn_nn_sqdist(const double* queries, int64_t n, const double* targets, int64_t m, double* best, int64_t* info, void* stream);
+int vfn_tri_areas(const double* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces, double* areas, int64_t* info,
+                  void* stream);
+int64_t vfn_cumsum_workspace_bytes(int64_t n);
+int vfn_cumsum_f64(const double* x, int64_t n, double* out, void* workspace, int64_t workspace_bytes, void* stream);
+int vfn_sample_surface(const double* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces, const double* cum,
+                       const double* uniforms, int64_t count, double* points, int64_t* face_index, int64_t* info, void* stream);
+int64_t vfn_reduce_stats_workspace_bytes(int64_t n);
+int vfn_reduce_stats(const double* x, int64_t n, double threshold, double* stats, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* =============================================================================================
  * Optimizer side of a training step over ONE flat fp32 buffer (train/vector_field_nerf_train.py:254-260:
  * torch.nn.utils.clip_grad_norm_(model.parameters(), clip); optimizer.step()).  The unique parameters — and their gradients
  * and Adam moments — are laid out contiguously, sorted into up to four REGIONS [start, end) of equal multiplicity `mult` =

@@ -40,6 +40,8 @@ EXPORTS = (
     "vfn_select_samples", "vfn_grid_lattice_points", "vfn_linear_rows_fold", "vfn_weight_grad_partials_bf16_fold",
     "vfn_mesh_tables", "vfn_mesh_scan_workspace_bytes", "vfn_mesh_count", "vfn_mesh_emit", "vfn_mesh_dedup", "vfn_mesh_number",
     "vfn_mesh_field_norms",
+    "vfn_nn_sqdist", "vfn_tri_areas", "vfn_cumsum_workspace_bytes", "vfn_cumsum_f64", "vfn_sample_surface",
+    "vfn_reduce_stats_workspace_bytes", "vfn_reduce_stats",
 )
 
 
@@ -1326,6 +1328,105 @@ def mesh_dedup(tri_verts: torch.Tensor, info: Optional[torch.Tensor] = None):
                                   _ptr(vertices, "vertices", torch.float64) if n_vert else None,
                                   _ptr(ids, "faces", torch.int64) if n_slots else None, _stream()), "vfn_mesh_number")
     return vertices, ids
+
+
+# ------------------------------------------------------------------------------------------------
+# mesh scoring (csrc/vfn_metrics.hip; vf_nerf_amd/metrics3d.py is the public surface).  Everything float64, contiguous, on one device.
+# ------------------------------------------------------------------------------------------------
+METRICS_STATUS_NONFINITE, METRICS_STATUS_INDEX = 1, 2
+CUMSUM_TILE, REDUCE_TILE, REDUCE_TOP = 1024, 4096, 1024      # csrc/vfn_metrics.hip: SCAN_TILE, RED_TILE, RED_TOP
+
+
+def _bytes_ws(fn_name: str, n: int, dev) -> torch.Tensor:
+    b = int(getattr(load(), fn_name)(C.c_int64(n)))
+    if b < 0:
+        raise VfnError(f"{fn_name} failed: {load().vfn_last_error().decode()}")
+    return torch.empty(max(b, 1), dtype=torch.uint8, device=dev)
+
+
+def nn_sqdist(queries: torch.Tensor, targets: torch.Tensor, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """queries[n,3], targets[m,3] -> best[n]: the squared distance of every query to its nearest target, all pairs in float64.  A
+    non-finite coordinate in either set raises (one status word crosses to the host) — or, with the caller's zero-filled ``info``
+    (int64 [1]), sets its bit METRICS_STATUS_NONFINITE for the caller to read with its results (``nn_check``)."""
+    n, m = queries.shape[0], targets.shape[0]
+    best = torch.empty(n, dtype=torch.float64, device=queries.device)
+    own = info is None
+    if own:
+        info = torch.zeros(1, dtype=torch.int64, device=queries.device)
+    _check(load().vfn_nn_sqdist(_ptr(queries, "queries", torch.float64), C.c_int64(n), _ptr(targets, "targets", torch.float64), C.c_int64(m),
+                                _ptr(best, "best", torch.float64), _ptr(info, "info", torch.int64), _stream()), "vfn_nn_sqdist")
+    if own:
+        nn_check(int(info.cpu()))
+    return best
+
+
+def nn_check(status: int) -> None:
+    if status & METRICS_STATUS_NONFINITE:
+        raise VfnError("nearest-neighbour search: a non-finite coordinate in the queries or the targets")
+
+
+def tri_areas(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """vertices[V,3] float64, faces[F,3] int64 -> areas[F].  A face index outside [0, V) or a non-finite area raises."""
+    nv, nf = vertices.shape[0], faces.shape[0]
+    areas = torch.empty(nf, dtype=torch.float64, device=faces.device)
+    info = torch.zeros(1, dtype=torch.int64, device=faces.device)
+    _check(load().vfn_tri_areas(_ptr(vertices, "vertices", torch.float64) if nv else None, C.c_int64(nv), _ptr(faces, "faces", torch.int64),
+                                C.c_int64(nf), _ptr(areas, "areas", torch.float64), _ptr(info, "info", torch.int64), _stream()), "vfn_tri_areas")
+    status = int(info.cpu())
+    if status & METRICS_STATUS_INDEX:
+        raise VfnError(f"triangle areas: a face index lies outside [0, {nv})")
+    if status & METRICS_STATUS_NONFINITE:
+        raise VfnError("triangle areas: a non-finite area (non-finite or overflowing vertex coordinates)")
+    return areas
+
+
+def cumsum_levels(n: int) -> int:
+    """Scan levels of vfn_cumsum_f64 over n values (a prefix is at most 12 additions deep per level)."""
+    levels = 1
+    while n > CUMSUM_TILE:
+        n, levels = (n + CUMSUM_TILE - 1) // CUMSUM_TILE, levels + 1
+    return levels
+
+
+def cumsum_f64(x: torch.Tensor) -> torch.Tensor:
+    """x[n] float64 -> the inclusive prefix sums as a fixed tree (the bits depend on n and the data alone)."""
+    n = x.shape[0]
+    out = torch.empty_like(x)
+    ws = _bytes_ws("vfn_cumsum_workspace_bytes", n, x.device)
+    _check(load().vfn_cumsum_f64(_ptr(x, "x", torch.float64), C.c_int64(n), _ptr(out, "out", torch.float64), _ptr(ws, "workspace", torch.uint8),
+                                 C.c_int64(ws.numel()), _stream()), "vfn_cumsum_f64")
+    return out
+
+
+def sample_surface(vertices: torch.Tensor, faces: torch.Tensor, cum: torch.Tensor, uniforms: torch.Tensor):
+    """-> (points[count,3] float64, face_index[count] int64) for uniforms[count,3]; see include/vfn.h for the expressions."""
+    count = uniforms.shape[0]
+    dev = uniforms.device
+    points = torch.empty(count, 3, dtype=torch.float64, device=dev)
+    face_index = torch.empty(count, dtype=torch.int64, device=dev)
+    info = torch.zeros(1, dtype=torch.int64, device=dev)
+    _check(load().vfn_sample_surface(_ptr(vertices, "vertices", torch.float64), C.c_int64(vertices.shape[0]), _ptr(faces, "faces", torch.int64),
+                                     C.c_int64(faces.shape[0]), _ptr(cum, "cum", torch.float64), _ptr(uniforms, "uniforms", torch.float64),
+                                     C.c_int64(count), _ptr(points, "points", torch.float64), _ptr(face_index, "face_index", torch.int64),
+                                     _ptr(info, "info", torch.int64), _stream()), "vfn_sample_surface")
+    return points, face_index, info
+
+
+def reduce_stats(x: torch.Tensor, threshold: float) -> torch.Tensor:
+    """x[n] float64 -> stats[4] on the device: sum, min, max, number of x[i] < threshold (as a double).  Nothing crosses to the host."""
+    n = x.shape[0]
+    stats = torch.empty(4, dtype=torch.float64, device=x.device)
+    ws = _bytes_ws("vfn_reduce_stats_workspace_bytes", n, x.device)
+    _check(load().vfn_reduce_stats(_ptr(x, "x", torch.float64), C.c_int64(n), C.c_double(threshold), _ptr(stats, "stats", torch.float64),
+                                   _ptr(ws, "workspace", torch.uint8), C.c_int64(ws.numel()), _stream()), "vfn_reduce_stats")
+    return stats
+
+
+def reduce_sum_levels(n: int) -> int:
+    """Addition levels of vfn_reduce_stats's sum over n values: 4 (a lane's 16 values) + 8 (256 lanes) + the serial run of the second
+    level (ceil(P / 1024) - 1, P = ceil(n / 4096) partials) + 10 (1024 lanes)."""
+    p = (n + REDUCE_TILE - 1) // REDUCE_TILE
+    return 4 + 8 + ((p + REDUCE_TOP - 1) // REDUCE_TOP - 1) + 10
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,0 +1,253 @@
+"""Scoring a mesh against a mesh on the device (csrc/vfn_metrics.hip): the geometry of evaluation/methods.py:747-801
+(``metrics_3d_no_vf``) — ``utils.get_chamfer_distance`` (utils/utils.py:327-367) and precision / recall / F-score at a distance
+threshold — without copying either mesh to the host.
+
+* ``nearest_distances`` — every query's distance to its nearest target: all pairs in float64, bit-equal to
+  ``scipy.spatial.cKDTree(targets).query(queries)[0]`` (tests/test_metrics3d_host.py, tests/test_hip_metrics3d.py).  No index.
+* ``sample_surface`` — area-weighted surface samples (face by cumulative area, folded-square barycentric coordinates).
+* ``chamfer_from_points`` / ``chamfer_distance`` — the reference's four numbers with the reference's combination.
+* ``precision_recall_fscore`` — shares of points within a threshold of the other set.
+* ``score_mesh`` — both from one sampling and one search per direction, shaped like an entry of the reference's ``3d-metrics.json``.
+
+Inputs are numpy arrays or torch tensors on any device; a mesh is a ``mesh.Mesh`` (its ``vertices_scaled`` are used) or a
+``(vertices, faces)`` pair.  No CPU fallback: ``lib.VfnError`` when no device is visible.
+
+Out of scope: ``refuse()`` (Open3D TSDF fusion behind an OpenGL renderer), ``tsdf_mesh``, ICP alignment, the voxel down-sampling of
+the ``evaluate_3d_reconstruction`` package, trimesh's vertex merging, and PLY reading / writing.  The random numbers are torch's, not
+numpy's: a sampled point set is distributed as trimesh's, it is not the same set.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import lib
+from .mesh import Mesh
+
+LIMIT = 1 << 31
+
+
+def _device(device=None) -> torch.device:
+    if device is not None:
+        return torch.device(device)
+    if not torch.cuda.is_available():
+        raise lib.VfnError("mesh scoring runs on the device (no CPU fallback) and no GPU is visible")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _as_tensor(x, name: str) -> torch.Tensor:
+    if isinstance(x, torch.Tensor):
+        return x.detach()
+    if isinstance(x, np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(x))
+    raise TypeError(f"{name}: expected a numpy array or a torch tensor, got {type(x).__name__}")
+
+
+def _check_points(x, name: str) -> torch.Tensor:
+    """Shape / dtype / size checks on the host tensor, before any device call."""
+    t = _as_tensor(x, name)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} must be [n,3], got {tuple(t.shape)}")
+    if not (t.dtype.is_floating_point or t.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)):
+        raise ValueError(f"{name} must be real numbers, got {t.dtype}")
+    if t.shape[0] < 1:
+        raise ValueError(f"{name} is empty")
+    if t.shape[0] >= LIMIT:
+        raise ValueError(f"{name}: {t.shape[0]} rows exceed the 2^31 limit of one call")
+    return t
+
+
+def _check_mesh(m, name: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    if isinstance(m, Mesh):
+        vertices, faces = m.vertices_scaled, m.faces
+    elif isinstance(m, (tuple, list)) and len(m) == 2:
+        vertices, faces = m
+    else:
+        raise TypeError(f"{name}: expected a mesh.Mesh or a (vertices, faces) pair, got {type(m).__name__}")
+    v = _as_tensor(vertices, f"{name} vertices")
+    f = _as_tensor(faces, f"{name} faces")
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"{name} vertices must be [V,3], got {tuple(v.shape)}")
+    if not v.dtype.is_floating_point:
+        raise ValueError(f"{name} vertices must be floating point, got {v.dtype}")
+    if f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError(f"{name} faces must be [F,3], got {tuple(f.shape)}")
+    if f.dtype.is_floating_point or f.dtype in (torch.bool, torch.complex64, torch.complex128):
+        raise ValueError(f"{name} faces must be integers, got {f.dtype}")
+    if f.shape[0] < 1:
+        raise ValueError(f"{name} has no faces")
+    if v.shape[0] < 1:
+        raise ValueError(f"{name} has no vertices")
+    if v.shape[0] >= LIMIT or f.shape[0] >= LIMIT:
+        raise ValueError(f"{name}: {v.shape[0]} vertices / {f.shape[0]} faces exceed the 2^31 limit")
+    return v, f
+
+
+def _check_count(count, name: str = "count") -> int:
+    if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or int(count) < 1:
+        raise ValueError(f"{name} must be a positive integer, got {count!r}")
+    if int(count) >= LIMIT:
+        raise ValueError(f"{name} {count} exceeds the 2^31 limit of one call")
+    return int(count)
+
+
+def _check_threshold(threshold) -> float:
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+        raise ValueError(f"threshold must be a real number, got {threshold!r}")
+    if not math.isfinite(float(threshold)) or float(threshold) < 0:
+        raise ValueError(f"threshold must be finite and >= 0, got {threshold!r}")
+    return float(threshold)
+
+
+def _dev_points(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
+    return t.to(dev, torch.float64).contiguous()
+
+
+def nearest_distances(queries, targets, device=None) -> torch.Tensor:
+    """queries[n,3], targets[m,3] -> float64 [n] on the device: the distance of every query to its nearest target (sqrt of the kernel's
+    exact minimum of squared distances).  A NaN / inf coordinate raises ``lib.VfnError``."""
+    q, t = _check_points(queries, "queries"), _check_points(targets, "targets")
+    dev = _device(device)
+    return torch.sqrt(lib.nn_sqdist(_dev_points(q, dev), _dev_points(t, dev)))
+
+
+def face_areas(vertices, faces, device=None) -> torch.Tensor:
+    """-> areas[F] float64 on the device (csrc: vfn_tri_areas)."""
+    v, f = _check_mesh((vertices, faces), "mesh")
+    dev = _device(device)
+    return lib.tri_areas(_dev_points(v, dev), f.to(dev, torch.int64).contiguous())
+
+
+def sample_surface(vertices, faces, count: int, generator: Optional[torch.Generator] = None, uniforms=None, device=None):
+    """``count`` area-weighted points on the surface -> (points[count,3] float64, face_index[count] int64), device tensors.  A face is
+    chosen by its share of the cumulative area (a zero-area face never), the point by the folded-square barycentric rule.  ``uniforms``
+    ([count,3] in [0,1)) replaces the device's own random numbers; otherwise they come from ``generator`` (a device generator, or the
+    device's default one).  ValueError on no faces, on zero total area and on count < 1."""
+    v, f = _check_mesh((vertices, faces), "mesh")
+    count = _check_count(count)
+    u = None
+    if uniforms is not None:
+        u = _as_tensor(uniforms, "uniforms")
+        if tuple(u.shape) != (count, 3) or not u.dtype.is_floating_point:
+            raise ValueError(f"uniforms must be floating point [{count},3], got {u.dtype} {tuple(u.shape)}")
+    dev = _device(device)
+    v, f = _dev_points(v, dev), f.to(dev, torch.int64).contiguous()
+    cum = cumulative_areas(v, f)
+    if u is None:
+        u = torch.rand(count, 3, dtype=torch.float64, device=dev, generator=generator)
+    u = _dev_points(u, dev)
+    points, face_index, info = lib.sample_surface(v, f, cum, u)
+    return points, face_index
+
+
+def cumulative_areas(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """Device vertices / faces -> the inclusive cumulative-area table [F]: vfn_tri_areas, the fixed-tree scan vfn_cumsum_f64, then a
+    running maximum over the prefixes of the faces WITH area.  A tree scan rounds neighbouring prefixes along different paths, so
+    the raw prefixes may step down by an ulp, or up across a zero-area face; the running maximum (exact, so any evaluation order
+    gives the same bits) makes the table non-decreasing and level across every zero-area face — such a face can never be selected —
+    and keeps each entry within the scan's error bound (the maximum is a prefix of an earlier face, whose exact sum is no larger,
+    and at least the prefix of the last face with area, whose exact sum is the same).  One value crosses to the host: the total, to
+    refuse a surface without area."""
+    areas = lib.tri_areas(vertices, faces)
+    cum = lib.cumsum_f64(areas)
+    cum = torch.cummax(torch.where(areas > 0, cum, torch.zeros_like(cum)), dim=0).values
+    total = float(cum[-1].cpu())
+    if not total > 0.0:
+        raise ValueError("the mesh has zero total area: nothing to sample")
+    if not math.isfinite(total):
+        raise lib.VfnError("the mesh's total area is not finite")
+    return cum
+
+
+def _median_pair(sq: torch.Tensor) -> torch.Tensor:
+    """The two middle values of sq (equal for an odd count) as a device tensor [2]: np.median is their mean."""
+    n = sq.shape[0]
+    s = torch.sort(sq).values
+    return torch.stack((s[(n - 1) // 2], s[n // 2]))
+
+
+def _direction(dist: torch.Tensor, threshold: float) -> torch.Tensor:
+    """Nearest distances of one direction -> device [7]: sum, min, max of the SQUARED distances (the reference squares the KD-tree's
+    distances, utils.py:353-356), the two middle squares, n, number of distances < threshold."""
+    sq = dist * dist
+    s = lib.reduce_stats(sq, math.inf)
+    c = lib.reduce_stats(dist, threshold)
+    n = torch.tensor([float(dist.shape[0])], dtype=torch.float64, device=dist.device)
+    return torch.cat((s[:3], _median_pair(sq), n, c[3:4]))
+
+
+def _chamfer(one, two):
+    """Two host rows of ``_direction`` (ref -> pred, pred -> ref) -> (mean, median, min, max), utils.py:366-367."""
+    mean = one[0] / one[5] + two[0] / two[5]
+    median = (one[3] + one[4]) / 2.0 + (two[3] + two[4]) / 2.0
+    return float(mean), float(median), float(min(one[1], two[1])), float(max(one[2], two[2]))
+
+
+def _prf(pred_row, ref_row) -> dict:
+    n_p, n_r = int(pred_row[6]), int(ref_row[6])
+    p, r = n_p / int(pred_row[5]), n_r / int(ref_row[5])
+    return {"precision": p, "recall": r, "fscore": 2 * p * r / (p + r) if p + r > 0 else 0.0, "pred_within": n_p, "ref_within": n_r}
+
+
+def _both_directions(pred_points, ref_points, threshold: float, device=None):
+    """-> host float64 [2,7]: row 0 = the ref points against the pred set, row 1 = the pred points against the ref set.  One read."""
+    p, r = _check_points(pred_points, "pred_points"), _check_points(ref_points, "ref_points")
+    dev = _device(device)
+    p, r = _dev_points(p, dev), _dev_points(r, dev)
+    info = torch.zeros(1, dtype=torch.int64, device=dev)
+    one = _direction(torch.sqrt(lib.nn_sqdist(r, p, info=info)), threshold)
+    two = _direction(torch.sqrt(lib.nn_sqdist(p, r, info=info)), threshold)
+    host = torch.cat((one, two, info.to(torch.float64))).cpu().numpy()
+    lib.nn_check(int(host[14]))
+    return host[:14].reshape(2, 7)
+
+
+def chamfer_from_points(pred_points, ref_points, device=None) -> Tuple[float, float, float, float]:
+    """utils.py:350-367 on two point sets -> (mean, median, min, max) as Python floats: per direction the mean / median / min / max of
+    the squared nearest distances, then the sum of the means, the sum of the medians, the min of the mins, the max of the maxes.  The
+    median is np.median's (the mean of the two middle values for an even count)."""
+    rows = _both_directions(pred_points, ref_points, 0.0, device)
+    return _chamfer(rows[0], rows[1])
+
+
+def chamfer_distance(pred_mesh, ref_mesh, num_points: int = 2500000, generator: Optional[torch.Generator] = None, device=None):
+    """``utils.get_chamfer_distance``: ``num_points`` samples of each surface (pred first, then ref, from the same generator), then
+    ``chamfer_from_points``."""
+    pv, pf = _check_mesh(pred_mesh, "pred_mesh")
+    rv, rf = _check_mesh(ref_mesh, "ref_mesh")
+    num_points = _check_count(num_points, "num_points")
+    pred_points, _ = sample_surface(pv, pf, num_points, generator=generator, device=device)
+    ref_points, _ = sample_surface(rv, rf, num_points, generator=generator, device=device)
+    return chamfer_from_points(pred_points, ref_points, device=device)
+
+
+def precision_recall_fscore(pred_points, ref_points, threshold: float, device=None) -> dict:
+    """precision = the share of pred points whose nearest ref point is closer than ``threshold`` (distance < threshold), recall = the
+    share of ref points whose nearest pred point is closer than ``threshold``, fscore = 2 P R / (P + R), 0 when P + R = 0.  The counts
+    are returned too (``pred_within``, ``ref_within``).  This is the plain definition on the two point sets as given; it is NOT claimed
+    equal to the external ``evaluate_3d_reconstruction`` package the reference calls, which also voxel-down-samples both clouds and
+    optionally aligns them with ICP first."""
+    threshold = _check_threshold(threshold)
+    rows = _both_directions(pred_points, ref_points, threshold, device)
+    return _prf(rows[1], rows[0])
+
+
+def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: float = 0.05, generator: Optional[torch.Generator] = None,
+               uniforms=None, device=None) -> dict:
+    """One entry of the reference's ``3d-metrics.json`` (methods.py:794-801): {"chamfer distance": {mean, median, min, max}, "precision",
+    "recall", "fscore"} (plus the two counts), from ONE sampling of each mesh and ONE nearest-neighbour search per direction shared
+    by both metrics.  ``uniforms`` ([num_points,3]) is used for BOTH meshes when given."""
+    pv, pf = _check_mesh(pred_mesh, "pred_mesh")
+    rv, rf = _check_mesh(ref_mesh, "ref_mesh")
+    num_points = _check_count(num_points, "num_points")
+    threshold = _check_threshold(distance_thresh)
+    pred_points, _ = sample_surface(pv, pf, num_points, generator=generator, uniforms=uniforms, device=device)
+    ref_points, _ = sample_surface(rv, rf, num_points, generator=generator, uniforms=uniforms, device=device)
+    rows = _both_directions(pred_points, ref_points, threshold, device)
+    mean, median, mn, mx = _chamfer(rows[0], rows[1])
+    out = {"chamfer distance": {"mean": mean, "median": median, "min": mn, "max": mx}}
+    out.update(_prf(rows[1], rows[0]))
+    return out
