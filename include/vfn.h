@@ -762,6 +762,52 @@ int64_t vfn_reduce_stats_workspace_bytes(int64_t n);
 int vfn_reduce_stats(const double* x, int64_t n, double threshold, double* stats, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* =============================================================================================
+ * Fusing depth maps into a mesh (csrc/vfn_tsdf.hip): the stage of evaluation/methods.py:613-665 (tsdf_mesh) between the rendered depth
+ * maps and the mesh that metrics_3d scores, with the semantics of a uniform TSDF volume — projective integration with a running mean,
+ * classic marching cubes on the zero level set.  Two deliberate differences: the volume is DENSE over a box the caller gives (not
+ * hashed 16^3 blocks opened near back-projected points, so a voxel in free space in front of a surface collects tsdf = 1 observations
+ * that a hashed volume would never have allocated; the zero crossing lies inside the truncation band either way), and no colour.
+ * Volume: tsdf[nx, ny, nz] and weight[nx, ny, nz], float32, C order (k fastest), zero-filled by the caller before the first view;
+ * voxel (i, j, k) has its centre at origin + (index + 0.5) voxel_length.  nx ny nz < 2^31, voxel_length > 0, sdf_trunc > 0.
+ *   vfn_tsdf_integrate  depth[V, H, W] (float32 metres, 0 = no measurement), intrinsics[V, 4] = fx fy cx cy, extrinsics[V, 12] = the
+ *                     world -> camera rows e00 .. e23.  Per voxel and view, in float32, every operation rounded once in the
+ *                     association written (no contraction, correctly rounded / and sqrtf):
+ *                       x = ox + ((float)i + 0.5f) vl                                   (y, z alike)
+ *                       xc = ((e00 x + e01 y) + e02 z) + e03                            (yc, zc alike)
+ *                       skip unless zc > 0
+ *                       u = floorf(((xc fx) / zc + cx) + 0.5f);  v = floorf(((yc fy) / zc + cy) + 0.5f)
+ *                       skip unless 0 <= u < W and 0 <= v < H
+ *                       d = depth[v, u];  skip unless d > 0
+ *                       a = (u - cx) / fx;  b = (v - cy) / fy;  m = sqrtf((1.0f + a a) + b b)
+ *                       sdf = (d - zc) m;  skip unless sdf > -sdf_trunc
+ *                       t = fminf(1.0f, sdf / sdf_trunc)
+ *                       tsdf = (tsdf weight + t) / (weight + 1.0f);  weight = weight + 1.0f
+ *                     The views of one call are applied in index order per voxel, rounded to float32 after each: the bits of V
+ *                     single-view calls in that order.  The volume is read and written once per call, whatever V is.  A workgroup
+ *                     may skip a view that provably touches none of its voxels; skipping never changes a bit.
+ *   vfn_tsdf_count    cells (i, j, k), i < nx - 1, j < ny - 1, k < nz - 1, in C order; corners in the order of vfn_mesh_tables
+ *                     ((0,0,0) (0,1,0) (1,1,0) (1,0,0) (0,0,1) (0,1,1) (1,1,1) (1,0,1)).  A cell with any corner at weight == 0 counts
+ *                     0; case bit q is set iff tsdf_q < 0 (exactly 0 is outside); counts[cell] = triangles of the classic table's
+ *                     row, offsets = their inclusive scan, info[0] = triangles T.  counts / offsets: (nx-1)(ny-1)(nz-1) int32; the
+ *                     scan workspace is vfn_mesh_scan_workspace_bytes(cells).
+ *   vfn_tsdf_emit     tri_verts[3 T, 3] (double), triangles in the table row's order at slot 3 (offsets[cell] - counts[cell] + t) +
+ *                     corner: the layout vfn_mesh_dedup / vfn_mesh_number consume.  A vertex is computed from its edge alone — L the
+ *                     endpoint with the lower lattice index, U the other (one step along one axis), f = (double)|tsdf|:
+ *                       position[c] = (double)origin[c] + ((double)index_L[c] + 0.5) (double)vl       on all three axes
+ *                       position[axis] = position[axis] + (f_L / (f_L + f_U)) (double)vl
+ *                     in float64 without contraction, so the cells around an edge emit identical bits and the positional merge joins
+ *                     them; vertices that coincide at a corner whose tsdf is exactly 0 merge too, degenerate faces are kept.
+ * Limits: 3 T < 2^31.  No atomics.
+ * ============================================================================================= */
+int vfn_tsdf_integrate(float* tsdf, float* weight, int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz,
+                       float voxel_length, float sdf_trunc, const float* depth, int32_t height, int32_t width,
+                       const float* intrinsics, const float* extrinsics, int32_t n_views, void* stream);
+int vfn_tsdf_count(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, int32_t* counts, int32_t* offsets,
+                   int64_t* info, void* scan_ws, int64_t scan_ws_bytes, void* stream);
+int vfn_tsdf_emit(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz,
+                  float voxel_length, const int32_t* counts, const int32_t* offsets, double* tri_verts, void* stream);
+
+/* =============================================================================================
  * Optimizer side of a training step over ONE flat fp32 buffer (train/vector_field_nerf_train.py:254-260:
  * torch.nn.utils.clip_grad_norm_(model.parameters(), clip); optimizer.step()).  The unique parameters — and their gradients
  * and Adam moments — are laid out contiguously, sorted into up to four REGIONS [start, end) of equal multiplicity `mult` =

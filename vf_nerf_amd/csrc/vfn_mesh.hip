@@ -18,97 +18,7 @@
 // scope only; no float atomics.  All arithmetic in fp64 with -ffp-contract=off (build.sh): the reference's numpy expressions,
 // operation for operation.
 #include "vfn_common.h"
-#include <hipcub/hipcub.hpp>
-
-// The classic marching-cubes triangle table (Lorensen & Cline 1987, in the public form of P. Bourke's "Polygonising a scalar field"):
-// edges of up to five triangles per case, -1 terminated.  Corner / edge numbering: corners (0,0,0) (0,1,0) (1,1,0) (1,0,0) (0,0,1)
-// (0,1,1) (1,1,1) (1,0,1) (dimensions i, j, k), edge e joins EDGE_A[e] and EDGE_B[e].  The edge table is not stored: edge e of case c
-// is cut iff its two corners lie on different sides, which is what the classic 256-entry edge table lists.
-#define VFN_MC_TRI_ROWS                                                                                                           \
-    {-1}, {0, 8, 3, -1}, {0, 1, 9, -1}, {1, 8, 3, 9, 8, 1, -1}, {1, 2, 10, -1}, {0, 8, 3, 1, 2, 10, -1}, {9, 2, 10, 0, 2, 9, -1},  \
-    {2, 8, 3, 2, 10, 8, 10, 9, 8, -1}, {3, 11, 2, -1}, {0, 11, 2, 8, 11, 0, -1}, {1, 9, 0, 2, 3, 11, -1},                          \
-    {1, 11, 2, 1, 9, 11, 9, 8, 11, -1}, {3, 10, 1, 11, 10, 3, -1}, {0, 10, 1, 0, 8, 10, 8, 11, 10, -1},                            \
-    {3, 9, 0, 3, 11, 9, 11, 10, 9, -1}, {9, 8, 10, 10, 8, 11, -1}, {4, 7, 8, -1}, {4, 3, 0, 7, 3, 4, -1}, {0, 1, 9, 8, 4, 7, -1},  \
-    {4, 1, 9, 4, 7, 1, 7, 3, 1, -1}, {1, 2, 10, 8, 4, 7, -1}, {3, 4, 7, 3, 0, 4, 1, 2, 10, -1}, {9, 2, 10, 9, 0, 2, 8, 4, 7, -1},  \
-    {2, 10, 9, 2, 9, 7, 2, 7, 3, 7, 9, 4, -1}, {8, 4, 7, 3, 11, 2, -1}, {11, 4, 7, 11, 2, 4, 2, 0, 4, -1},                         \
-    {9, 0, 1, 8, 4, 7, 2, 3, 11, -1}, {4, 7, 11, 9, 4, 11, 9, 11, 2, 9, 2, 1, -1}, {3, 10, 1, 3, 11, 10, 7, 8, 4, -1},             \
-    {1, 11, 10, 1, 4, 11, 1, 0, 4, 7, 11, 4, -1}, {4, 7, 8, 9, 0, 11, 9, 11, 10, 11, 0, 3, -1},                                    \
-    {4, 7, 11, 4, 11, 9, 9, 11, 10, -1}, {9, 5, 4, -1}, {9, 5, 4, 0, 8, 3, -1}, {0, 5, 4, 1, 5, 0, -1},                            \
-    {8, 5, 4, 8, 3, 5, 3, 1, 5, -1}, {1, 2, 10, 9, 5, 4, -1}, {3, 0, 8, 1, 2, 10, 4, 9, 5, -1}, {5, 2, 10, 5, 4, 2, 4, 0, 2, -1},  \
-    {2, 10, 5, 3, 2, 5, 3, 5, 4, 3, 4, 8, -1}, {9, 5, 4, 2, 3, 11, -1}, {0, 11, 2, 0, 8, 11, 4, 9, 5, -1},                         \
-    {0, 5, 4, 0, 1, 5, 2, 3, 11, -1}, {2, 1, 5, 2, 5, 8, 2, 8, 11, 4, 8, 5, -1}, {10, 3, 11, 10, 1, 3, 9, 5, 4, -1},               \
-    {4, 9, 5, 0, 8, 1, 8, 10, 1, 8, 11, 10, -1}, {5, 4, 0, 5, 0, 11, 5, 11, 10, 11, 0, 3, -1},                                     \
-    {5, 4, 8, 5, 8, 10, 10, 8, 11, -1}, {9, 7, 8, 5, 7, 9, -1}, {9, 3, 0, 9, 5, 3, 5, 7, 3, -1}, {0, 7, 8, 0, 1, 7, 1, 5, 7, -1},  \
-    {1, 5, 3, 3, 5, 7, -1}, {9, 7, 8, 9, 5, 7, 10, 1, 2, -1}, {10, 1, 2, 9, 5, 0, 5, 3, 0, 5, 7, 3, -1},                           \
-    {8, 0, 2, 8, 2, 5, 8, 5, 7, 10, 5, 2, -1}, {2, 10, 5, 2, 5, 3, 3, 5, 7, -1}, {7, 9, 5, 7, 8, 9, 3, 11, 2, -1},                 \
-    {9, 5, 7, 9, 7, 2, 9, 2, 0, 2, 7, 11, -1}, {2, 3, 11, 0, 1, 8, 1, 7, 8, 1, 5, 7, -1}, {11, 2, 1, 11, 1, 7, 7, 1, 5, -1},       \
-    {9, 5, 8, 8, 5, 7, 10, 1, 3, 10, 3, 11, -1}, {5, 7, 0, 5, 0, 9, 7, 11, 0, 1, 0, 10, 11, 10, 0, -1},                            \
-    {11, 10, 0, 11, 0, 3, 10, 5, 0, 8, 0, 7, 5, 7, 0, -1}, {11, 10, 5, 7, 11, 5, -1}, {10, 6, 5, -1}, {0, 8, 3, 5, 10, 6, -1},     \
-    {9, 0, 1, 5, 10, 6, -1}, {1, 8, 3, 1, 9, 8, 5, 10, 6, -1}, {1, 6, 5, 2, 6, 1, -1}, {1, 6, 5, 1, 2, 6, 3, 0, 8, -1},            \
-    {9, 6, 5, 9, 0, 6, 0, 2, 6, -1}, {5, 9, 8, 5, 8, 2, 5, 2, 6, 3, 2, 8, -1}, {2, 3, 11, 10, 6, 5, -1},                           \
-    {11, 0, 8, 11, 2, 0, 10, 6, 5, -1}, {0, 1, 9, 2, 3, 11, 5, 10, 6, -1}, {5, 10, 6, 1, 9, 2, 9, 11, 2, 9, 8, 11, -1},            \
-    {6, 3, 11, 6, 5, 3, 5, 1, 3, -1}, {0, 8, 11, 0, 11, 5, 0, 5, 1, 5, 11, 6, -1}, {3, 11, 6, 0, 3, 6, 0, 6, 5, 0, 5, 9, -1},      \
-    {6, 5, 9, 6, 9, 11, 11, 9, 8, -1}, {5, 10, 6, 4, 7, 8, -1}, {4, 3, 0, 4, 7, 3, 6, 5, 10, -1}, {1, 9, 0, 5, 10, 6, 8, 4, 7, -1}, \
-    {10, 6, 5, 1, 9, 7, 1, 7, 3, 7, 9, 4, -1}, {6, 1, 2, 6, 5, 1, 4, 7, 8, -1}, {1, 2, 5, 5, 2, 6, 3, 0, 4, 3, 4, 7, -1},          \
-    {8, 4, 7, 9, 0, 5, 0, 6, 5, 0, 2, 6, -1}, {7, 3, 9, 7, 9, 4, 3, 2, 9, 5, 9, 6, 2, 6, 9, -1},                                   \
-    {3, 11, 2, 7, 8, 4, 10, 6, 5, -1}, {5, 10, 6, 4, 7, 2, 4, 2, 0, 2, 7, 11, -1}, {0, 1, 9, 4, 7, 8, 2, 3, 11, 5, 10, 6, -1},     \
-    {9, 2, 1, 9, 11, 2, 9, 4, 11, 7, 11, 4, 5, 10, 6, -1}, {8, 4, 7, 3, 11, 5, 3, 5, 1, 5, 11, 6, -1},                             \
-    {5, 1, 11, 5, 11, 6, 1, 0, 11, 7, 11, 4, 0, 4, 11, -1}, {0, 5, 9, 0, 6, 5, 0, 3, 6, 11, 6, 3, 8, 4, 7, -1},                    \
-    {6, 5, 9, 6, 9, 11, 4, 7, 9, 7, 11, 9, -1}, {10, 4, 9, 6, 4, 10, -1}, {4, 10, 6, 4, 9, 10, 0, 8, 3, -1},                       \
-    {10, 0, 1, 10, 6, 0, 6, 4, 0, -1}, {8, 3, 1, 8, 1, 6, 8, 6, 4, 6, 1, 10, -1}, {1, 4, 9, 1, 2, 4, 2, 6, 4, -1},                 \
-    {3, 0, 8, 1, 2, 9, 2, 4, 9, 2, 6, 4, -1}, {0, 2, 4, 4, 2, 6, -1}, {8, 3, 2, 8, 2, 4, 4, 2, 6, -1},                             \
-    {10, 4, 9, 10, 6, 4, 11, 2, 3, -1}, {0, 8, 2, 2, 8, 11, 4, 9, 10, 4, 10, 6, -1}, {3, 11, 2, 0, 1, 6, 0, 6, 4, 6, 1, 10, -1},   \
-    {6, 4, 1, 6, 1, 10, 4, 8, 1, 2, 1, 11, 8, 11, 1, -1}, {9, 6, 4, 9, 3, 6, 9, 1, 3, 11, 6, 3, -1},                               \
-    {8, 11, 1, 8, 1, 0, 11, 6, 1, 9, 1, 4, 6, 4, 1, -1}, {3, 11, 6, 3, 6, 0, 0, 6, 4, -1}, {6, 4, 8, 11, 6, 8, -1},                \
-    {7, 10, 6, 7, 8, 10, 8, 9, 10, -1}, {0, 7, 3, 0, 10, 7, 0, 9, 10, 6, 7, 10, -1}, {10, 6, 7, 1, 10, 7, 1, 7, 8, 1, 8, 0, -1},   \
-    {10, 6, 7, 10, 7, 1, 1, 7, 3, -1}, {1, 2, 6, 1, 6, 8, 1, 8, 9, 8, 6, 7, -1}, {2, 6, 9, 2, 9, 1, 6, 7, 9, 0, 9, 3, 7, 3, 9, -1}, \
-    {7, 8, 0, 7, 0, 6, 6, 0, 2, -1}, {7, 3, 2, 6, 7, 2, -1}, {2, 3, 11, 10, 6, 8, 10, 8, 9, 8, 6, 7, -1},                          \
-    {2, 0, 7, 2, 7, 11, 0, 9, 7, 6, 7, 10, 9, 10, 7, -1}, {1, 8, 0, 1, 7, 8, 1, 10, 7, 6, 7, 10, 2, 3, 11, -1},                    \
-    {11, 2, 1, 11, 1, 7, 10, 6, 1, 6, 7, 1, -1}, {8, 9, 6, 8, 6, 7, 9, 1, 6, 11, 6, 3, 1, 3, 6, -1}, {0, 9, 1, 11, 6, 7, -1},      \
-    {7, 8, 0, 7, 0, 6, 3, 11, 0, 11, 6, 0, -1}, {7, 11, 6, -1}, {7, 6, 11, -1}, {3, 0, 8, 11, 7, 6, -1}, {0, 1, 9, 11, 7, 6, -1},  \
-    {8, 1, 9, 8, 3, 1, 11, 7, 6, -1}, {10, 1, 2, 6, 11, 7, -1}, {1, 2, 10, 3, 0, 8, 6, 11, 7, -1}, {2, 9, 0, 2, 10, 9, 6, 11, 7, -1}, \
-    {6, 11, 7, 2, 10, 3, 10, 8, 3, 10, 9, 8, -1}, {7, 2, 3, 6, 2, 7, -1}, {7, 0, 8, 7, 6, 0, 6, 2, 0, -1},                         \
-    {2, 7, 6, 2, 3, 7, 0, 1, 9, -1}, {1, 6, 2, 1, 8, 6, 1, 9, 8, 8, 7, 6, -1}, {10, 7, 6, 10, 1, 7, 1, 3, 7, -1},                  \
-    {10, 7, 6, 1, 7, 10, 1, 8, 7, 1, 0, 8, -1}, {0, 3, 7, 0, 7, 10, 0, 10, 9, 6, 10, 7, -1}, {7, 6, 10, 7, 10, 8, 8, 10, 9, -1},   \
-    {6, 8, 4, 11, 8, 6, -1}, {3, 6, 11, 3, 0, 6, 0, 4, 6, -1}, {8, 6, 11, 8, 4, 6, 9, 0, 1, -1},                                   \
-    {9, 4, 6, 9, 6, 3, 9, 3, 1, 11, 3, 6, -1}, {6, 8, 4, 6, 11, 8, 2, 10, 1, -1}, {1, 2, 10, 3, 0, 11, 0, 6, 11, 0, 4, 6, -1},     \
-    {4, 11, 8, 4, 6, 11, 0, 2, 9, 2, 10, 9, -1}, {10, 9, 3, 10, 3, 2, 9, 4, 3, 11, 3, 6, 4, 6, 3, -1},                             \
-    {8, 2, 3, 8, 4, 2, 4, 6, 2, -1}, {0, 4, 2, 4, 6, 2, -1}, {1, 9, 0, 2, 3, 4, 2, 4, 6, 4, 3, 8, -1},                             \
-    {1, 9, 4, 1, 4, 2, 2, 4, 6, -1}, {8, 1, 3, 8, 6, 1, 8, 4, 6, 6, 10, 1, -1}, {10, 1, 0, 10, 0, 6, 6, 0, 4, -1},                 \
-    {4, 6, 3, 4, 3, 8, 6, 10, 3, 0, 3, 9, 10, 9, 3, -1}, {10, 9, 4, 6, 10, 4, -1}, {4, 9, 5, 7, 6, 11, -1},                        \
-    {0, 8, 3, 4, 9, 5, 11, 7, 6, -1}, {5, 0, 1, 5, 4, 0, 7, 6, 11, -1}, {11, 7, 6, 8, 3, 4, 3, 5, 4, 3, 1, 5, -1},                 \
-    {9, 5, 4, 10, 1, 2, 7, 6, 11, -1}, {6, 11, 7, 1, 2, 10, 0, 8, 3, 4, 9, 5, -1}, {7, 6, 11, 5, 4, 10, 4, 2, 10, 4, 0, 2, -1},    \
-    {3, 4, 8, 3, 5, 4, 3, 2, 5, 10, 5, 2, 11, 7, 6, -1}, {7, 2, 3, 7, 6, 2, 5, 4, 9, -1}, {9, 5, 4, 0, 8, 6, 0, 6, 2, 6, 8, 7, -1}, \
-    {3, 6, 2, 3, 7, 6, 1, 5, 0, 5, 4, 0, -1}, {6, 2, 8, 6, 8, 7, 2, 1, 8, 4, 8, 5, 1, 5, 8, -1},                                   \
-    {9, 5, 4, 10, 1, 6, 1, 7, 6, 1, 3, 7, -1}, {1, 6, 10, 1, 7, 6, 1, 0, 7, 8, 7, 0, 9, 5, 4, -1},                                 \
-    {4, 0, 10, 4, 10, 5, 0, 3, 10, 6, 10, 7, 3, 7, 10, -1}, {7, 6, 10, 7, 10, 8, 5, 4, 10, 4, 8, 10, -1},                          \
-    {6, 9, 5, 6, 11, 9, 11, 8, 9, -1}, {3, 6, 11, 0, 6, 3, 0, 5, 6, 0, 9, 5, -1}, {0, 11, 8, 0, 5, 11, 0, 1, 5, 5, 6, 11, -1},     \
-    {6, 11, 3, 6, 3, 5, 5, 3, 1, -1}, {1, 2, 10, 9, 5, 11, 9, 11, 8, 11, 5, 6, -1},                                                \
-    {0, 11, 3, 0, 6, 11, 0, 9, 6, 5, 6, 9, 1, 2, 10, -1}, {11, 8, 5, 11, 5, 6, 8, 0, 5, 10, 5, 2, 0, 2, 5, -1},                    \
-    {6, 11, 3, 6, 3, 5, 2, 10, 3, 10, 5, 3, -1}, {5, 8, 9, 5, 2, 8, 5, 6, 2, 3, 8, 2, -1}, {9, 5, 6, 9, 6, 0, 0, 6, 2, -1},        \
-    {1, 5, 8, 1, 8, 0, 5, 6, 8, 3, 8, 2, 6, 2, 8, -1}, {1, 5, 6, 2, 1, 6, -1}, {1, 3, 6, 1, 6, 10, 3, 8, 6, 5, 6, 9, 8, 9, 6, -1}, \
-    {10, 1, 0, 10, 0, 6, 9, 5, 0, 5, 6, 0, -1}, {0, 3, 8, 5, 6, 10, -1}, {10, 5, 6, -1}, {11, 5, 10, 7, 5, 11, -1},                \
-    {11, 5, 10, 11, 7, 5, 8, 3, 0, -1}, {5, 11, 7, 5, 10, 11, 1, 9, 0, -1}, {10, 7, 5, 10, 11, 7, 9, 8, 1, 8, 3, 1, -1},           \
-    {11, 1, 2, 11, 7, 1, 7, 5, 1, -1}, {0, 8, 3, 1, 2, 7, 1, 7, 5, 7, 2, 11, -1}, {9, 7, 5, 9, 2, 7, 9, 0, 2, 2, 11, 7, -1},       \
-    {7, 5, 2, 7, 2, 11, 5, 9, 2, 3, 2, 8, 9, 8, 2, -1}, {2, 5, 10, 2, 3, 5, 3, 7, 5, -1}, {8, 2, 0, 8, 5, 2, 8, 7, 5, 10, 2, 5, -1}, \
-    {9, 0, 1, 5, 10, 3, 5, 3, 7, 3, 10, 2, -1}, {9, 8, 2, 9, 2, 1, 8, 7, 2, 10, 2, 5, 7, 5, 2, -1}, {1, 3, 5, 3, 7, 5, -1},        \
-    {0, 8, 7, 0, 7, 1, 1, 7, 5, -1}, {9, 0, 3, 9, 3, 5, 5, 3, 7, -1}, {9, 8, 7, 5, 9, 7, -1}, {5, 8, 4, 5, 10, 8, 10, 11, 8, -1},  \
-    {5, 0, 4, 5, 11, 0, 5, 10, 11, 11, 3, 0, -1}, {0, 1, 9, 8, 4, 10, 8, 10, 11, 10, 4, 5, -1},                                    \
-    {10, 11, 4, 10, 4, 5, 11, 3, 4, 9, 4, 1, 3, 1, 4, -1}, {2, 5, 1, 2, 8, 5, 2, 11, 8, 4, 5, 8, -1},                              \
-    {0, 4, 11, 0, 11, 3, 4, 5, 11, 2, 11, 1, 5, 1, 11, -1}, {0, 2, 5, 0, 5, 9, 2, 11, 5, 4, 5, 8, 11, 8, 5, -1},                   \
-    {9, 4, 5, 2, 11, 3, -1}, {2, 5, 10, 3, 5, 2, 3, 4, 5, 3, 8, 4, -1}, {5, 10, 2, 5, 2, 4, 4, 2, 0, -1},                          \
-    {3, 10, 2, 3, 5, 10, 3, 8, 5, 4, 5, 8, 0, 1, 9, -1}, {5, 10, 2, 5, 2, 4, 1, 9, 2, 9, 4, 2, -1}, {8, 4, 5, 8, 5, 3, 3, 5, 1, -1}, \
-    {0, 4, 5, 1, 0, 5, -1}, {8, 4, 5, 8, 5, 3, 9, 0, 5, 0, 3, 5, -1}, {9, 4, 5, -1}, {4, 11, 7, 4, 9, 11, 9, 10, 11, -1},          \
-    {0, 8, 3, 4, 9, 7, 9, 11, 7, 9, 10, 11, -1}, {1, 10, 11, 1, 11, 4, 1, 4, 0, 7, 4, 11, -1},                                     \
-    {3, 1, 4, 3, 4, 8, 1, 10, 4, 7, 4, 11, 10, 11, 4, -1}, {4, 11, 7, 9, 11, 4, 9, 2, 11, 9, 1, 2, -1},                            \
-    {9, 7, 4, 9, 11, 7, 9, 1, 11, 2, 11, 1, 0, 8, 3, -1}, {11, 7, 4, 11, 4, 2, 2, 4, 0, -1}, {11, 7, 4, 11, 4, 2, 8, 3, 4, 3, 2, 4, -1}, \
-    {2, 9, 10, 2, 7, 9, 2, 3, 7, 7, 4, 9, -1}, {9, 10, 7, 9, 7, 4, 10, 2, 7, 8, 7, 0, 2, 0, 7, -1},                                \
-    {3, 7, 10, 3, 10, 2, 7, 4, 10, 1, 10, 0, 4, 0, 10, -1}, {1, 10, 2, 8, 7, 4, -1}, {4, 9, 1, 4, 1, 7, 7, 1, 3, -1},              \
-    {4, 9, 1, 4, 1, 7, 0, 8, 1, 8, 7, 1, -1}, {4, 0, 3, 7, 4, 3, -1}, {4, 8, 7, -1}, {9, 10, 8, 10, 11, 8, -1},                    \
-    {3, 0, 9, 3, 9, 11, 11, 9, 10, -1}, {0, 1, 10, 0, 10, 8, 8, 10, 11, -1}, {3, 1, 10, 11, 3, 10, -1},                            \
-    {1, 2, 11, 1, 11, 9, 9, 11, 8, -1}, {3, 0, 9, 3, 9, 11, 1, 2, 9, 2, 11, 9, -1}, {0, 2, 11, 8, 0, 11, -1}, {3, 2, 11, -1},      \
-    {2, 3, 8, 2, 8, 10, 10, 8, 9, -1}, {9, 10, 2, 0, 9, 2, -1}, {2, 3, 8, 2, 8, 10, 0, 1, 8, 1, 10, 8, -1}, {1, 10, 2, -1},        \
-    {1, 3, 8, 9, 1, 8, -1}, {0, 9, 1, -1}, {0, 3, 8, -1}, {-1}
+#include "vfn_mc_tables.h"     // VFN_MC_TRI_ROWS, the edge / corner tables, the ordered scan
 
 namespace {
 
@@ -116,12 +26,12 @@ namespace {
 const signed char TRI_HOST[256][16] = {VFN_MC_TRI_ROWS};
 __device__ __constant__ signed char TRI[256][16] = {VFN_MC_TRI_ROWS};
 // marching_cubes_lookup.EDGE_VERTEX order: edge 3 is (0, 3), edge 7 is (4, 7)
-const int EDGE_A_HOST[12] = {0, 1, 2, 0, 4, 5, 6, 4, 0, 1, 2, 3};
-const int EDGE_B_HOST[12] = {1, 2, 3, 3, 5, 6, 7, 7, 4, 5, 6, 7};
-__device__ __constant__ int EDGE_A[12] = {0, 1, 2, 0, 4, 5, 6, 4, 0, 1, 2, 3};
-__device__ __constant__ int EDGE_B[12] = {1, 2, 3, 3, 5, 6, 7, 7, 4, 5, 6, 7};
+const int EDGE_A_HOST[12] = VFN_MC_EDGE_A;
+const int EDGE_B_HOST[12] = VFN_MC_EDGE_B;
+__device__ __constant__ int EDGE_A[12] = VFN_MC_EDGE_A;
+__device__ __constant__ int EDGE_B[12] = VFN_MC_EDGE_B;
 // marching_cubes_vt.inc: corner q of cell (i, j, k) is (i, j, k) + INC[q]
-__device__ __constant__ int INC[8][3] = {{0, 0, 0}, {0, 1, 0}, {1, 1, 0}, {1, 0, 0}, {0, 0, 1}, {0, 1, 1}, {1, 1, 1}, {1, 0, 1}};
+__device__ __constant__ int INC[8][3] = VFN_MC_INC;
 // the 28 corner pairs (a < b) in the order of marching_cubes_vt.combs, and pair index of (a, b) for a < b
 __device__ __constant__ unsigned char PA[28] = {0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 5, 5, 6};
 __device__ __constant__ unsigned char PB[28] = {1, 2, 3, 4, 5, 6, 7, 2, 3, 4, 5, 6, 7, 3, 4, 5, 6, 7, 4, 5, 6, 7, 5, 6, 7, 6, 7, 7};
@@ -366,22 +276,10 @@ __global__ __launch_bounds__(256) void vfn_mesh_field_norms_kernel(const float* 
 
 inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
 
-int scan_bytes(long long n, size_t* bytes) {
-    *bytes = 0;
-    const hipError_t e = hipcub::DeviceScan::InclusiveSum(nullptr, *bytes, (const int*)nullptr, (int*)nullptr, (int)n);
-    return e == hipSuccess ? VFN_OK : VFN_ERR_LAUNCH;
-}
+int scan_bytes(long long n, size_t* bytes) { return vfn_mc_scan_bytes(n, bytes); }
 
 int inclusive_scan(const int* in, int* out, long long n, void* ws, long long ws_bytes, hipStream_t s, const char* what) {
-    size_t need = 0;
-    VFN_REQUIRE(scan_bytes(n, &need) == VFN_OK, "%s: scan size query failed", what);
-    VFN_REQUIRE(ws && (long long)need <= ws_bytes, "%s: scan workspace of %lld bytes < %lld needed", what, ws_bytes, (long long)need);
-    const hipError_t e = hipcub::DeviceScan::InclusiveSum(ws, need, in, out, (int)n, s);
-    if (e != hipSuccess) {
-        vfn_set_error("%s: scan failed: %s", what, hipGetErrorString(e));
-        return VFN_ERR_LAUNCH;
-    }
-    return VFN_OK;
+    return vfn_mc_inclusive_scan(in, out, n, ws, ws_bytes, s, what);
 }
 
 int make_args(MeshArgs& a, int32_t form, const void* comb, const void* udf, int32_t f64, const int64_t* cells, const uint8_t* sides,

@@ -1,0 +1,336 @@
+// vfn_tsdf.hip — a dense truncated-signed-distance volume on the device: the stage between the rendered depth maps and the mesh that
+// evaluation/methods.py:613-665 (tsdf_mesh) reports, with the semantics of a uniform TSDF volume (projective integration with a
+// running mean, extraction of the zero level set with classic marching cubes).  include/vfn.h states the arithmetic; here:
+//   integrate  ONE pass over the volume for ALL views of a call.  A lane owns RUN = 4 consecutive k voxels (16-B loads and stores of
+//              tsdf and weight), keeps them in registers and applies the views in index order, rounding after each: the bits of V
+//              single-view calls.  A workgroup covers a brick of 4 x 8 x 32 voxels; its 256 lanes first test one view each against the
+//              brick (below), the ballots go to LDS, and every wave then walks the set bits in ascending order — the view index is
+//              wave-uniform, so the 16 per-view parameters are scalar loads, not per-lane ones.  The depth reads are gathers:
+//              neighbouring lanes project to neighbouring pixels and the caches serve them.
+//   brick test A view is skipped for a brick only when NO voxel centre of the brick can pass the per-voxel tests.  The test uses the
+//              voxel's own fp32 expressions at the brick's extreme centres: every operation of x -> xc -> (xc fx) / zc + cx + 0.5 is
+//              monotone in each operand once the signs of the coefficients are fixed, and rounding keeps order (a <= b gives
+//              fl(a) <= fl(b)), so the extreme of the ROUNDED value over the brick is the rounded value at a corner — no margin, no
+//              second arithmetic.  A NaN anywhere makes every comparison false and the view is kept.
+//   count/emit one lane per cell in C order: the case from the signs of the eight corner values (a corner with weight 0 voids the cell),
+//              the triangle count, the ordered scan of the mesh unit, then every triangle's three float64 vertices at their slots in
+//              the layout vfn_mesh_dedup / vfn_mesh_number consume.  A vertex is a function of its edge alone, so the (up to) four
+//              cells around an edge emit identical bits and the positional merge joins them.
+// No atomics.  fp32 (integration) and fp64 (vertices) without contraction: -ffp-contract=off (build.sh), correctly rounded / and sqrtf.
+#include "vfn_common.h"
+#include "vfn_mc_tables.h"
+
+namespace {
+
+__device__ __constant__ signed char TRI[256][16] = {VFN_MC_TRI_ROWS};
+__device__ __constant__ int EDGE_A[12] = VFN_MC_EDGE_A;
+__device__ __constant__ int EDGE_B[12] = VFN_MC_EDGE_B;
+__device__ __constant__ int INC[8][3] = VFN_MC_INC;
+
+constexpr int RUN = 4;                     // consecutive k voxels of a lane: one 16-B access per array
+constexpr int BK_RUNS = 8, BJ = 8, BI = 4; // lanes of a workgroup along k (runs), j, i: a brick of 4 x 8 x 32 voxels, one i-slab per wave
+constexpr int BK = BK_RUNS * RUN;
+constexpr int THREADS = BK_RUNS * BJ * BI;
+static_assert(THREADS == 256, "one view per lane in the brick test, four ballots per round");
+
+struct Volume {
+    float* tsdf;
+    float* weight;
+    int nx, ny, nz;
+    float ox, oy, oz, vl, trunc;
+};
+
+struct Views {
+    const float* depth;        // [V, H, W]
+    const float* intr;         // [V, 4]: fx fy cx cy
+    const float* extr;         // [V, 12]: world -> camera rows
+    int n, h, w;
+};
+
+__device__ __forceinline__ float centre(float o, int i, float vl) { return o + ((float)i + 0.5f) * vl; }
+
+__device__ __forceinline__ float cam_row(const float* __restrict__ e, float x, float y, float z) {
+    return ((e[0] * x + e[1] * y) + e[2] * z) + e[3];
+}
+
+// the largest / smallest ROUNDED value of cam_row over the box [lo, hi]^3 of voxel centres: at the corner the coefficient signs select
+__device__ __forceinline__ float row_max(const float* __restrict__ e, const float lo[3], const float hi[3]) {
+    return cam_row(e, e[0] >= 0.f ? hi[0] : lo[0], e[1] >= 0.f ? hi[1] : lo[1], e[2] >= 0.f ? hi[2] : lo[2]);
+}
+__device__ __forceinline__ float row_min(const float* __restrict__ e, const float lo[3], const float hi[3]) {
+    return cam_row(e, e[0] >= 0.f ? lo[0] : hi[0], e[1] >= 0.f ? lo[1] : hi[1], e[2] >= 0.f ? lo[2] : hi[2]);
+}
+
+// One image axis: can floorf(((c f) / zc + p) + 0.5f) lie in [0, size) for some c in [c_lo, c_hi], zc in [z_lo, z_hi], zc > 0?
+// (f > 0.)  n / zc with zc > 0 falls with zc where n >= 0 and rises where n < 0; without a positive lower bound of zc a positive
+// quotient is unbounded.  false only when every candidate is provably outside.
+__device__ __forceinline__ bool axis_may_hit(float c_lo, float c_hi, float z_lo, float z_hi, float f, float p, float size) {
+    const float n_hi = c_hi * f, n_lo = c_lo * f;
+    if (n_hi < 0.f) {                                         // largest quotient at the largest zc
+        if (((n_hi / z_hi + p) + 0.5f) < 0.f) return false;
+    } else if (n_hi >= 0.f && z_lo > 0.f) {                   // largest quotient at the smallest zc
+        if (((n_hi / z_lo + p) + 0.5f) < 0.f) return false;
+    }
+    if (n_lo >= 0.f) {                                        // smallest quotient at the largest zc
+        if (((n_lo / z_hi + p) + 0.5f) >= size) return false;
+    } else if (n_lo < 0.f && z_lo > 0.f) {                    // smallest quotient at the smallest zc
+        if (((n_lo / z_lo + p) + 0.5f) >= size) return false;
+    }
+    return true;
+}
+
+__device__ bool brick_may_see(const float* __restrict__ e, const float* __restrict__ k, const float lo[3], const float hi[3], float wf, float hf) {
+    const float z_hi = row_max(e + 8, lo, hi);
+    if (z_hi <= 0.f) return false;                            // zc <= 0 for every voxel of the brick
+    const float fx = k[0], fy = k[1];
+    if (!(fx > 0.f) || !(fy > 0.f)) return true;              // (the monotonicity argument needs positive focal lengths)
+    const float z_lo = row_min(e + 8, lo, hi);
+    if (!axis_may_hit(row_min(e, lo, hi), row_max(e, lo, hi), z_lo, z_hi, fx, k[2], wf)) return false;
+    if (!axis_may_hit(row_min(e + 4, lo, hi), row_max(e + 4, lo, hi), z_lo, z_hi, fy, k[3], hf)) return false;
+    return true;
+}
+
+// one view into the RUN voxels of a lane (include/vfn.h: the association is the contract)
+__device__ __forceinline__ void integrate_view(const Views& vs, int view, float x, float y, const float z[RUN], int cnt, float trunc,
+                                               float ts[RUN], float wt[RUN]) {
+    const float* __restrict__ e = vs.extr + (long long)view * 12;
+    const float* __restrict__ k = vs.intr + (long long)view * 4;
+    const float* __restrict__ dv = vs.depth + (long long)view * vs.h * vs.w;
+    const float fx = k[0], fy = k[1], cx = k[2], cy = k[3];
+    const float wf = (float)vs.w, hf = (float)vs.h;
+    const float px = e[0] * x + e[1] * y, py = e[4] * x + e[5] * y, pz = e[8] * x + e[9] * y;      // (the z-independent sums)
+#pragma unroll
+    for (int r = 0; r < RUN; ++r) {
+        if (r >= cnt) continue;
+        const float zc = (pz + e[10] * z[r]) + e[11];
+        if (!(zc > 0.f)) continue;
+        const float xc = (px + e[2] * z[r]) + e[3], yc = (py + e[6] * z[r]) + e[7];
+        const float u = floorf(((xc * fx) / zc + cx) + 0.5f), v = floorf(((yc * fy) / zc + cy) + 0.5f);
+        if (!(u >= 0.f && u < wf && v >= 0.f && v < hf)) continue;
+        const float d = dv[(long long)(int)v * vs.w + (int)u];
+        if (!(d > 0.f)) continue;
+        const float a = (u - cx) / fx, b = (v - cy) / fy;
+        const float m = sqrtf((1.0f + a * a) + b * b);
+        const float sdf = (d - zc) * m;
+        if (!(sdf > -trunc)) continue;
+        const float t = fminf(1.0f, sdf / trunc);
+        ts[r] = (ts[r] * wt[r] + t) / (wt[r] + 1.0f);
+        wt[r] = wt[r] + 1.0f;
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(THREADS) void vfn_tsdf_integrate_kernel(Volume vol, Views vs, int nbj, int nbk) {
+    __shared__ unsigned long long seen[THREADS / 64];
+    const long long b = blockIdx.x;
+    const int bk = (int)(b % nbk), bj = (int)((b / nbk) % nbj), bi = (int)(b / ((long long)nbk * nbj));
+    const int t = threadIdx.x;
+    const int i = bi * BI + (t >> 6), j = bj * BJ + ((t >> 3) & 7), k0 = bk * BK + (t & 7) * RUN;
+    const bool live = i < vol.nx && j < vol.ny && k0 < vol.nz;
+    const int cnt = live ? min(RUN, vol.nz - k0) : 0;
+    const long long off = ((long long)i * vol.ny + j) * vol.nz + k0;
+
+    float ts[RUN] = {0.f, 0.f, 0.f, 0.f}, wt[RUN] = {0.f, 0.f, 0.f, 0.f}, z[RUN];
+    if (live) {
+        if (VEC) {
+            const float4 a = *reinterpret_cast<const float4*>(vol.tsdf + off), c = *reinterpret_cast<const float4*>(vol.weight + off);
+            ts[0] = a.x; ts[1] = a.y; ts[2] = a.z; ts[3] = a.w;
+            wt[0] = c.x; wt[1] = c.y; wt[2] = c.z; wt[3] = c.w;
+        } else {
+            for (int r = 0; r < cnt; ++r) { ts[r] = vol.tsdf[off + r]; wt[r] = vol.weight[off + r]; }
+        }
+    }
+    const float x = centre(vol.ox, i, vol.vl), y = centre(vol.oy, j, vol.vl);
+#pragma unroll
+    for (int r = 0; r < RUN; ++r) z[r] = centre(vol.oz, k0 + r, vol.vl);
+
+    // the brick's extreme voxel centres (the same fp32 expression the lanes evaluate: monotone in the index)
+    const float lo[3] = {centre(vol.ox, bi * BI, vol.vl), centre(vol.oy, bj * BJ, vol.vl), centre(vol.oz, bk * BK, vol.vl)};
+    const float hi[3] = {centre(vol.ox, min(bi * BI + BI, vol.nx) - 1, vol.vl), centre(vol.oy, min(bj * BJ + BJ, vol.ny) - 1, vol.vl),
+                         centre(vol.oz, min(bk * BK + BK, vol.nz) - 1, vol.vl)};
+    const float wf = (float)vs.w, hf = (float)vs.h;
+
+    for (int base = 0; base < vs.n; base += THREADS) {
+        const int mine = base + t;
+        const bool may = mine < vs.n && brick_may_see(vs.extr + (long long)mine * 12, vs.intr + (long long)mine * 4, lo, hi, wf, hf);
+        const unsigned long long ballot = __ballot(may);
+        if ((t & 63) == 0) seen[t >> 6] = ballot;
+        __syncthreads();
+        for (int g = 0; g < THREADS / 64; ++g) {
+            const unsigned long long m64 = seen[g];
+            unsigned m_lo = __builtin_amdgcn_readfirstlane((unsigned)m64), m_hi = __builtin_amdgcn_readfirstlane((unsigned)(m64 >> 32));
+            while (m_lo) {                                    // ascending view order
+                const int bit = __builtin_ctz(m_lo);
+                m_lo &= m_lo - 1;
+                integrate_view(vs, base + g * 64 + bit, x, y, z, cnt, vol.trunc, ts, wt);
+            }
+            while (m_hi) {
+                const int bit = __builtin_ctz(m_hi);
+                m_hi &= m_hi - 1;
+                integrate_view(vs, base + g * 64 + 32 + bit, x, y, z, cnt, vol.trunc, ts, wt);
+            }
+        }
+        __syncthreads();
+    }
+
+    if (live) {
+        if (VEC) {
+            *reinterpret_cast<float4*>(vol.tsdf + off) = make_float4(ts[0], ts[1], ts[2], ts[3]);
+            *reinterpret_cast<float4*>(vol.weight + off) = make_float4(wt[0], wt[1], wt[2], wt[3]);
+        } else {
+            for (int r = 0; r < cnt; ++r) { vol.tsdf[off + r] = ts[r]; vol.weight[off + r] = wt[r]; }
+        }
+    }
+}
+
+// ---- extraction -------------------------------------------------------------------------------------------------------
+struct Lattice {
+    const float* tsdf;
+    const float* weight;
+    int nx, ny, nz;
+    long long cells;          // (nx - 1)(ny - 1)(nz - 1)
+    float ox, oy, oz, vl;
+};
+
+// cell p in C order: its lattice index, corner values and case; false for a cell that emits nothing
+__device__ __forceinline__ bool eval_cell(const Lattice& a, long long p, int c[3], float v[8], int& top) {
+    const long long cz = a.nz - 1, cy = a.ny - 1;
+    c[2] = (int)(p % cz);
+    c[1] = (int)((p / cz) % cy);
+    c[0] = (int)(p / (cz * cy));
+    int t = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const long long idx = ((long long)(c[0] + INC[q][0]) * a.ny + (c[1] + INC[q][1])) * a.nz + (c[2] + INC[q][2]);
+        if (a.weight[idx] == 0.f) return false;               // an unobserved corner voids the cell
+        v[q] = a.tsdf[idx];
+        t |= (v[q] < 0.f ? 1 : 0) << q;                       // exactly 0 counts as outside
+    }
+    top = t;
+    return t != 0 && t != 255;
+}
+
+__device__ __forceinline__ int tri_count(int top) {
+    int n = 0;
+    while (n < 5 && TRI[top][3 * n] >= 0) ++n;
+    return n;
+}
+
+__global__ __launch_bounds__(256) void vfn_tsdf_count_kernel(Lattice a, int* __restrict__ counts) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.cells) return;
+    int c[3], top = 0;
+    float v[8];
+    counts[p] = eval_cell(a, p, c, v, top) ? tri_count(top) : 0;
+}
+
+__global__ void vfn_tsdf_total_kernel(const int* __restrict__ incl, long long last, long long* __restrict__ info) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) info[0] = last >= 0 ? (long long)incl[last] : 0ll;
+}
+
+// the vertex of cut edge e of cell c: a function of the edge alone (its lower endpoint L, its axis, the two values)
+__device__ __forceinline__ void edge_vertex(const Lattice& a, const int c[3], const float v[8], int e, double out[3]) {
+    const int qa = EDGE_A[e], qb = EDGE_B[e];
+    int axis = 0;
+    if (INC[qa][1] != INC[qb][1]) axis = 1;
+    if (INC[qa][2] != INC[qb][2]) axis = 2;
+    const bool a_low = INC[qa][axis] < INC[qb][axis];
+    const int ql = a_low ? qa : qb, qu = a_low ? qb : qa;
+    const double vl = (double)a.vl;
+    const double o[3] = {(double)a.ox, (double)a.oy, (double)a.oz};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) out[d] = o[d] + ((double)(c[d] + INC[ql][d]) + 0.5) * vl;
+    const double fl = fabs((double)v[ql]), fu = fabs((double)v[qu]);
+    out[axis] = out[axis] + (fl / (fl + fu)) * vl;
+}
+
+__global__ __launch_bounds__(256) void vfn_tsdf_emit_kernel(Lattice a, const int* __restrict__ counts, const int* __restrict__ incl,
+                                                            double* __restrict__ tri_verts) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.cells) return;
+    const int n = counts[p];
+    if (n == 0) return;
+    int c[3], top = 0;
+    float v[8];
+    if (!eval_cell(a, p, c, v, top)) return;
+    const long long slot0 = (long long)(incl[p] - n) * 3;
+    for (int t = 0; t < n; ++t)
+        for (int k = 0; k < 3; ++k) {
+            double x[3];
+            edge_vertex(a, c, v, TRI[top][3 * t + k], x);
+            double* o = tri_verts + (slot0 + 3 * t + k) * 3;
+            o[0] = x[0]; o[1] = x[1]; o[2] = x[2];
+        }
+}
+
+inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
+
+int check_dims(int32_t nx, int32_t ny, int32_t nz, float vl, const char* what) {
+    VFN_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1 && (long long)nx * ny < (1ll << 31) && (long long)nx * ny * nz < (1ll << 31),
+                "%s: dims (%d, %d, %d) must be positive with fewer than 2^31 voxels", what, nx, ny, nz);
+    VFN_REQUIRE(vl > 0.f && vl - vl == 0.f, "%s: voxel_length must be positive and finite", what);
+    return VFN_OK;
+}
+
+int make_lattice(Lattice& a, const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz, float vl,
+                 const char* what) {
+    const int rc = check_dims(nx, ny, nz, vl, what);
+    if (rc != VFN_OK) return rc;
+    VFN_REQUIRE(tsdf && weight, "%s: NULL volume", what);
+    a = Lattice{tsdf, weight, nx, ny, nz, (long long)(nx - 1) * (ny - 1) * (nz - 1), ox, oy, oz, vl};
+    return VFN_OK;
+}
+
+}  // namespace
+
+extern "C" int vfn_tsdf_integrate(float* tsdf, float* weight, int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz,
+                                  float voxel_length, float sdf_trunc, const float* depth, int32_t height, int32_t width,
+                                  const float* intrinsics, const float* extrinsics, int32_t n_views, void* stream) {
+    const int rc = check_dims(nx, ny, nz, voxel_length, "vfn_tsdf_integrate");
+    if (rc != VFN_OK) return rc;
+    VFN_REQUIRE(tsdf && weight, "vfn_tsdf_integrate: NULL volume");
+    VFN_REQUIRE(sdf_trunc > 0.f && sdf_trunc - sdf_trunc == 0.f, "vfn_tsdf_integrate: sdf_trunc must be positive and finite");
+    VFN_REQUIRE(n_views >= 0 && height >= 1 && width >= 1 && (long long)height * width < (1ll << 31),
+                "vfn_tsdf_integrate: bad views (%d of %d x %d)", n_views, height, width);
+    if (n_views == 0) return VFN_OK;
+    VFN_REQUIRE(depth && intrinsics && extrinsics, "vfn_tsdf_integrate: NULL view argument");
+    const long long nbi = (nx + BI - 1) / BI, nbj = (ny + BJ - 1) / BJ, nbk = (nz + BK - 1) / BK;
+    const long long bricks = nbi * nbj * nbk;
+    VFN_REQUIRE(bricks < (1ll << 31), "vfn_tsdf_integrate: %lld bricks exceed one launch", bricks);
+    Volume vol{tsdf, weight, nx, ny, nz, ox, oy, oz, voxel_length, sdf_trunc};
+    Views vs{depth, intrinsics, extrinsics, n_views, height, width};
+    // 16-B accesses need rows of a multiple of four voxels and 16-B aligned arrays; anything else takes the scalar form
+    const bool vec = nz % RUN == 0 && ((uintptr_t)tsdf & 15) == 0 && ((uintptr_t)weight & 15) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (vec) hipLaunchKernelGGL(vfn_tsdf_integrate_kernel<true>, dim3((unsigned)bricks), dim3(THREADS), 0, s, vol, vs, (int)nbj, (int)nbk);
+    else hipLaunchKernelGGL(vfn_tsdf_integrate_kernel<false>, dim3((unsigned)bricks), dim3(THREADS), 0, s, vol, vs, (int)nbj, (int)nbk);
+    return vfn_check_launch("vfn_tsdf_integrate");
+}
+
+extern "C" int vfn_tsdf_count(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, int32_t* counts, int32_t* offsets,
+                              int64_t* info, void* scan_ws, int64_t scan_ws_bytes, void* stream) {
+    Lattice a;
+    const int rc = make_lattice(a, tsdf, weight, nx, ny, nz, 0.f, 0.f, 0.f, 1.f, "vfn_tsdf_count");
+    if (rc != VFN_OK) return rc;
+    VFN_REQUIRE(info && (a.cells == 0 || (counts && offsets)), "vfn_tsdf_count: NULL output");
+    hipStream_t s = (hipStream_t)stream;
+    if (a.cells > 0) {
+        hipLaunchKernelGGL(vfn_tsdf_count_kernel, dim3(blocks_for(a.cells)), dim3(256), 0, s, a, (int*)counts);
+        const int r2 = vfn_mc_inclusive_scan(counts, offsets, a.cells, scan_ws, scan_ws_bytes, s, "vfn_tsdf_count");
+        if (r2 != VFN_OK) return r2;
+    }
+    hipLaunchKernelGGL(vfn_tsdf_total_kernel, dim3(1), dim3(64), 0, s, (const int*)offsets, (long long)(a.cells - 1), (long long*)info);
+    return vfn_check_launch("vfn_tsdf_count");
+}
+
+extern "C" int vfn_tsdf_emit(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz,
+                             float voxel_length, const int32_t* counts, const int32_t* offsets, double* tri_verts, void* stream) {
+    Lattice a;
+    const int rc = make_lattice(a, tsdf, weight, nx, ny, nz, ox, oy, oz, voxel_length, "vfn_tsdf_emit");
+    if (rc != VFN_OK) return rc;
+    if (a.cells == 0) return VFN_OK;
+    VFN_REQUIRE(counts && offsets && tri_verts, "vfn_tsdf_emit: NULL argument");
+    hipLaunchKernelGGL(vfn_tsdf_emit_kernel, dim3(blocks_for(a.cells)), dim3(256), 0, (hipStream_t)stream, a, (const int*)counts,
+                       (const int*)offsets, tri_verts);
+    return vfn_check_launch("vfn_tsdf_emit");
+}

@@ -42,6 +42,7 @@ EXPORTS = (
     "vfn_mesh_field_norms",
     "vfn_nn_sqdist", "vfn_tri_areas", "vfn_cumsum_workspace_bytes", "vfn_cumsum_f64", "vfn_sample_surface",
     "vfn_reduce_stats_workspace_bytes", "vfn_reduce_stats",
+    "vfn_tsdf_integrate", "vfn_tsdf_count", "vfn_tsdf_emit",
 )
 
 
@@ -1427,6 +1428,70 @@ def reduce_sum_levels(n: int) -> int:
     level (ceil(P / 1024) - 1, P = ceil(n / 4096) partials) + 10 (1024 lanes)."""
     p = (n + REDUCE_TILE - 1) // REDUCE_TILE
     return 4 + 8 + ((p + REDUCE_TOP - 1) // REDUCE_TOP - 1) + 10
+
+
+# ------------------------------------------------------------------------------------------------
+# TSDF fusion (csrc/vfn_tsdf.hip; vf_nerf_amd/tsdf.py is the public surface)
+# ------------------------------------------------------------------------------------------------
+def _tsdf_volume_args(tsdf: torch.Tensor, weight: torch.Tensor):
+    if tsdf.dim() != 3 or weight.shape != tsdf.shape:
+        raise VfnError(f"tsdf / weight must be two [nx,ny,nz] tensors of one shape, got {tuple(tsdf.shape)} and {tuple(weight.shape)}")
+    if tsdf.numel() < 1 or tsdf.numel() >= (1 << 31):
+        raise VfnError(f"a volume of {tsdf.numel()} voxels is outside [1, 2^31)")
+    if weight.device != tsdf.device:
+        raise VfnError("tsdf and weight live on different devices")
+    nx, ny, nz = tsdf.shape
+    return (_ptr(tsdf, "tsdf"), _ptr(weight, "weight"), C.c_int32(nx), C.c_int32(ny), C.c_int32(nz))
+
+
+def tsdf_integrate(tsdf: torch.Tensor, weight: torch.Tensor, origin: Sequence[float], voxel_length: float, sdf_trunc: float,
+                   depth: torch.Tensor, intrinsics: torch.Tensor, extrinsics: torch.Tensor) -> None:
+    """All views of depth[V,H,W] (intrinsics[V,4] = fx fy cx cy, extrinsics[V,12] = world -> camera rows) into the volume, in place, in one
+    pass over it; origin / voxel_length / sdf_trunc are taken as float32.  See include/vfn.h for the arithmetic."""
+    vol = _tsdf_volume_args(tsdf, weight)
+    if depth.dim() != 3:
+        raise VfnError(f"depth must be [V,H,W], got {tuple(depth.shape)}")
+    v, h, w = depth.shape
+    if tuple(intrinsics.shape) != (v, 4) or tuple(extrinsics.shape) != (v, 12):
+        raise VfnError(f"{v} views need intrinsics [{v},4] and extrinsics [{v},12], got {tuple(intrinsics.shape)} and {tuple(extrinsics.shape)}")
+    if h < 1 or w < 1 or h * w >= (1 << 31) or v >= (1 << 31):
+        raise VfnError(f"{v} depth maps of {h} x {w} are outside the limits of one call")
+    for t in (depth, intrinsics, extrinsics):
+        if t.device != tsdf.device:
+            raise VfnError("the views and the volume live on different devices")
+    with torch.cuda.device(tsdf.device):
+        _check(load().vfn_tsdf_integrate(*vol, *(C.c_float(float(o)) for o in origin), C.c_float(float(voxel_length)), C.c_float(float(sdf_trunc)),
+                                         _ptr(depth, "depth"), C.c_int32(h), C.c_int32(w), _ptr(intrinsics, "intrinsics"),
+                                         _ptr(extrinsics, "extrinsics"), C.c_int32(v), _stream()), "vfn_tsdf_integrate")
+
+
+def tsdf_extract(tsdf: torch.Tensor, weight: torch.Tensor, origin: Sequence[float], voxel_length: float):
+    """The zero level set of the volume: count -> emit (csrc/vfn_tsdf.hip) -> dedup -> number (the mesh unit's) on the current stream
+    -> (vertices[n,3] float64, faces[m,3] int64, 0-based).  The triangle and the vertex count cross to the host to size the outputs."""
+    vol = _tsdf_volume_args(tsdf, weight)
+    dev = tsdf.device
+    nx, ny, nz = tsdf.shape
+    cells = (nx - 1) * (ny - 1) * (nz - 1)
+    box = tuple(C.c_float(float(o)) for o in origin) + (C.c_float(float(voxel_length)),)
+    with torch.cuda.device(dev):
+        info = torch.zeros(4, dtype=torch.int64, device=dev)
+        counts = torch.empty(max(cells, 1), dtype=torch.int32, device=dev)
+        offsets = torch.empty_like(counts)
+        ws = _scan_ws(cells, dev)
+        _check(load().vfn_tsdf_count(*vol, _ptr(counts, "counts", torch.int32), _ptr(offsets, "offsets", torch.int32),
+                                     _ptr(info, "info", torch.int64), _ptr(ws, "scan_ws", torch.uint8), C.c_int64(ws.numel()), _stream()),
+               "vfn_tsdf_count")
+        n_tri = int(info[0].cpu())
+        n_slots = 3 * n_tri
+        if n_tri < 0 or n_slots >= (1 << 31):
+            raise VfnError(f"TSDF extraction: {n_tri} triangles exceed the 2^31 / 3 limit")
+        if n_tri == 0:
+            return torch.empty(0, 3, dtype=torch.float64, device=dev), torch.empty(0, 3, dtype=torch.int64, device=dev)
+        tri_verts = torch.empty(n_slots, 3, dtype=torch.float64, device=dev)
+        _check(load().vfn_tsdf_emit(*vol, *box, _ptr(counts, "counts", torch.int32), _ptr(offsets, "offsets", torch.int32),
+                                    _ptr(tri_verts, "tri_verts", torch.float64), _stream()), "vfn_tsdf_emit")
+        vertices, ids = mesh_dedup(tri_verts, info=info)
+    return vertices, ids.view(n_tri, 3)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,0 +1,310 @@
+"""Fusing depth maps into a mesh on the device (csrc/vfn_tsdf.hip): the stage of evaluation/methods.py:613-665 (``tsdf_mesh``) between
+``render-images`` and ``3d-metrics`` — the mesh that ``metrics_3d`` scores for a trained VF-NeRF — without leaving the device.
+
+* ``TSDFVolume`` — a dense truncated-signed-distance volume: ``integrate`` fuses one depth map or a stack of them in ONE pass over the
+  volume, ``extract_mesh`` triangulates the zero level set with classic marching cubes.
+* ``reference_depth`` — a depth map as ``tsdf_mesh`` hands it to the fusion: millimetres as uint16, truncated at ``depth_trunc``.
+* ``fuse_depth_maps`` — depth maps + cameras -> mesh; the box defaults to the back-projected valid depth points, padded by ``sdf_trunc``.
+* ``fuse_rendered_views`` — a model's views rendered (``VectorFieldNerf.render_chunked``, as ``evaluator.render_view``), their depth
+  maps kept on the device and fused; only the mesh leaves it.
+
+The semantics are modelled on a uniform TSDF volume's integration and extraction as ``tsdf_mesh`` drives one (voxel length 4/512,
+``sdf_trunc`` 0.04, extrinsic = inv(pose)); include/vfn.h states the arithmetic operation for operation and tests/tsdf_restatement.py
+restates it in NumPy, which the device equals bit for bit.  Two deliberate differences from the reference's fusion:
+
+* the volume is DENSE over a box the caller gives, not hashed 16^3 blocks opened near back-projected points.  A voxel in free space in
+  front of a surface therefore collects ``tsdf = 1`` observations here in cases where the hashed volume would never have allocated it;
+  the zero crossing lies inside the truncation band either way;
+* no colour is fused.
+
+A mesh is ``(vertices float64 [n,3], faces int64 [m,3])``, 0-based, on the device — the form ``mesh.triangulate`` returns and
+``metrics3d.score_mesh`` accepts.  No CPU fallback: ``lib.VfnError`` when no device is visible.
+
+Out of scope: ``refuse()`` (its fusion half is this volume; it needs a mesh rasteriser for the depth maps), Laplacian smoothing
+(``tsdf-smoothed.ply``), PLY reading / writing.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import lib
+
+LIMIT = 1 << 31
+VOXEL_LENGTH = 4.0 / 512.0        # evaluation/methods.py:624
+SDF_TRUNC = 0.04                  # :625
+DEPTH_SCALE, DEPTH_TRUNC = 1000.0, 10.0
+
+
+def _device(device=None) -> torch.device:
+    if device is not None:
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise lib.VfnError(f"TSDF fusion runs on the device (no CPU fallback), got device {dev}")
+        return dev
+    if not torch.cuda.is_available():
+        raise lib.VfnError("TSDF fusion runs on the device (no CPU fallback) and no GPU is visible")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _as_tensor(x, name: str) -> torch.Tensor:
+    if isinstance(x, torch.Tensor):
+        return x.detach()
+    if isinstance(x, np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(x))
+    raise TypeError(f"{name}: expected a numpy array or a torch tensor, got {type(x).__name__}")
+
+
+def _positive(x, name: str) -> float:
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not math.isfinite(float(x)) or float(x) <= 0:
+        raise ValueError(f"{name} must be a positive finite number, got {x!r}")
+    f = float(np.float32(x))
+    if not (f > 0 and math.isfinite(f)):
+        raise ValueError(f"{name} = {x!r} is not a positive float32")
+    return f
+
+
+def _check_dims(dims) -> Tuple[int, int, int]:
+    d = tuple(dims)
+    if len(d) != 3 or any(isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 1 for n in d):
+        raise ValueError(f"dims must be three positive integers, got {dims!r}")
+    d = tuple(int(n) for n in d)
+    if d[0] * d[1] * d[2] >= LIMIT:
+        raise ValueError(f"a volume of {d[0]} x {d[1]} x {d[2]} voxels exceeds the 2^31 limit")
+    return d
+
+
+def _check_depth_values(d: torch.Tensor, name: str) -> None:
+    """One reduction on whatever device the map lives on: non-finite or negative depths are refused."""
+    if d.numel() and not bool((torch.isfinite(d) & (d >= 0)).all()):
+        raise ValueError(f"{name} holds non-finite or negative values")
+
+
+def split_intrinsics(intrinsics, n_views: int) -> torch.Tensor:
+    """[3,3] / [4,4] shared or [V,3,3] / [V,4,4] per view -> float32 [V,4] = fx fy cx cy (host).  Skew is refused: the projection of
+    include/vfn.h has none."""
+    k = _as_tensor(intrinsics, "intrinsics").cpu()
+    if k.dim() == 2:
+        k = k.unsqueeze(0).expand(n_views, -1, -1)
+    if k.dim() != 3 or k.shape[0] != n_views or tuple(k.shape[1:]) not in ((3, 3), (4, 4)):
+        raise ValueError(f"intrinsics must be [3,3], [4,4] or one of those per view ({n_views}), got {tuple(_as_tensor(intrinsics, 'intrinsics').shape)}")
+    k = k.to(torch.float32)
+    out = torch.stack([k[:, 0, 0], k[:, 1, 1], k[:, 0, 2], k[:, 1, 2]], dim=1).contiguous()
+    if not bool(torch.isfinite(out).all()) or not bool((out[:, :2] > 0).all()):
+        raise ValueError("intrinsics need finite values and positive focal lengths")
+    if bool((k[:, 0, 1] != 0).any()):
+        raise ValueError("intrinsics with skew are not supported")
+    return out
+
+
+def extrinsics_from_poses(poses, n_views: int) -> torch.Tensor:
+    """Camera-to-world poses [4,4] / [V,4,4] -> float32 [V,12]: the first three rows of float32(inv(float64 pose)) (host)."""
+    p = _as_tensor(poses, "pose").cpu()
+    if p.dim() == 2:
+        p = p.unsqueeze(0)
+    if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4) or p.shape[0] != n_views:
+        raise ValueError(f"poses must be [4,4] per view ({n_views}), got {tuple(_as_tensor(poses, 'pose').shape)}")
+    p64 = p.to(torch.float64).numpy()
+    if not np.isfinite(p64).all():
+        raise ValueError("a pose holds non-finite values")
+    out = np.empty((n_views, 12), dtype=np.float32)
+    for i in range(n_views):
+        try:
+            inv = np.linalg.inv(p64[i])
+        except np.linalg.LinAlgError:
+            raise ValueError(f"pose {i} is singular") from None
+        e = inv.astype(np.float32)
+        if not np.isfinite(e).all() or np.linalg.matrix_rank(p64[i]) < 4:
+            raise ValueError(f"pose {i} is singular")
+        out[i] = e[:3].reshape(12)
+    return torch.from_numpy(out)
+
+
+def _stack_depths(depth, name: str = "depth") -> torch.Tensor:
+    d = _as_tensor(depth, name)
+    if d.dim() == 2:
+        d = d.unsqueeze(0)
+    if d.dim() == 4 and d.shape[-1] == 1:
+        d = d[..., 0]
+    if d.dim() != 3 or d.shape[1] < 1 or d.shape[2] < 1:
+        raise ValueError(f"{name} must be [H,W] or [V,H,W], got {tuple(_as_tensor(depth, name).shape)}")
+    if not d.dtype.is_floating_point:
+        raise ValueError(f"{name} must be floating point (metres), got {d.dtype}")
+    if d.shape[1] * d.shape[2] >= LIMIT:
+        raise ValueError(f"{name}: a map of {d.shape[1]} x {d.shape[2]} pixels exceeds the 2^31 limit")
+    return d
+
+
+def reference_depth(depth_map, depth_scale: float = DEPTH_SCALE, depth_trunc: float = DEPTH_TRUNC) -> torch.Tensor:
+    """A depth map in metres as ``tsdf_mesh`` feeds it to the fusion (evaluation/methods.py:651-657): q = trunc(float64(depth) depth_scale) as
+    uint16, d = float32(q) / float32(depth_scale), d = 0 where d >= depth_trunc.  Non-finite, negative or >= 65.536 m (at the default
+    scale: anything whose q leaves uint16) inputs are refused — NumPy's out-of-range cast is undefined and not inherited.  Stays on
+    the input's device."""
+    d = _as_tensor(depth_map, "depth_map")
+    if not d.dtype.is_floating_point:
+        raise ValueError(f"depth_map must be floating point (metres), got {d.dtype}")
+    _check_depth_values(d, "depth_map")
+    q = torch.trunc(d.to(torch.float64) * float(depth_scale))      # (the reference multiplies the float64 array it loads from depth-i.npy)
+    if d.numel() and bool((q > 65535).any()):
+        raise ValueError(f"depth_map holds values of {65536 / depth_scale} m or more: their millimetres leave uint16")
+    out = q.to(torch.float32) / torch.tensor(depth_scale, dtype=torch.float32, device=d.device)
+    return torch.where(out >= depth_trunc, torch.zeros_like(out), out)
+
+
+class TSDFVolume:
+    """A dense TSDF volume of ``dims = (nx, ny, nz)`` voxels of ``voxel_length`` whose first voxel's corner is ``origin``: voxel (i, j, k)
+    has its centre at origin + (index + 0.5) voxel_length.  ``tsdf`` / ``weight`` are float32 [nx,ny,nz] device tensors, zero until a
+    view has been integrated."""
+
+    def __init__(self, origin, dims, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC, device=None):
+        self.dims = _check_dims(dims)
+        self.voxel_length = _positive(voxel_length, "voxel_length")
+        self.sdf_trunc = _positive(sdf_trunc, "sdf_trunc")
+        o = np.asarray(origin.detach().cpu() if isinstance(origin, torch.Tensor) else origin, dtype=np.float64).reshape(-1)
+        if o.shape != (3,) or not np.isfinite(o.astype(np.float32)).all():
+            raise ValueError(f"origin must be three finite numbers, got {origin!r}")
+        self.origin = tuple(float(x) for x in o.astype(np.float32))
+        self.device = _device(device)
+        self.tsdf = torch.zeros(self.dims, dtype=torch.float32, device=self.device)
+        self.weight = torch.zeros(self.dims, dtype=torch.float32, device=self.device)
+
+    def reset(self) -> None:
+        self.tsdf.zero_()
+        self.weight.zero_()
+
+    def integrate(self, depth, intrinsics, pose) -> None:
+        """One depth map [H,W] or a stack [V,H,W] (float metres, 0 = no measurement; host or device tensors or NumPy) with intrinsics
+        [3,3] / [4,4] shared or per view and camera-to-world poses [4,4] / [V,4,4].  The V views are fused in index order by ONE kernel
+        that reads and writes the volume once: the bits of V single-view calls."""
+        d = _stack_depths(depth)
+        v = d.shape[0]
+        k = split_intrinsics(intrinsics, v)
+        e = extrinsics_from_poses(pose, v)
+        _check_depth_values(d, "depth")
+        d = d.to(self.device, torch.float32).contiguous()
+        lib.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel_length, self.sdf_trunc, d, k.to(self.device), e.to(self.device))
+
+    def extract_mesh(self):
+        """-> (vertices float64 [n,3], faces int64 [m,3], 0-based) on the device; two empty tensors when nothing crosses zero."""
+        return lib.tsdf_extract(self.tsdf, self.weight, self.origin, self.voxel_length)
+
+
+def depth_bounds(depths: torch.Tensor, k: torch.Tensor, poses: torch.Tensor) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+    """min / max (float64 [3] each, host) of the valid depth points of depths[V,H,W] back-projected through fx fy cx cy and the
+    camera-to-world poses — torch on the depth maps' device; None when no pixel is valid."""
+    dev = depths.device
+    v, h, w = depths.shape
+    k = k.to(dev, torch.float64)
+    p = poses.to(dev, torch.float64)
+    lo = torch.full((3,), float("inf"), dtype=torch.float64, device=dev)
+    hi = -lo
+    uu = torch.arange(w, dtype=torch.float64, device=dev)[None, :]
+    vv = torch.arange(h, dtype=torch.float64, device=dev)[:, None]
+    for i in range(v):
+        d = depths[i].to(torch.float64)
+        valid = d > 0
+        if not bool(valid.any()):
+            continue
+        cam = torch.stack([(uu - k[i, 2]) / k[i, 0] * d, (vv - k[i, 3]) / k[i, 1] * d, d], dim=-1)[valid]      # [n,3]
+        world = cam @ p[i, :3, :3].T + p[i, :3, 3]
+        lo, hi = torch.minimum(lo, world.min(dim=0).values), torch.maximum(hi, world.max(dim=0).values)
+    if not bool(torch.isfinite(lo).all()):
+        return None
+    return lo.cpu(), hi.cpu()
+
+
+def _box(bounds, vl: float):
+    """(min[3], max[3]) -> (origin float64 [3], dims): ceil(extent / voxel_length) voxels per axis, at least one."""
+    if len(bounds) != 2:
+        raise ValueError("bounds must be (min[3], max[3])")
+    lo, hi = (np.asarray(b.detach().cpu() if isinstance(b, torch.Tensor) else b, dtype=np.float64).reshape(-1) for b in bounds)
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all()) or not (hi > lo).all():
+        raise ValueError(f"bounds must be two finite [3] corners with max > min, got {bounds!r}")
+    extent = (hi - lo) / vl
+    if not (extent < LIMIT).all():
+        raise ValueError(f"a box of {extent} voxels exceeds the 2^31 limit")
+    return lo, _check_dims(tuple(max(1, int(math.ceil(float(x)))) for x in extent))
+
+
+def fuse_depth_maps(depths, intrinsics, poses, bounds=None, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC, device=None):
+    """Depth maps [V,H,W] (or one [H,W]) with their cameras -> (vertices, faces): one volume, one integration pass, one extraction.
+    ``bounds`` = (min[3], max[3]) of the box; None: the min / max of the back-projected valid depth points, padded by ``sdf_trunc``.
+    The box is covered by ceil(extent / voxel_length) voxels per axis (at least one)."""
+    vl, tr = _positive(voxel_length, "voxel_length"), _positive(sdf_trunc, "sdf_trunc")
+    d = _stack_depths(depths, "depths")
+    v = d.shape[0]
+    k = split_intrinsics(intrinsics, v)
+    e = extrinsics_from_poses(poses, v)
+    _check_depth_values(d, "depths")                           # (on whatever device the maps live)
+    box = None if bounds is None else _box(bounds, vl)         # every refusal that needs no device comes before the device is asked for
+    dev = _device(device if device is not None else (d.device if d.is_cuda else None))
+    d = d.to(dev, torch.float32).contiguous()
+    if box is None:
+        p = _as_tensor(poses, "poses").cpu()
+        found = depth_bounds(d, k, p.unsqueeze(0) if p.dim() == 2 else p)
+        if found is None:
+            return torch.empty(0, 3, dtype=torch.float64, device=dev), torch.empty(0, 3, dtype=torch.int64, device=dev)
+        box = _box((found[0].numpy() - tr, found[1].numpy() + tr), vl)
+    vol = TSDFVolume(box[0], box[1], voxel_length=vl, sdf_trunc=tr, device=dev)
+    lib.tsdf_integrate(vol.tsdf, vol.weight, vol.origin, vol.voxel_length, vol.sdf_trunc, d, k.to(dev), e.to(dev))
+    return vol.extract_mesh()
+
+
+@torch.no_grad()
+def render_depth_maps(model, poses, intrinsics, height: int, width: int, epoch: int, split_size: int = 512, white: bool = False,
+                      n_streams: int = 2, min_chunk: Optional[int] = None) -> torch.Tensor:
+    """Every pixel of every view rendered as ``evaluator.render_view`` renders it (``VectorFieldNerf.render_chunked`` with sparse
+    colours, chunks of max(split_size, min_chunk) rays) -> depth maps [V,height,width] float32 that stay on the device."""
+    from . import evaluator
+    p = _as_tensor(poses, "poses").to(torch.float32)
+    p = p.unsqueeze(0) if p.dim() == 2 else p
+    if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4):
+        raise ValueError(f"poses must be [V,4,4], got {tuple(p.shape)}")
+    v = p.shape[0]
+    k = _as_tensor(intrinsics, "intrinsics").to(torch.float32)
+    if k.dim() == 2:
+        k = k.unsqueeze(0).expand(v, -1, -1)
+    if k.dim() != 3 or k.shape[0] != v or tuple(k.shape[1:]) not in ((3, 3), (4, 4)):
+        raise ValueError(f"intrinsics must be [3,3], [4,4] or one of those per view ({v}), got {tuple(k.shape)}")
+    if k.shape[1] == 3:
+        k4 = torch.eye(4).repeat(v, 1, 1)
+        k4[:, :3, :3] = k.cpu()
+        k = k4
+    if height < 1 or width < 1:
+        raise ValueError(f"bad image size {height} x {width}")
+    dev = _device(getattr(model.config.cuda_config, "device", None))
+    vv, uu = torch.meshgrid(torch.arange(height, dtype=torch.float32), torch.arange(width, dtype=torch.float32), indexing="ij")
+    uv = torch.stack([uu.reshape(-1), vv.reshape(-1)], dim=1).to(dev)
+    chunk = max(int(split_size), int(evaluator.MIN_CHUNK if min_chunk is None else min_chunk))
+    out = torch.empty(v, height, width, dtype=torch.float32, device=dev)
+    keep = getattr(model, "sparse_colours", False)
+    model.sparse_colours = bool(evaluator.SPARSE_COLOURS) or keep
+    try:
+        for i in range(v):
+            _, depth = model.render_chunked(p[i].to(dev), uv, k[i].to(dev), epoch, chunk=chunk, n_streams=n_streams, white=white)
+            out[i] = depth.reshape(height, width)
+    finally:
+        model.sparse_colours = keep
+    return out
+
+
+@torch.no_grad()
+def fuse_rendered_views(model, poses, intrinsics, height: int, width: int, epoch: int, bounds=None, voxel_length: float = VOXEL_LENGTH,
+                        sdf_trunc: float = SDF_TRUNC, as_reference: bool = True, depth_scale: float = DEPTH_SCALE,
+                        depth_trunc: float = DEPTH_TRUNC, split_size: int = 512, white: bool = False, n_streams: int = 2,
+                        min_chunk: Optional[int] = None):
+    """render-images -> tsdf-mesh in one call: the model's views (camera-to-world ``poses`` [V,4,4], ``intrinsics`` shared or per view)
+    rendered at ``height`` x ``width``, their depth maps — as ``tsdf_mesh`` stores them when ``as_reference`` (``reference_depth``) —
+    fused into a volume over ``bounds`` and triangulated.  The depth maps never leave the device; -> (vertices, faces).
+
+    A rendered depth below zero (compositing can leave one on a ray without a surface) is no measurement and becomes 0 — where the
+    reference's unchecked uint16 cast in practice wraps it past ``depth_trunc``, which zeroes it too.  Non-finite depths are refused."""
+    depths = render_depth_maps(model, poses, intrinsics, height, width, epoch, split_size=split_size, white=white, n_streams=n_streams,
+                               min_chunk=min_chunk)
+    depths = torch.where(depths < 0, torch.zeros_like(depths), depths)
+    if as_reference:
+        depths = reference_depth(depths, depth_scale=depth_scale, depth_trunc=depth_trunc)
+    return fuse_depth_maps(depths, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depths.device)
