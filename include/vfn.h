@@ -808,6 +808,52 @@ int vfn_tsdf_emit(const float* tsdf, const float* weight, int32_t nx, int32_t ny
                   float voxel_length, const int32_t* counts, const int32_t* offsets, double* tri_verts, void* stream);
 
 /* =============================================================================================
+ * Rasterising a mesh's depth, and Laplacian smoothing (csrc/vfn_raster.hip): what evaluation/methods.py:33-72 (refuse: the mesh's depth
+ * from every dataset view by an OpenGL renderer, faces not culled, re-fused with depth_scale 1 / depth_trunc 5) and :686-691
+ * (filter_smooth_laplacian, 10 iterations) need on top of the TSDF volume.  Neither renderer nor filter is reproduced bit for bit (no
+ * fixed arithmetic is published for either): this is a SPECIFICATION, restated in tests/raster_restatement.py.
+ *   vfn_raster_depth  vertices[n, 3] (double, world), faces[m, 3] (int64, 0-based), intrinsics[V, 4] = fx fy cx cy, extrinsics[V, 12] =
+ *                     the world -> camera rows e00 .. e23 (float32; the camera looks along +z, x right, y down), near, far,
+ *                     pixel_centre c (float32).  Writes depth[V, H, W] (float32): the z-depth of the nearest surface, 0 where there
+ *                     is none.  All arithmetic float64 with the float32 inputs promoted, every operation rounded once in the
+ *                     association written, no contraction, correctly rounded /.  Per view and face (q = 0, 1, 2 its vertices):
+ *                       P_q.x = ((e00 X + e01 Y) + e02 Z) + e03                                  (y, z alike)
+ *                       skip the face if all three P_q.z < near, or all three P_q.z > far
+ *                       n0 = P1 x P2,  n1 = P2 x P0,  n2 = P0 x P1          (a x b).x = a.y b.z - a.z b.y, cyclic
+ *                       D = (P0.x n0.x + P0.y n0.y) + P0.z n0.z;  skip the face if D == 0 or D is not finite
+ *                       candidate pixels — all three P_q.z >= near:  px_q = (P_q.x fx) / P_q.z + cx,  py_q alike;
+ *                           u from max(0, ceil(min px - c) - 1) to min(W - 1, floor(max px - c) + 1), v alike (an empty range
+ *                           skips the face); otherwise (the face straddles the near plane): every pixel of the view
+ *                       per candidate pixel (u, v):
+ *                         dx = (((double)u + c) - cx) / fx;  dy = (((double)v + c) - cy) / fy
+ *                         e_i = (n_i.x dx + n_i.y dy) + n_i.z        i = 0, 1, 2 — evaluated directly, never incrementally
+ *                         s = (e0 + e1) + e2
+ *                         covered iff s != 0 and, with sigma = sign(D), sigma e_i >= 0 for all three i (edges inclusive, no culling)
+ *                         z = D / s;  kept iff near <= z <= far;  candidate value (float)z
+ *                       depth[v, u] = the minimum candidate value over all faces, 0 if there is none
+ *                     (ray / triangle intersection as homogeneous edge functions: for the ray (dx, dy, 1), z is the z-depth.  A face
+ *                     through the camera plane needs no clipping; the two faces of an edge get exactly negated n_i, so a closed
+ *                     surface has no holes without a fill rule; the minimum commutes, so no bit depends on face order or schedule.)
+ *                     depth is filled and finished inside the call.  info[4] (int64, zero-filled by the caller, only added to / OR-ed
+ *                     into): info[0] bit 1 = a non-finite vertex coordinate, bit 2 = a face index outside [0, n) — such a face is
+ *                     not drawn and nothing is read through its indices; with either bit set depth is meaningless.  info[1] =
+ *                     fragments (kept candidates), info[2] = atomics sent, info[3] = (face, view) pairs walked by a whole wave.
+ *                     Limits: 0 < near < far finite, c finite, H, W >= 1, V H W < 2^31, n, m < 2^31.  Every argument check answers
+ *                     before any launch.
+ *   vfn_smooth_laplacian_step  one Jacobi step src[n, 3] -> dst[n, 3] (double, two different arrays) over a CSR adjacency:
+ *                     row_start[n + 1], neighbours[row_start[n]] (int64), a vertex's neighbours in ascending order, each once:
+ *                       s = v[nb_0];  s = s + v[nb_1];  ...                  per component, in the row's order
+ *                       new = v + lam (s / (double)count - v)
+ *                     a vertex without neighbours is copied.  info[0] bit 2 = a row or a neighbour outside its range (that vertex is
+ *                     copied).  float64 without contraction, no atomics.
+ * ============================================================================================= */
+int vfn_raster_depth(const double* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces, const float* intrinsics,
+                     const float* extrinsics, int32_t n_views, int32_t height, int32_t width, float near, float far, float pixel_centre,
+                     float* depth, int64_t* info, void* stream);
+int vfn_smooth_laplacian_step(const double* src, double* dst, int64_t n_vertices, const int64_t* row_start, const int64_t* neighbours,
+                              int64_t n_neighbours, double lam, int64_t* info, void* stream);
+
+/* =============================================================================================
  * Optimizer side of a training step over ONE flat fp32 buffer (train/vector_field_nerf_train.py:254-260:
  * torch.nn.utils.clip_grad_norm_(model.parameters(), clip); optimizer.step()).  The unique parameters — and their gradients
  * and Adam moments — are laid out contiguously, sorted into up to four REGIONS [start, end) of equal multiplicity `mult` =

@@ -43,6 +43,7 @@ EXPORTS = (
     "vfn_nn_sqdist", "vfn_tri_areas", "vfn_cumsum_workspace_bytes", "vfn_cumsum_f64", "vfn_sample_surface",
     "vfn_reduce_stats_workspace_bytes", "vfn_reduce_stats",
     "vfn_tsdf_integrate", "vfn_tsdf_count", "vfn_tsdf_emit",
+    "vfn_raster_depth", "vfn_smooth_laplacian_step",
 )
 
 
@@ -1492,6 +1493,76 @@ def tsdf_extract(tsdf: torch.Tensor, weight: torch.Tensor, origin: Sequence[floa
                                     _ptr(tri_verts, "tri_verts", torch.float64), _stream()), "vfn_tsdf_emit")
         vertices, ids = mesh_dedup(tri_verts, info=info)
     return vertices, ids.view(n_tri, 3)
+
+
+# ------------------------------------------------------------------------------------------------
+# depth rasteriser and Laplacian smoothing (csrc/vfn_raster.hip; vf_nerf_amd/raster.py and refuse.py are the public surface)
+# ------------------------------------------------------------------------------------------------
+RASTER_STATUS_NONFINITE, RASTER_STATUS_INDEX = 1, 2
+
+
+def raster_depth(vertices: torch.Tensor, faces: torch.Tensor, intrinsics: torch.Tensor, extrinsics: torch.Tensor, height: int, width: int,
+                 near: float, far: float, pixel_centre: float):
+    """vertices[n,3] float64, faces[m,3] int64, intrinsics[V,4] = fx fy cx cy, extrinsics[V,12] (float32) -> (depth[V,H,W] float32,
+    counters) with counters = {"fragments", "atomics", "cooperative"} — see include/vfn.h for the arithmetic.  A face index outside
+    [0, n) or a non-finite vertex raises (one status read), never faults."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise VfnError(f"vertices must be [n,3] and faces [m,3], got {tuple(vertices.shape)} and {tuple(faces.shape)}")
+    v = intrinsics.shape[0]
+    if tuple(intrinsics.shape) != (v, 4) or tuple(extrinsics.shape) != (v, 12):
+        raise VfnError(f"{v} views need intrinsics [{v},4] and extrinsics [{v},12], got {tuple(intrinsics.shape)} and {tuple(extrinsics.shape)}")
+    h, w = int(height), int(width)
+    if h < 1 or w < 1 or v * h * w >= (1 << 31):
+        raise VfnError(f"{v} depth maps of {h} x {w} are outside the limits of one call")
+    dev = intrinsics.device
+    if not intrinsics.is_cuda:
+        raise VfnError(f"intrinsics: expected a CUDA/HIP tensor, got {dev} (the HIP path has no CPU fallback)")
+    for t in (vertices, faces, extrinsics):
+        if t.device != dev:
+            raise VfnError("the mesh and the views live on different devices")
+    nv, nf = vertices.shape[0], faces.shape[0]
+    with torch.cuda.device(dev):
+        depth = torch.empty(v, h, w, dtype=torch.float32, device=dev)
+        info = torch.zeros(4, dtype=torch.int64, device=dev)
+        _check(load().vfn_raster_depth(_ptr(vertices, "vertices", torch.float64) if nv else None, C.c_int64(nv),
+                                       _ptr(faces, "faces", torch.int64) if nf else None, C.c_int64(nf), _ptr(intrinsics, "intrinsics"),
+                                       _ptr(extrinsics, "extrinsics"), C.c_int32(v), C.c_int32(h), C.c_int32(w), C.c_float(float(near)),
+                                       C.c_float(float(far)), C.c_float(float(pixel_centre)), _ptr(depth, "depth"),
+                                       _ptr(info, "info", torch.int64), _stream()), "vfn_raster_depth")
+        status, fragments, atomics, cooperative = (int(x) for x in info.cpu()) if v else (0, 0, 0, 0)
+    if status & RASTER_STATUS_INDEX:
+        raise VfnError(f"depth rasteriser: a face index lies outside [0, {nv})")
+    if status & RASTER_STATUS_NONFINITE:
+        raise VfnError("depth rasteriser: a non-finite vertex coordinate")
+    return depth, {"fragments": fragments, "atomics": atomics, "cooperative": cooperative}
+
+
+def smooth_laplacian(vertices: torch.Tensor, row_start: torch.Tensor, neighbours: torch.Tensor, iterations: int, lam: float) -> torch.Tensor:
+    """``iterations`` Jacobi steps of vfn_smooth_laplacian_step over the CSR (row_start[n+1], neighbours, int64) between two buffers ->
+    a new vertices[n,3] float64 tensor."""
+    n = vertices.shape[0]
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or row_start.shape != (n + 1,):
+        raise VfnError(f"vertices must be [n,3] with row_start [n+1], got {tuple(vertices.shape)} and {tuple(row_start.shape)}")
+    if not vertices.is_cuda:
+        raise VfnError(f"vertices: expected a CUDA/HIP tensor, got {vertices.device} (the HIP path has no CPU fallback)")
+    a = vertices.clone()
+    if n == 0 or iterations == 0:
+        return a
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        b = torch.empty_like(a)
+        info = torch.zeros(1, dtype=torch.int64, device=dev)
+        nnz = neighbours.shape[0]
+        for _ in range(iterations):
+            _check(load().vfn_smooth_laplacian_step(_ptr(a, "src", torch.float64), _ptr(b, "dst", torch.float64), C.c_int64(n),
+                                                    _ptr(row_start, "row_start", torch.int64),
+                                                    _ptr(neighbours, "neighbours", torch.int64) if nnz else None, C.c_int64(nnz),
+                                                    C.c_double(float(lam)), _ptr(info, "info", torch.int64), _stream()),
+                   "vfn_smooth_laplacian_step")
+            a, b = b, a
+        if int(info.cpu()) != 0:
+            raise VfnError("Laplacian smoothing: the adjacency names a vertex or a row outside its range")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------

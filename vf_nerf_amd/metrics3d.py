@@ -13,9 +13,10 @@ Inputs are numpy arrays or torch tensors on any device; a mesh is a ``mesh.Mesh`
 ``(vertices, faces)`` pair.  No CPU fallback: ``lib.VfnError`` when no device is visible.
 
 The mesh that ``metrics_3d`` scores for a VF-NeRF run, ``tsdf_mesh``'s, comes from ``vf_nerf_amd.tsdf`` (``fuse_depth_maps`` /
-``fuse_rendered_views``) in the form ``score_mesh`` accepts.
+``fuse_rendered_views``) in the form ``score_mesh`` accepts; the other three meshes it scores (smoothed, refused, both) and its whole
+dictionary come from ``vf_nerf_amd.refuse`` (``reconstruction_meshes``, ``metrics_3d``).
 
-Out of scope: ``refuse()`` (TSDF fusion of depth maps rasterised from a mesh by an OpenGL renderer), ICP alignment, the voxel down-sampling of
+Out of scope: ICP alignment, the voxel down-sampling of
 the ``evaluate_3d_reconstruction`` package, trimesh's vertex merging, and PLY reading / writing.  The random numbers are torch's, not
 numpy's: a sampled point set is distributed as trimesh's, it is not the same set.
 """

@@ -1,0 +1,103 @@
+"""The tail of the reference's ``metrics_3d`` (evaluation/methods.py:667-744) on the device: the four meshes it scores — ``tsdf``,
+``tsdf-smoothed``, ``refused-tsdf``, ``refused-tsdf-smoothed`` — from the one ``vf_nerf_amd.tsdf`` produces, and their scores.
+
+* ``refuse`` — methods.py:33-72: the mesh's depth from every view (``raster.rasterize_depth`` in place of the OpenGL renderer), depths
+  at or beyond ``depth_trunc`` dropped (depth_scale 1, no uint16 step: methods.py:61-62), the maps re-fused by
+  ``tsdf.fuse_depth_maps`` (voxel length 4/512, ``sdf_trunc`` 0.04).  Whatever no camera sees disappears.
+* ``smooth_laplacian`` — methods.py:690 (``filter_smooth_laplacian(number_of_iterations=10)``): uniform-weight Laplacian smoothing,
+  Jacobi steps ``v + lam (mean of the neighbours - v)`` over the edge-neighbours of every vertex.  ``iterations = 10`` and
+  ``lam = 0.5`` are Open3D's filter as remembered, not verified; Open3D's neighbour sets have no fixed summation order, so ours
+  (ascending neighbour index, include/vfn.h) is a specification.
+* ``reconstruction_meshes`` — the four meshes; ``metrics_3d`` — the dictionary of methods.py:732-741, every entry a
+  ``metrics3d.score_mesh``.
+
+Everything stays on the device between the stages; a mesh is ``(vertices float64 [n,3], faces int64 [m,3])``.  No CPU fallback.
+
+Out of scope: colour (the reference fuses the dataset's RGB along with the depth; nothing it reports depends on it), ICP alignment
+(``icp_align``), PLY reading / writing.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import lib, metrics3d, raster, tsdf
+
+DEPTH_TRUNC = 5.0                  # evaluation/methods.py:62
+ITERATIONS, LAM = 10, 0.5
+MESH_NAMES = ("tsdf", "refused_tsdf", "tsdf_smoothed", "refused_tsdf_smoothed")      # the order of methods.py:732-736
+
+
+def refuse(mesh, intrinsics, poses, height: int, width: int, bounds=None, voxel_length: float = tsdf.VOXEL_LENGTH,
+           sdf_trunc: float = tsdf.SDF_TRUNC, depth_trunc: float = DEPTH_TRUNC, near: float = raster.NEAR, far: float = raster.FAR,
+           pixel_centre: float = raster.PIXEL_CENTRE, device=None):
+    """Render the mesh's depth from every view, drop depths >= ``depth_trunc``, fuse the maps again -> (vertices, faces).  ``bounds`` as
+    in ``tsdf.fuse_depth_maps`` (None: the back-projected depth points, padded by ``sdf_trunc``).  Two empty tensors when no camera
+    sees anything."""
+    if isinstance(depth_trunc, bool) or not isinstance(depth_trunc, (int, float, np.integer, np.floating)) or not float(depth_trunc) > 0:
+        raise ValueError(f"depth_trunc must be a positive number, got {depth_trunc!r}")
+    vl, _ = tsdf._positive(voxel_length, "voxel_length"), tsdf._positive(sdf_trunc, "sdf_trunc")
+    if bounds is not None:
+        tsdf._box(bounds, vl)                                              # every refusal that needs no device comes before the first launch
+    depth = raster.rasterize_depth_counted(mesh, intrinsics, poses, height, width, near=near, far=far, pixel_centre=pixel_centre, device=device)[0]
+    depth = torch.where(depth >= float(depth_trunc), torch.zeros_like(depth), depth)
+    return tsdf.fuse_depth_maps(depth, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depth.device)
+
+
+def vertex_adjacency(faces: torch.Tensor, n_vertices: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """faces[m,3] (int64, every index in [0, n)) -> the CSR of the edge-neighbours (row_start[n+1], neighbours), on faces' device: the
+    three undirected edges of every face, self-edges dropped, duplicates removed, a vertex's neighbours in ascending order."""
+    a = torch.cat([faces[:, 0], faces[:, 1], faces[:, 2], faces[:, 1], faces[:, 2], faces[:, 0]])
+    b = torch.cat([faces[:, 1], faces[:, 2], faces[:, 0], faces[:, 0], faces[:, 1], faces[:, 2]])
+    keep = a != b
+    keys = torch.unique(a[keep] * n_vertices + b[keep])                  # sorted: by vertex, then by neighbour
+    rows = torch.div(keys, n_vertices, rounding_mode="floor")
+    row_start = torch.zeros(n_vertices + 1, dtype=torch.int64, device=faces.device)
+    row_start[1:] = torch.cumsum(torch.bincount(rows, minlength=n_vertices), dim=0)
+    return row_start, (keys - rows * n_vertices).contiguous()
+
+
+def smooth_laplacian(mesh, iterations: int = ITERATIONS, lam: float = LAM, device=None):
+    """``iterations`` Jacobi steps of uniform Laplacian smoothing -> (vertices, faces) on the device; the faces are the input's.  A vertex
+    that no face uses (or only degenerate ones) stays where it is."""
+    v, f = raster.check_mesh(mesh)
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 0:
+        raise ValueError(f"iterations must be a non-negative integer, got {iterations!r}")
+    if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)) or not math.isfinite(float(lam)):
+        raise ValueError(f"lam must be a finite number, got {lam!r}")
+    dev = raster._device(device if device is not None else (v.device if v.is_cuda else None))
+    v, f = v.to(dev, torch.float64).contiguous(), f.to(dev, torch.int64).contiguous()
+    n = v.shape[0]
+    if f.numel() and (int(f.min()) < 0 or int(f.max()) >= n):
+        raise lib.VfnError(f"Laplacian smoothing: a face index lies outside [0, {n})")
+    row_start, neighbours = vertex_adjacency(f, n)
+    return lib.smooth_laplacian(v, row_start, neighbours, int(iterations), float(lam)), f
+
+
+def reconstruction_meshes(tsdf_mesh, intrinsics, poses, height: int, width: int, iterations: int = ITERATIONS, lam: float = LAM,
+                          **refuse_args) -> Dict[str, tuple]:
+    """The four meshes ``metrics_3d`` scores (methods.py:686-709) from the TSDF mesh and the dataset's cameras: ``tsdf`` (as given),
+    ``tsdf_smoothed``, ``refused_tsdf`` = refuse(tsdf), ``refused_tsdf_smoothed`` = refuse(tsdf_smoothed).  ``refuse_args`` go to
+    ``refuse`` (bounds, voxel_length, sdf_trunc, depth_trunc, near, far, pixel_centre, device)."""
+    smoothed = smooth_laplacian(tsdf_mesh, iterations=iterations, lam=lam, device=refuse_args.get("device"))
+    dev = smoothed[0].device
+    v, f = raster.check_mesh(tsdf_mesh)
+    plain = (v.to(dev, torch.float64).contiguous(), smoothed[1])
+    return {"tsdf": plain, "tsdf_smoothed": smoothed,
+            "refused_tsdf": refuse(plain, intrinsics, poses, height, width, **refuse_args),
+            "refused_tsdf_smoothed": refuse(smoothed, intrinsics, poses, height, width, **refuse_args)}
+
+
+def metrics_3d(tsdf_mesh, gt_mesh, intrinsics, poses, height: int, width: int, num_points: int = 1000000, distance_thresh: float = 0.01,
+               generator: Optional[torch.Generator] = None, uniforms=None, iterations: int = ITERATIONS, lam: float = LAM,
+               **refuse_args) -> Dict[str, dict]:
+    """The dictionary the reference writes to ``3d-metrics.json`` (methods.py:732-741): keys ``tsdf``, ``refused_tsdf``,
+    ``tsdf_smoothed``, ``refused_tsdf_smoothed``, each ``metrics3d.score_mesh(mesh, gt_mesh)`` — {"chamfer distance": {mean, median,
+    min, max}, "precision", "recall", "fscore", ...} — scored in that order with the one ``generator`` (or the same ``uniforms``)."""
+    meshes = reconstruction_meshes(tsdf_mesh, intrinsics, poses, height, width, iterations=iterations, lam=lam, **refuse_args)
+    dev = meshes["tsdf"][0].device
+    return {name: metrics3d.score_mesh(meshes[name], gt_mesh, num_points=num_points, distance_thresh=distance_thresh, generator=generator,
+                                       uniforms=uniforms, device=dev) for name in MESH_NAMES}

@@ -20,8 +20,8 @@ restates it in NumPy, which the device equals bit for bit.  Two deliberate diffe
 A mesh is ``(vertices float64 [n,3], faces int64 [m,3])``, 0-based, on the device — the form ``mesh.triangulate`` returns and
 ``metrics3d.score_mesh`` accepts.  No CPU fallback: ``lib.VfnError`` when no device is visible.
 
-Out of scope: ``refuse()`` (its fusion half is this volume; it needs a mesh rasteriser for the depth maps), Laplacian smoothing
-(``tsdf-smoothed.ply``), PLY reading / writing.
+``refuse()`` and Laplacian smoothing (``tsdf-smoothed.ply``) are ``vf_nerf_amd.refuse``: a mesh's depth rasterised on the device
+(``vf_nerf_amd.raster``) and re-fused by this volume.  Out of scope: colour, PLY reading / writing.
 """
 from __future__ import annotations
 
