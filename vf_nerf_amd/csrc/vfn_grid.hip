@@ -22,10 +22,11 @@
 // corners outside the grid read as zero (the reference's zero padding).
 #include <string.h>
 #include "vfn_common.h"
+#include "vfn_mc_tables.h"     // VFN_MC_INC, VFN_MC_PAIR_A / _B
 
 namespace {
 
-__device__ __constant__ int CORNER[8][3] = {{0, 0, 0}, {0, 1, 0}, {1, 1, 0}, {1, 0, 0}, {0, 0, 1}, {0, 1, 1}, {1, 1, 1}, {1, 0, 1}};
+__device__ __constant__ int CORNER[8][3] = VFN_MC_INC;
 
 __device__ __forceinline__ void load_vec(const float* vt, long long N, int i, int j, int k, float (&v)[3]) {
     if (i < N && j < N && k < N) {
@@ -308,8 +309,8 @@ __global__ __launch_bounds__(256) void vfn_grid_unify_kernel(const float* __rest
 // ------------------------------------------------------------------------------------------------------------------------
 // the 28 corner pairs of every cell: do the two corners side differently, and their field magnitudes (mc_utils.py:170-223)
 // ------------------------------------------------------------------------------------------------------------------------
-__device__ __constant__ unsigned char PAIR_A[28] = {0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 5, 5, 6};
-__device__ __constant__ unsigned char PAIR_B[28] = {1, 2, 3, 4, 5, 6, 7, 2, 3, 4, 5, 6, 7, 3, 4, 5, 6, 7, 4, 5, 6, 7, 5, 6, 7, 6, 7, 7};
+__device__ __constant__ unsigned char PAIR_A[28] = VFN_MC_PAIR_A;
+__device__ __constant__ unsigned char PAIR_B[28] = VFN_MC_PAIR_B;
 
 template <bool FROM_BYTES>
 __global__ __launch_bounds__(256) void vfn_grid_comb_kernel(const long long* __restrict__ choice, const unsigned char* __restrict__ sides,

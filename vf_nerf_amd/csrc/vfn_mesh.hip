@@ -1,7 +1,7 @@
 // vfn_mesh.hip — contrastive marching cubes on the device: evaluation/utils/marching_cubes_vt.py:186-315
 // (contrastive_marching_cubes, combs_to_verts :62-101, vertex_interpolate :9-16), the last host stage of the evaluator's mesh
 // pipeline (evaluation/methods.py:140-322).  The reference visits every surface cell in a Python loop and deduplicates vertices
-// in a dict; here:
+// in a dict; here (count and emit are the extraction skeleton of vfn_mc_extract.h over the mesh source below):
 //   count     one lane per cell POSITION in the reference's order: it evaluates the cell's eight corner values and case and writes
 //             its triangle count; an ordered device scan (rocPRIM through hipCUB) gives every triangle its output slot.
 //   emit      the same lanes again: the float64 corner positions of the cell's triangles at their slots (3 vertices per triangle,
@@ -18,23 +18,17 @@
 // scope only; no float atomics.  All arithmetic in fp64 with -ffp-contract=off (build.sh): the reference's numpy expressions,
 // operation for operation.
 #include "vfn_common.h"
-#include "vfn_mc_tables.h"     // VFN_MC_TRI_ROWS, the edge / corner tables, the ordered scan
+#include "vfn_mc_extract.h"    // TRI / EDGE_A / EDGE_B / INC, the ordered scan, count -> scan -> total -> emit over a source
 
 namespace {
 
-// (entries after a row's -1 are never read; the host copy pads them with -1 for vfn_mesh_tables)
+// the host copies vfn_mesh_tables hands out (it pads the entries after a row's -1 with -1)
 const signed char TRI_HOST[256][16] = {VFN_MC_TRI_ROWS};
-__device__ __constant__ signed char TRI[256][16] = {VFN_MC_TRI_ROWS};
-// marching_cubes_lookup.EDGE_VERTEX order: edge 3 is (0, 3), edge 7 is (4, 7)
 const int EDGE_A_HOST[12] = VFN_MC_EDGE_A;
 const int EDGE_B_HOST[12] = VFN_MC_EDGE_B;
-__device__ __constant__ int EDGE_A[12] = VFN_MC_EDGE_A;
-__device__ __constant__ int EDGE_B[12] = VFN_MC_EDGE_B;
-// marching_cubes_vt.inc: corner q of cell (i, j, k) is (i, j, k) + INC[q]
-__device__ __constant__ int INC[8][3] = VFN_MC_INC;
 // the 28 corner pairs (a < b) in the order of marching_cubes_vt.combs, and pair index of (a, b) for a < b
-__device__ __constant__ unsigned char PA[28] = {0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 5, 5, 6};
-__device__ __constant__ unsigned char PB[28] = {1, 2, 3, 4, 5, 6, 7, 2, 3, 4, 5, 6, 7, 3, 4, 5, 6, 7, 4, 5, 6, 7, 5, 6, 7, 6, 7, 7};
+__device__ __constant__ unsigned char PA[28] = VFN_MC_PAIR_A;
+__device__ __constant__ unsigned char PB[28] = VFN_MC_PAIR_B;
 
 __device__ __forceinline__ int pair_index(int a, int b) {     // a < b
     return a * 7 - a * (a - 1) / 2 + (b - a - 1);
@@ -42,7 +36,10 @@ __device__ __forceinline__ int pair_index(int a, int b) {     // a < b
 
 constexpr unsigned STATUS_NONFINITE = 1u, STATUS_INDEX = 2u;
 
+// the mesh source of vfn_mc_extract.h, in its general and fused forms
 struct MeshArgs {
+    using Value = double;
+    struct Emit { double P[8][3]; };     // the cell's corner positions
     int form;                     // VFN_MESH_GENERAL | VFN_MESH_FUSED
     const void* comb;             // general: [m, 28]
     const void* udf;              // general: [m, 28, 2] or NULL
@@ -53,6 +50,11 @@ struct MeshArgs {
     long long m;                  // cell positions
     int res;
     double size, iso;
+
+    __host__ __device__ long long positions() const { return m; }
+    __device__ bool eval(long long p, int c[3], double v[8], int& top, unsigned& status) const;
+    __device__ void emit_setup(const int c[3], Emit& em) const;
+    __device__ void vertex(const int c[3], const double v[8], const Emit& em, int e, double out[3]) const;
 };
 
 __device__ __forceinline__ double grid_pos(int i, int res, double size) {
@@ -91,10 +93,10 @@ __device__ bool general_values(const T* __restrict__ comb, const T* __restrict__
 }
 
 // one cell position: its grid coordinates, corner values and case.  Returns false for a position that yields nothing.
-__device__ bool eval_cell(const MeshArgs& a, long long p, int c[3], double v[8], int& top, unsigned& status) {
-    const long long r = a.res;
+__device__ bool MeshArgs::eval(long long p, int c[3], double v[8], int& top, unsigned& status) const {
+    const long long r = res;
     bool from_norms;
-    if (a.form == VFN_MESH_FUSED) {
+    if (form == VFN_MESH_FUSED) {
         // evaluation/methods.py:184-188: (res/2)^3 blocks of 2x2x2 cells in raster order, corner order inside a block
         const long long blk = p >> 3, h = r >> 1;
         const int q = (int)(p & 7);
@@ -102,8 +104,8 @@ __device__ bool eval_cell(const MeshArgs& a, long long p, int c[3], double v[8],
         c[1] = (int)((blk / h) % h) * 2 + INC[q][1];
         c[2] = (int)(blk % h) * 2 + INC[q][2];
         const long long cell = ((long long)c[0] * r + c[1]) * r + c[2];
-        if (!finite((double)a.norms[cell])) status |= STATUS_NONFINITE;      // every grid point is corner 0 of one position
-        const unsigned bits = a.sides[cell];
+        if (!finite((double)norms[cell])) status |= STATUS_NONFINITE;      // every grid point is corner 0 of one position
+        const unsigned bits = sides[cell];
         if (bits == 0u || bits == 0xffu) return false;           // comb all zero: max 0 <= 0.5, no triangles
         // comb(a, b) = bit_a ^ bit_b: the anchor pair is (0, first corner unlike 0), and corner v sides with the second anchor iff
         // its bit differs from corner 0's: value = (bit_v != bit_0 ? +1 : -1) x norm(corner v), norm 0 outside the grid
@@ -111,63 +113,37 @@ __device__ bool eval_cell(const MeshArgs& a, long long p, int c[3], double v[8],
 #pragma unroll
         for (int q2 = 0; q2 < 8; ++q2) {
             const int ii = c[0] + INC[q2][0], jj = c[1] + INC[q2][1], kk = c[2] + INC[q2][2];
-            const float nv = (ii < r && jj < r && kk < r) ? a.norms[((long long)ii * r + jj) * r + kk] : 0.f;
+            const float nv = (ii < r && jj < r && kk < r) ? norms[((long long)ii * r + jj) * r + kk] : 0.f;
             v[q2] = (((bits >> q2) & 1u) != b0 ? 1.0 : -1.0) * (double)nv;
         }
         from_norms = true;
     } else {
-        if (a.cells) {
+        if (cells) {
             for (int d = 0; d < 3; ++d) {
-                const long long x = a.cells[p * 3 + d];
+                const long long x = cells[p * 3 + d];
                 if (x < 0 || x >= r) { status |= STATUS_INDEX; return false; }
                 c[d] = (int)x;
             }
         } else {
             c[0] = (int)(p / (r * r)); c[1] = (int)((p / r) % r); c[2] = (int)(p % r);
         }
-        if (a.f64) from_norms = general_values<double>((const double*)a.comb + p * 28, a.udf ? (const double*)a.udf + p * 56 : nullptr, v);
-        else from_norms = general_values<float>((const float*)a.comb + p * 28, a.udf ? (const float*)a.udf + p * 56 : nullptr, v);
+        if (f64) from_norms = general_values<double>((const double*)comb + p * 28, udf ? (const double*)udf + p * 56 : nullptr, v);
+        else from_norms = general_values<float>((const float*)comb + p * 28, udf ? (const float*)udf + p * 56 : nullptr, v);
     }
     int t = 0;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) t |= (v[q] < a.iso ? 1 : 0) << q;
+    for (int q = 0; q < 8; ++q) t |= (v[q] < iso ? 1 : 0) << q;
     top = t;
     if (t == 0 || t == 255) return false;                      // EDGE_TABLE[0] = EDGE_TABLE[255] = 0: no edge is cut
-    if (from_norms && a.form != VFN_MESH_FUSED)
+    if (from_norms && form != VFN_MESH_FUSED)
         for (int q = 0; q < 8; ++q)
             if (!finite(v[q])) status |= STATUS_NONFINITE;
     return true;
 }
 
-__device__ __forceinline__ int tri_count(int top) {
-    int n = 0;
-    while (n < 5 && TRI[top][3 * n] >= 0) ++n;
-    return n;
-}
-
-__global__ __launch_bounds__(256) void vfn_mesh_count_kernel(MeshArgs a, int* __restrict__ counts, long long* __restrict__ info) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned status = 0;
-    if (p < a.m) {
-        int c[3], top = 0;
-        double v[8];
-        counts[p] = eval_cell(a, p, c, v, top, status) ? tri_count(top) : 0;
-    }
-    // (one atomic per wave that saw a bad input)
-    const unsigned long long any = __ballot(status != 0u);
-    if (any) {
-        unsigned all = status;
-        for (int o = 32; o > 0; o >>= 1) all |= (unsigned)__shfl_xor((int)all, o, 64);
-        if ((threadIdx.x & 63) == (unsigned)__builtin_ctzll(any)) atomicOr((unsigned long long*)&info[1], (unsigned long long)all);
-    }
-}
-
-__global__ void vfn_mesh_total_kernel(const int* __restrict__ incl, long long last, long long* __restrict__ info, int slot) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) info[slot] = last >= 0 ? (long long)incl[last] : 0ll;
-}
-
 // vertex_interpolate (:9-16): swap when p1 > p2 in any component, interpolate only when |v1 - v2| > 1e-5
-__device__ __forceinline__ void edge_vertex(const double P[8][3], const double v[8], int e, double iso, double out[3]) {
+__device__ __forceinline__ void MeshArgs::vertex(const int[3], const double v[8], const Emit& em, int e, double out[3]) const {
+    const double (*P)[3] = em.P;
     int e1 = EDGE_A[e], e2 = EDGE_B[e];
     if (P[e1][0] > P[e2][0] || P[e1][1] > P[e2][1] || P[e1][2] > P[e2][2]) { const int t = e1; e1 = e2; e2 = t; }
     const double v1 = v[e1], v2 = v[e2];
@@ -178,28 +154,10 @@ __device__ __forceinline__ void edge_vertex(const double P[8][3], const double v
     }
 }
 
-__global__ __launch_bounds__(256) void vfn_mesh_emit_kernel(MeshArgs a, const int* __restrict__ counts, const int* __restrict__ incl,
-                                                            double* __restrict__ tri_verts) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= a.m) return;
-    const int n = counts[p];
-    if (n == 0) return;
-    int c[3], top = 0;
-    double v[8];
-    unsigned status = 0;
-    if (!eval_cell(a, p, c, v, top, status)) return;
-    double P[8][3];
+__device__ __forceinline__ void MeshArgs::emit_setup(const int c[3], Emit& em) const {
 #pragma unroll
     for (int q = 0; q < 8; ++q)
-        for (int d = 0; d < 3; ++d) P[q][d] = grid_pos(c[d] + INC[q][d], a.res, a.size);
-    const long long slot0 = (long long)(incl[p] - n) * 3;
-    for (int t = 0; t < n; ++t)
-        for (int k = 0; k < 3; ++k) {
-            double x[3];
-            edge_vertex(P, v, TRI[top][3 * t + k], a.iso, x);
-            double* o = tri_verts + (slot0 + 3 * t + k) * 3;
-            o[0] = x[0]; o[1] = x[1]; o[2] = x[2];
-        }
+        for (int d = 0; d < 3; ++d) em.P[q][d] = grid_pos(c[d] + INC[q][d], res, size);
 }
 
 // ---- deduplication ----------------------------------------------------------------------------------------------------
@@ -274,14 +232,6 @@ __global__ __launch_bounds__(256) void vfn_mesh_field_norms_kernel(const float* 
     }
 }
 
-inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
-
-int scan_bytes(long long n, size_t* bytes) { return vfn_mc_scan_bytes(n, bytes); }
-
-int inclusive_scan(const int* in, int* out, long long n, void* ws, long long ws_bytes, hipStream_t s, const char* what) {
-    return vfn_mc_inclusive_scan(in, out, n, ws, ws_bytes, s, what);
-}
-
 int make_args(MeshArgs& a, int32_t form, const void* comb, const void* udf, int32_t f64, const int64_t* cells, const uint8_t* sides,
               const float* norms, int64_t m, int32_t res, double size, double isovalue, const char* what) {
     a = MeshArgs{};
@@ -321,7 +271,7 @@ extern "C" int vfn_mesh_tables(int32_t* edge_table, int32_t* edge_vertex, int8_t
 extern "C" int64_t vfn_mesh_scan_workspace_bytes(int64_t n) {
     size_t b = 0;
     if (n < 1) n = 1;
-    if (scan_bytes(n, &b) != VFN_OK) return -1;
+    if (vfn_mc_scan_bytes(n, &b) != VFN_OK) return -1;
     return (int64_t)b;
 }
 
@@ -331,15 +281,7 @@ extern "C" int vfn_mesh_count(int32_t form, const void* comb, const void* udf, i
     MeshArgs a;
     const int rc = make_args(a, form, comb, udf, f64, cells, sides, norms, m, res, size, isovalue, "vfn_mesh_count");
     if (rc != VFN_OK) return rc;
-    VFN_REQUIRE(info && (m == 0 || (counts && offsets)), "vfn_mesh_count: NULL output");
-    hipStream_t s = (hipStream_t)stream;
-    if (m > 0) {
-        hipLaunchKernelGGL(vfn_mesh_count_kernel, dim3(blocks_for(m)), dim3(256), 0, s, a, (int*)counts, (long long*)info);
-        const int r2 = inclusive_scan(counts, offsets, m, scan_ws, scan_ws_bytes, s, "vfn_mesh_count");
-        if (r2 != VFN_OK) return r2;
-    }
-    hipLaunchKernelGGL(vfn_mesh_total_kernel, dim3(1), dim3(64), 0, s, (const int*)offsets, (long long)(m - 1), (long long*)info, 0);
-    return vfn_check_launch("vfn_mesh_count");
+    return vfn_mc_count(a, counts, offsets, info, scan_ws, scan_ws_bytes, (hipStream_t)stream, "vfn_mesh_count");
 }
 
 extern "C" int vfn_mesh_emit(int32_t form, const void* comb, const void* udf, int32_t f64, const int64_t* cells, const uint8_t* sides,
@@ -348,11 +290,7 @@ extern "C" int vfn_mesh_emit(int32_t form, const void* comb, const void* udf, in
     MeshArgs a;
     const int rc = make_args(a, form, comb, udf, f64, cells, sides, norms, m, res, size, isovalue, "vfn_mesh_emit");
     if (rc != VFN_OK) return rc;
-    if (m == 0) return VFN_OK;
-    VFN_REQUIRE(counts && offsets && tri_verts, "vfn_mesh_emit: NULL argument");
-    hipLaunchKernelGGL(vfn_mesh_emit_kernel, dim3(blocks_for(m)), dim3(256), 0, (hipStream_t)stream, a, (const int*)counts, (const int*)offsets,
-                       tri_verts);
-    return vfn_check_launch("vfn_mesh_emit");
+    return vfn_mc_emit(a, counts, offsets, tri_verts, (hipStream_t)stream, "vfn_mesh_emit");
 }
 
 extern "C" int vfn_mesh_dedup(const double* tri_verts, int64_t n_slots, int32_t* table, int32_t* owner, int64_t table_size, int32_t* bucket,
@@ -368,10 +306,10 @@ extern "C" int vfn_mesh_dedup(const double* tri_verts, int64_t n_slots, int32_t*
                            (int*)owner, (long long)(table_size - 1), (int*)bucket);
         hipLaunchKernelGGL(vfn_mesh_flag_kernel, dim3(blocks_for(n_slots)), dim3(256), 0, s, (const int*)owner, (const int*)bucket,
                            (long long)n_slots, (int*)flags);
-        const int rc = inclusive_scan(flags, vid, n_slots, scan_ws, scan_ws_bytes, s, "vfn_mesh_dedup");
+        const int rc = vfn_mc_inclusive_scan(flags, vid, n_slots, scan_ws, scan_ws_bytes, s, "vfn_mesh_dedup");
         if (rc != VFN_OK) return rc;
     }
-    hipLaunchKernelGGL(vfn_mesh_total_kernel, dim3(1), dim3(64), 0, s, (const int*)vid, (long long)(n_slots - 1), (long long*)info, 2);
+    hipLaunchKernelGGL(vfn_mc_total_kernel, dim3(1), dim3(64), 0, s, (const int*)vid, (long long)(n_slots - 1), (long long*)info, 2);
     return vfn_check_launch("vfn_mesh_dedup");
 }
 

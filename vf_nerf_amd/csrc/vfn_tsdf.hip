@@ -12,20 +12,15 @@
 //              monotone in each operand once the signs of the coefficients are fixed, and rounding keeps order (a <= b gives
 //              fl(a) <= fl(b)), so the extreme of the ROUNDED value over the brick is the rounded value at a corner — no margin, no
 //              second arithmetic.  A NaN anywhere makes every comparison false and the view is kept.
-//   count/emit one lane per cell in C order: the case from the signs of the eight corner values (a corner with weight 0 voids the cell),
-//              the triangle count, the ordered scan of the mesh unit, then every triangle's three float64 vertices at their slots in
-//              the layout vfn_mesh_dedup / vfn_mesh_number consume.  A vertex is a function of its edge alone, so the (up to) four
+//   count/emit the extraction skeleton of vfn_mc_extract.h over the TSDF source below, one lane per cell in C order: the case from the
+//              signs of the eight corner values (a corner with weight 0 voids the cell), the triangle count, the ordered scan, then
+//              every triangle's three float64 vertices at their slots in the layout vfn_mesh_dedup / vfn_mesh_number consume.  A vertex is a function of its edge alone, so the (up to) four
 //              cells around an edge emit identical bits and the positional merge joins them.
 // No atomics.  fp32 (integration) and fp64 (vertices) without contraction: -ffp-contract=off (build.sh), correctly rounded / and sqrtf.
 #include "vfn_common.h"
-#include "vfn_mc_tables.h"
+#include "vfn_mc_extract.h"    // EDGE_A / EDGE_B / INC, count -> scan -> total -> emit over a source
 
 namespace {
-
-__device__ __constant__ signed char TRI[256][16] = {VFN_MC_TRI_ROWS};
-__device__ __constant__ int EDGE_A[12] = VFN_MC_EDGE_A;
-__device__ __constant__ int EDGE_B[12] = VFN_MC_EDGE_B;
-__device__ __constant__ int INC[8][3] = VFN_MC_INC;
 
 constexpr int RUN = 4;                     // consecutive k voxels of a lane: one 16-B access per array
 constexpr int BK_RUNS = 8, BJ = 8, BI = 4; // lanes of a workgroup along k (runs), j, i: a brick of 4 x 8 x 32 voxels, one i-slab per wave
@@ -184,86 +179,54 @@ __global__ __launch_bounds__(THREADS) void vfn_tsdf_integrate_kernel(Volume vol,
 }
 
 // ---- extraction -------------------------------------------------------------------------------------------------------
+// the TSDF source of vfn_mc_extract.h: it never sets a status
 struct Lattice {
+    using Value = float;
+    struct Emit {};
     const float* tsdf;
     const float* weight;
     int nx, ny, nz;
     long long cells;          // (nx - 1)(ny - 1)(nz - 1)
     float ox, oy, oz, vl;
-};
 
-// cell p in C order: its lattice index, corner values and case; false for a cell that emits nothing
-__device__ __forceinline__ bool eval_cell(const Lattice& a, long long p, int c[3], float v[8], int& top) {
-    const long long cz = a.nz - 1, cy = a.ny - 1;
-    c[2] = (int)(p % cz);
-    c[1] = (int)((p / cz) % cy);
-    c[0] = (int)(p / (cz * cy));
-    int t = 0;
+    __host__ __device__ long long positions() const { return cells; }
+
+    // cell p in C order: its lattice index, corner values and case; false for a cell that emits nothing
+    __device__ __forceinline__ bool eval(long long p, int c[3], float v[8], int& top, unsigned&) const {
+        const long long cz = nz - 1, cy = ny - 1;
+        c[2] = (int)(p % cz);
+        c[1] = (int)((p / cz) % cy);
+        c[0] = (int)(p / (cz * cy));
+        int t = 0;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const long long idx = ((long long)(c[0] + INC[q][0]) * a.ny + (c[1] + INC[q][1])) * a.nz + (c[2] + INC[q][2]);
-        if (a.weight[idx] == 0.f) return false;               // an unobserved corner voids the cell
-        v[q] = a.tsdf[idx];
-        t |= (v[q] < 0.f ? 1 : 0) << q;                       // exactly 0 counts as outside
-    }
-    top = t;
-    return t != 0 && t != 255;
-}
-
-__device__ __forceinline__ int tri_count(int top) {
-    int n = 0;
-    while (n < 5 && TRI[top][3 * n] >= 0) ++n;
-    return n;
-}
-
-__global__ __launch_bounds__(256) void vfn_tsdf_count_kernel(Lattice a, int* __restrict__ counts) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= a.cells) return;
-    int c[3], top = 0;
-    float v[8];
-    counts[p] = eval_cell(a, p, c, v, top) ? tri_count(top) : 0;
-}
-
-__global__ void vfn_tsdf_total_kernel(const int* __restrict__ incl, long long last, long long* __restrict__ info) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) info[0] = last >= 0 ? (long long)incl[last] : 0ll;
-}
-
-// the vertex of cut edge e of cell c: a function of the edge alone (its lower endpoint L, its axis, the two values)
-__device__ __forceinline__ void edge_vertex(const Lattice& a, const int c[3], const float v[8], int e, double out[3]) {
-    const int qa = EDGE_A[e], qb = EDGE_B[e];
-    int axis = 0;
-    if (INC[qa][1] != INC[qb][1]) axis = 1;
-    if (INC[qa][2] != INC[qb][2]) axis = 2;
-    const bool a_low = INC[qa][axis] < INC[qb][axis];
-    const int ql = a_low ? qa : qb, qu = a_low ? qb : qa;
-    const double vl = (double)a.vl;
-    const double o[3] = {(double)a.ox, (double)a.oy, (double)a.oz};
-#pragma unroll
-    for (int d = 0; d < 3; ++d) out[d] = o[d] + ((double)(c[d] + INC[ql][d]) + 0.5) * vl;
-    const double fl = fabs((double)v[ql]), fu = fabs((double)v[qu]);
-    out[axis] = out[axis] + (fl / (fl + fu)) * vl;
-}
-
-__global__ __launch_bounds__(256) void vfn_tsdf_emit_kernel(Lattice a, const int* __restrict__ counts, const int* __restrict__ incl,
-                                                            double* __restrict__ tri_verts) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= a.cells) return;
-    const int n = counts[p];
-    if (n == 0) return;
-    int c[3], top = 0;
-    float v[8];
-    if (!eval_cell(a, p, c, v, top)) return;
-    const long long slot0 = (long long)(incl[p] - n) * 3;
-    for (int t = 0; t < n; ++t)
-        for (int k = 0; k < 3; ++k) {
-            double x[3];
-            edge_vertex(a, c, v, TRI[top][3 * t + k], x);
-            double* o = tri_verts + (slot0 + 3 * t + k) * 3;
-            o[0] = x[0]; o[1] = x[1]; o[2] = x[2];
+        for (int q = 0; q < 8; ++q) {
+            const long long idx = ((long long)(c[0] + INC[q][0]) * ny + (c[1] + INC[q][1])) * nz + (c[2] + INC[q][2]);
+            if (weight[idx] == 0.f) return false;                 // an unobserved corner voids the cell
+            v[q] = tsdf[idx];
+            t |= (v[q] < 0.f ? 1 : 0) << q;                       // exactly 0 counts as outside
         }
-}
+        top = t;
+        return t != 0 && t != 255;
+    }
 
-inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
+    __device__ __forceinline__ void emit_setup(const int[3], Emit&) const {}
+
+    // the vertex of cut edge e of the cell: a function of the edge alone (its lower endpoint L, its axis, the two values)
+    __device__ __forceinline__ void vertex(const int c[3], const float v[8], const Emit&, int e, double out[3]) const {
+        const int qa = EDGE_A[e], qb = EDGE_B[e];
+        int axis = 0;
+        if (INC[qa][1] != INC[qb][1]) axis = 1;
+        if (INC[qa][2] != INC[qb][2]) axis = 2;
+        const bool a_low = INC[qa][axis] < INC[qb][axis];
+        const int ql = a_low ? qa : qb, qu = a_low ? qb : qa;
+        const double vld = (double)vl;
+        const double o[3] = {(double)ox, (double)oy, (double)oz};
+#pragma unroll
+        for (int d = 0; d < 3; ++d) out[d] = o[d] + ((double)(c[d] + INC[ql][d]) + 0.5) * vld;
+        const double fl = fabs((double)v[ql]), fu = fabs((double)v[qu]);
+        out[axis] = out[axis] + (fl / (fl + fu)) * vld;
+    }
+};
 
 int check_dims(int32_t nx, int32_t ny, int32_t nz, float vl, const char* what) {
     VFN_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1 && (long long)nx * ny < (1ll << 31) && (long long)nx * ny * nz < (1ll << 31),
@@ -312,15 +275,7 @@ extern "C" int vfn_tsdf_count(const float* tsdf, const float* weight, int32_t nx
     Lattice a;
     const int rc = make_lattice(a, tsdf, weight, nx, ny, nz, 0.f, 0.f, 0.f, 1.f, "vfn_tsdf_count");
     if (rc != VFN_OK) return rc;
-    VFN_REQUIRE(info && (a.cells == 0 || (counts && offsets)), "vfn_tsdf_count: NULL output");
-    hipStream_t s = (hipStream_t)stream;
-    if (a.cells > 0) {
-        hipLaunchKernelGGL(vfn_tsdf_count_kernel, dim3(blocks_for(a.cells)), dim3(256), 0, s, a, (int*)counts);
-        const int r2 = vfn_mc_inclusive_scan(counts, offsets, a.cells, scan_ws, scan_ws_bytes, s, "vfn_tsdf_count");
-        if (r2 != VFN_OK) return r2;
-    }
-    hipLaunchKernelGGL(vfn_tsdf_total_kernel, dim3(1), dim3(64), 0, s, (const int*)offsets, (long long)(a.cells - 1), (long long*)info);
-    return vfn_check_launch("vfn_tsdf_count");
+    return vfn_mc_count(a, counts, offsets, info, scan_ws, scan_ws_bytes, (hipStream_t)stream, "vfn_tsdf_count");
 }
 
 extern "C" int vfn_tsdf_emit(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz,
@@ -328,9 +283,5 @@ extern "C" int vfn_tsdf_emit(const float* tsdf, const float* weight, int32_t nx,
     Lattice a;
     const int rc = make_lattice(a, tsdf, weight, nx, ny, nz, ox, oy, oz, voxel_length, "vfn_tsdf_emit");
     if (rc != VFN_OK) return rc;
-    if (a.cells == 0) return VFN_OK;
-    VFN_REQUIRE(counts && offsets && tri_verts, "vfn_tsdf_emit: NULL argument");
-    hipLaunchKernelGGL(vfn_tsdf_emit_kernel, dim3(blocks_for(a.cells)), dim3(256), 0, (hipStream_t)stream, a, (const int*)counts,
-                       (const int*)offsets, tri_verts);
-    return vfn_check_launch("vfn_tsdf_emit");
+    return vfn_mc_emit(a, counts, offsets, tri_verts, (hipStream_t)stream, "vfn_tsdf_emit");
 }

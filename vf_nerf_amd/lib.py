@@ -1239,7 +1239,8 @@ def grid_comb_format(choice: torch.Tensor, norms: torch.Tensor, n: int):
 # mesh triangulation (csrc/vfn_mesh.hip; vf_nerf_amd/mesh.py is the public surface)
 # ------------------------------------------------------------------------------------------------
 MESH_GENERAL, MESH_FUSED = 0, 1
-MESH_STATUS_NONFINITE, MESH_STATUS_INDEX = 1, 2
+# the status word every geometry kernel reports bad input with (mesh, metrics, rasteriser): a non-finite value, an index out of range
+GEOM_STATUS_NONFINITE, GEOM_STATUS_INDEX = 1, 2
 
 
 def mesh_tables():
@@ -1261,43 +1262,60 @@ def mesh_field_norms(field: torch.Tensor, want_unit: bool = True):
     return norms, unit
 
 
-def _scan_ws(n: int, dev) -> torch.Tensor:
-    b = int(load().vfn_mesh_scan_workspace_bytes(C.c_int64(max(n, 1))))
+def _bytes_ws(fn_name: str, n: int, dev) -> torch.Tensor:
+    """The workspace the entry point ``fn_name`` asks for over n elements, as a uint8 tensor on ``dev``."""
+    b = int(getattr(load(), fn_name)(C.c_int64(n)))
     if b < 0:
-        raise VfnError(f"vfn_mesh_scan_workspace_bytes failed: {load().vfn_last_error().decode()}")
+        raise VfnError(f"{fn_name} failed: {load().vfn_last_error().decode()}")
     return torch.empty(max(b, 1), dtype=torch.uint8, device=dev)
+
+
+def _extract(count, emit, cells: int, dev, what: str, check_status=None):
+    """The sequence both triangulating units run over their ``cells`` cell positions: count -> emit -> dedup -> number on the current
+    stream of ``dev`` -> (vertices[V,3] float64, faces[F,3] int64, 0-based).  ``count`` and ``emit`` are the unit's entry points closed
+    over the source's leading arguments; they receive the trailing ones.  Two values cross to the host, each to size the next outputs:
+    the triangle count — with the input status, handed to ``check_status`` — and the vertex count."""
+    from .geomargs import empty_mesh          # (geomargs imports this module)
+    with torch.cuda.device(dev):
+        info = torch.zeros(4, dtype=torch.int64, device=dev)
+        counts = torch.empty(max(cells, 1), dtype=torch.int32, device=dev)
+        offsets = torch.empty_like(counts)
+        ws = _bytes_ws("vfn_mesh_scan_workspace_bytes", cells, dev)
+        scanned = (_ptr(counts, "counts", torch.int32), _ptr(offsets, "offsets", torch.int32))
+        count(*scanned, _ptr(info, "info", torch.int64), _ptr(ws, "scan_ws", torch.uint8), C.c_int64(ws.numel()), _stream())
+        n_tri, status = (int(x) for x in info[:2].cpu())
+        if check_status is not None:
+            check_status(status)
+        n_slots = 3 * n_tri
+        if n_tri < 0 or n_slots >= (1 << 31):
+            raise VfnError(f"{what}: {n_tri} triangles exceed the 2^31 / 3 limit")
+        if n_tri == 0:
+            return empty_mesh(dev)
+        tri_verts = torch.empty(n_slots, 3, dtype=torch.float64, device=dev)
+        emit(*scanned, _ptr(tri_verts, "tri_verts", torch.float64), _stream())
+        vertices, ids = mesh_dedup(tri_verts, info=info)
+    return vertices, ids.view(n_tri, 3)
 
 
 def mesh_triangulate(form: int, m: int, res: int, size: float, isovalue: float, comb: Optional[torch.Tensor] = None,
                      udf: Optional[torch.Tensor] = None, cells: Optional[torch.Tensor] = None, sides: Optional[torch.Tensor] = None,
                      norms: Optional[torch.Tensor] = None, device=None):
-    """count -> emit -> dedup -> number on the current stream -> (vertices[V,3] float64, faces[F,3] int64, 0-based).  Two values cross to
-    the host: the triangle count (with the input status) and the vertex count, each to size the next outputs."""
+    """Contrastive marching cubes (csrc/vfn_mesh.hip) through ``_extract`` -> (vertices[V,3] float64, faces[F,3] int64, 0-based)."""
     dev = torch.device(device) if device is not None else (norms.device if norms is not None else comb.device)
     f64 = int(comb is not None and comb.dtype == torch.float64)
     dt = torch.float64 if f64 else torch.float32
     ptrs = (C.c_int32(form), _ptr(comb, "comb", dt), _ptr(udf, "udf", dt), C.c_int32(f64), _ptr(cells, "cells", torch.int64),
             _ptr(sides, "sides", torch.uint8), _ptr(norms, "norms"), C.c_int64(m), C.c_int32(res), C.c_double(size), C.c_double(isovalue))
-    info = torch.zeros(4, dtype=torch.int64, device=dev)
-    counts = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
-    offsets = torch.empty_like(counts)
-    ws = _scan_ws(m, dev)
-    _check(load().vfn_mesh_count(*ptrs, _ptr(counts, "counts", torch.int32), _ptr(offsets, "offsets", torch.int32), _ptr(info, "info", torch.int64),
-                                 _ptr(ws, "scan_ws", torch.uint8), C.c_int64(ws.numel()), _stream()), "vfn_mesh_count")
-    n_tri, status = (int(x) for x in info[:2].cpu())
-    if status & MESH_STATUS_INDEX:
-        raise VfnError(f"mesh triangulation: a cell index lies outside [0, {res})")
-    if status & MESH_STATUS_NONFINITE:
-        raise VfnError("mesh triangulation: a non-finite norm / udf value in a triangulated cell (NaN vertices cannot be deduplicated "
-                       "meaningfully; the reference's dict would keep every one of them)")
-    n_slots = 3 * n_tri
-    if n_tri < 0 or n_slots >= (1 << 31):
-        raise VfnError(f"mesh triangulation: {n_tri} triangles exceed the 2^31 / 3 limit")
-    tri_verts = torch.empty(max(n_slots, 1), 3, dtype=torch.float64, device=dev)
-    _check(load().vfn_mesh_emit(*ptrs, _ptr(counts, "counts", torch.int32), _ptr(offsets, "offsets", torch.int32),
-                                _ptr(tri_verts, "tri_verts", torch.float64), _stream()), "vfn_mesh_emit")
-    vertices, ids = mesh_dedup(tri_verts[:n_slots], info=info)
-    return vertices, ids.view(n_tri, 3)
+
+    def check_status(status: int) -> None:
+        if status & GEOM_STATUS_INDEX:
+            raise VfnError(f"mesh triangulation: a cell index lies outside [0, {res})")
+        if status & GEOM_STATUS_NONFINITE:
+            raise VfnError("mesh triangulation: a non-finite norm / udf value in a triangulated cell (NaN vertices cannot be deduplicated "
+                           "meaningfully; the reference's dict would keep every one of them)")
+
+    return _extract(lambda *out: _check(load().vfn_mesh_count(*ptrs, *out), "vfn_mesh_count"),
+                    lambda *out: _check(load().vfn_mesh_emit(*ptrs, *out), "vfn_mesh_emit"), m, dev, "mesh triangulation", check_status)
 
 
 def mesh_dedup(tri_verts: torch.Tensor, info: Optional[torch.Tensor] = None):
@@ -1310,46 +1328,39 @@ def mesh_dedup(tri_verts: torch.Tensor, info: Optional[torch.Tensor] = None):
         raise VfnError(f"mesh deduplication: {n_slots} slots exceed the 2^31 limit")
     if info is None:
         info = torch.zeros(4, dtype=torch.int64, device=dev)
-    if n_slots == 0:
-        tri_verts = torch.empty(1, 3, dtype=torch.float64, device=dev)
-    table_size = 1 << max(6, (2 * n_slots - 1).bit_length())
-    table = torch.empty(table_size, dtype=torch.int32, device=dev)
-    owner = torch.empty_like(table)
-    bucket = torch.empty(max(n_slots, 1), dtype=torch.int32, device=dev)
-    flags, vid = torch.empty_like(bucket), torch.empty_like(bucket)
-    ws = _scan_ws(n_slots, dev)
-    _check(load().vfn_mesh_dedup(_ptr(tri_verts, "tri_verts", torch.float64), C.c_int64(n_slots), _ptr(table, "table", torch.int32),
-                                 _ptr(owner, "owner", torch.int32), C.c_int64(table_size), _ptr(bucket, "bucket", torch.int32),
-                                 _ptr(flags, "flags", torch.int32), _ptr(vid, "vid", torch.int32), _ptr(info, "info", torch.int64),
-                                 _ptr(ws, "scan_ws", torch.uint8), C.c_int64(ws.numel()), _stream()), "vfn_mesh_dedup")
-    n_vert = int(info[2].cpu())
-    vertices = torch.empty(n_vert, 3, dtype=torch.float64, device=dev)
-    ids = torch.empty(n_slots, dtype=torch.int64, device=dev)
-    _check(load().vfn_mesh_number(_ptr(tri_verts, "tri_verts", torch.float64), C.c_int64(n_slots), _ptr(owner, "owner", torch.int32),
-                                  _ptr(bucket, "bucket", torch.int32), _ptr(vid, "vid", torch.int32),
-                                  _ptr(vertices, "vertices", torch.float64) if n_vert else None,
-                                  _ptr(ids, "faces", torch.int64) if n_slots else None, _stream()), "vfn_mesh_number")
+    with torch.cuda.device(dev):
+        if n_slots == 0:
+            tri_verts = torch.empty(1, 3, dtype=torch.float64, device=dev)
+        table_size = 1 << max(6, (2 * n_slots - 1).bit_length())
+        table = torch.empty(table_size, dtype=torch.int32, device=dev)
+        owner = torch.empty_like(table)
+        bucket = torch.empty(max(n_slots, 1), dtype=torch.int32, device=dev)
+        flags, vid = torch.empty_like(bucket), torch.empty_like(bucket)
+        ws = _bytes_ws("vfn_mesh_scan_workspace_bytes", n_slots, dev)
+        _check(load().vfn_mesh_dedup(_ptr(tri_verts, "tri_verts", torch.float64), C.c_int64(n_slots), _ptr(table, "table", torch.int32),
+                                     _ptr(owner, "owner", torch.int32), C.c_int64(table_size), _ptr(bucket, "bucket", torch.int32),
+                                     _ptr(flags, "flags", torch.int32), _ptr(vid, "vid", torch.int32), _ptr(info, "info", torch.int64),
+                                     _ptr(ws, "scan_ws", torch.uint8), C.c_int64(ws.numel()), _stream()), "vfn_mesh_dedup")
+        n_vert = int(info[2].cpu())
+        vertices = torch.empty(n_vert, 3, dtype=torch.float64, device=dev)
+        ids = torch.empty(n_slots, dtype=torch.int64, device=dev)
+        _check(load().vfn_mesh_number(_ptr(tri_verts, "tri_verts", torch.float64), C.c_int64(n_slots), _ptr(owner, "owner", torch.int32),
+                                      _ptr(bucket, "bucket", torch.int32), _ptr(vid, "vid", torch.int32),
+                                      _ptr(vertices, "vertices", torch.float64) if n_vert else None,
+                                      _ptr(ids, "faces", torch.int64) if n_slots else None, _stream()), "vfn_mesh_number")
     return vertices, ids
 
 
 # ------------------------------------------------------------------------------------------------
 # mesh scoring (csrc/vfn_metrics.hip; vf_nerf_amd/metrics3d.py is the public surface).  Everything float64, contiguous, on one device.
 # ------------------------------------------------------------------------------------------------
-METRICS_STATUS_NONFINITE, METRICS_STATUS_INDEX = 1, 2
 CUMSUM_TILE, REDUCE_TILE, REDUCE_TOP = 1024, 4096, 1024      # csrc/vfn_metrics.hip: SCAN_TILE, RED_TILE, RED_TOP
-
-
-def _bytes_ws(fn_name: str, n: int, dev) -> torch.Tensor:
-    b = int(getattr(load(), fn_name)(C.c_int64(n)))
-    if b < 0:
-        raise VfnError(f"{fn_name} failed: {load().vfn_last_error().decode()}")
-    return torch.empty(max(b, 1), dtype=torch.uint8, device=dev)
 
 
 def nn_sqdist(queries: torch.Tensor, targets: torch.Tensor, info: Optional[torch.Tensor] = None) -> torch.Tensor:
     """queries[n,3], targets[m,3] -> best[n]: the squared distance of every query to its nearest target, all pairs in float64.  A
     non-finite coordinate in either set raises (one status word crosses to the host) — or, with the caller's zero-filled ``info``
-    (int64 [1]), sets its bit METRICS_STATUS_NONFINITE for the caller to read with its results (``nn_check``)."""
+    (int64 [1]), sets its bit GEOM_STATUS_NONFINITE for the caller to read with its results (``nn_check``)."""
     n, m = queries.shape[0], targets.shape[0]
     best = torch.empty(n, dtype=torch.float64, device=queries.device)
     own = info is None
@@ -1363,7 +1374,7 @@ def nn_sqdist(queries: torch.Tensor, targets: torch.Tensor, info: Optional[torch
 
 
 def nn_check(status: int) -> None:
-    if status & METRICS_STATUS_NONFINITE:
+    if status & GEOM_STATUS_NONFINITE:
         raise VfnError("nearest-neighbour search: a non-finite coordinate in the queries or the targets")
 
 
@@ -1375,9 +1386,9 @@ def tri_areas(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     _check(load().vfn_tri_areas(_ptr(vertices, "vertices", torch.float64) if nv else None, C.c_int64(nv), _ptr(faces, "faces", torch.int64),
                                 C.c_int64(nf), _ptr(areas, "areas", torch.float64), _ptr(info, "info", torch.int64), _stream()), "vfn_tri_areas")
     status = int(info.cpu())
-    if status & METRICS_STATUS_INDEX:
+    if status & GEOM_STATUS_INDEX:
         raise VfnError(f"triangle areas: a face index lies outside [0, {nv})")
-    if status & METRICS_STATUS_NONFINITE:
+    if status & GEOM_STATUS_NONFINITE:
         raise VfnError("triangle areas: a non-finite area (non-finite or overflowing vertex coordinates)")
     return areas
 
@@ -1467,40 +1478,18 @@ def tsdf_integrate(tsdf: torch.Tensor, weight: torch.Tensor, origin: Sequence[fl
 
 
 def tsdf_extract(tsdf: torch.Tensor, weight: torch.Tensor, origin: Sequence[float], voxel_length: float):
-    """The zero level set of the volume: count -> emit (csrc/vfn_tsdf.hip) -> dedup -> number (the mesh unit's) on the current stream
-    -> (vertices[n,3] float64, faces[m,3] int64, 0-based).  The triangle and the vertex count cross to the host to size the outputs."""
+    """The zero level set of the volume (csrc/vfn_tsdf.hip) through ``_extract`` -> (vertices[n,3] float64, faces[m,3] int64, 0-based)."""
     vol = _tsdf_volume_args(tsdf, weight)
-    dev = tsdf.device
     nx, ny, nz = tsdf.shape
-    cells = (nx - 1) * (ny - 1) * (nz - 1)
     box = tuple(C.c_float(float(o)) for o in origin) + (C.c_float(float(voxel_length)),)
-    with torch.cuda.device(dev):
-        info = torch.zeros(4, dtype=torch.int64, device=dev)
-        counts = torch.empty(max(cells, 1), dtype=torch.int32, device=dev)
-        offsets = torch.empty_like(counts)
-        ws = _scan_ws(cells, dev)
-        _check(load().vfn_tsdf_count(*vol, _ptr(counts, "counts", torch.int32), _ptr(offsets, "offsets", torch.int32),
-                                     _ptr(info, "info", torch.int64), _ptr(ws, "scan_ws", torch.uint8), C.c_int64(ws.numel()), _stream()),
-               "vfn_tsdf_count")
-        n_tri = int(info[0].cpu())
-        n_slots = 3 * n_tri
-        if n_tri < 0 or n_slots >= (1 << 31):
-            raise VfnError(f"TSDF extraction: {n_tri} triangles exceed the 2^31 / 3 limit")
-        if n_tri == 0:
-            return torch.empty(0, 3, dtype=torch.float64, device=dev), torch.empty(0, 3, dtype=torch.int64, device=dev)
-        tri_verts = torch.empty(n_slots, 3, dtype=torch.float64, device=dev)
-        _check(load().vfn_tsdf_emit(*vol, *box, _ptr(counts, "counts", torch.int32), _ptr(offsets, "offsets", torch.int32),
-                                    _ptr(tri_verts, "tri_verts", torch.float64), _stream()), "vfn_tsdf_emit")
-        vertices, ids = mesh_dedup(tri_verts, info=info)
-    return vertices, ids.view(n_tri, 3)
+    return _extract(lambda *out: _check(load().vfn_tsdf_count(*vol, *out), "vfn_tsdf_count"),
+                    lambda *out: _check(load().vfn_tsdf_emit(*vol, *box, *out), "vfn_tsdf_emit"),
+                    (nx - 1) * (ny - 1) * (nz - 1), tsdf.device, "TSDF extraction")
 
 
 # ------------------------------------------------------------------------------------------------
 # depth rasteriser and Laplacian smoothing (csrc/vfn_raster.hip; vf_nerf_amd/raster.py and refuse.py are the public surface)
 # ------------------------------------------------------------------------------------------------
-RASTER_STATUS_NONFINITE, RASTER_STATUS_INDEX = 1, 2
-
-
 def raster_depth(vertices: torch.Tensor, faces: torch.Tensor, intrinsics: torch.Tensor, extrinsics: torch.Tensor, height: int, width: int,
                  near: float, far: float, pixel_centre: float):
     """vertices[n,3] float64, faces[m,3] int64, intrinsics[V,4] = fx fy cx cy, extrinsics[V,12] (float32) -> (depth[V,H,W] float32,
@@ -1530,9 +1519,9 @@ def raster_depth(vertices: torch.Tensor, faces: torch.Tensor, intrinsics: torch.
                                        C.c_float(float(far)), C.c_float(float(pixel_centre)), _ptr(depth, "depth"),
                                        _ptr(info, "info", torch.int64), _stream()), "vfn_raster_depth")
         status, fragments, atomics, cooperative = (int(x) for x in info.cpu()) if v else (0, 0, 0, 0)
-    if status & RASTER_STATUS_INDEX:
+    if status & GEOM_STATUS_INDEX:
         raise VfnError(f"depth rasteriser: a face index lies outside [0, {nv})")
-    if status & RASTER_STATUS_NONFINITE:
+    if status & GEOM_STATUS_NONFINITE:
         raise VfnError("depth rasteriser: a non-finite vertex coordinate")
     return depth, {"fragments": fragments, "atomics": atomics, "cooperative": cooperative}
 

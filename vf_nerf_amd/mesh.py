@@ -20,34 +20,11 @@ from __future__ import annotations
 
 from typing import NamedTuple, Optional
 
-import numpy as np
 import torch
 
-from . import grid, lib
+from . import geomargs, grid, lib
 
 N_COMBS = 28
-
-
-def _device(device) -> torch.device:
-    if device is not None:
-        return torch.device(device)
-    if not torch.cuda.is_available():
-        raise lib.VfnError("mesh triangulation runs on the device (no CPU fallback) and no GPU is visible")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _as_tensor(x, name: str) -> torch.Tensor:
-    if isinstance(x, torch.Tensor):
-        return x.detach()
-    if isinstance(x, np.ndarray):
-        return torch.from_numpy(np.ascontiguousarray(x))
-    raise TypeError(f"{name}: expected a numpy array or a torch tensor, got {type(x).__name__}")
-
-
-def _check_res(res) -> int:
-    if isinstance(res, bool) or not isinstance(res, (int, np.integer)) or int(res) < 1:
-        raise ValueError(f"res must be a positive integer, got {res!r}")
-    return int(res)
 
 
 def _check_even(res: int) -> None:
@@ -61,12 +38,12 @@ def triangulate(comb_values, isovalue: float = 0.0, res: int = 100, size: float 
     res^3 cells (``udf`` may then be None: corner values 0 / 1).  fp32 inputs stay fp32 on the device (the kernel widens them exactly);
     any other dtype is converted to float64 (exact for the integer / fp16 / bool tables the reference accepts).
     -> (vertices float64 [V,3], faces int64 [F,3], 0-based), on the device."""
-    res = _check_res(res)
-    comb = _as_tensor(comb_values, "comb_values")
-    u = None if udf is None else _as_tensor(udf, "udf")
+    res = geomargs.positive_int(res, "res")
+    comb = geomargs.as_tensor(comb_values, "comb_values")
+    u = None if udf is None else geomargs.as_tensor(udf, "udf")
     cells = None
     if selected_indices is not None:
-        cells = _as_tensor(selected_indices, "selected_indices")
+        cells = geomargs.as_tensor(selected_indices, "selected_indices")
         if cells.dim() != 2 or cells.shape[1] != 3:
             raise ValueError(f"selected_indices must be [M,3], got {tuple(cells.shape)}")
         if cells.dtype.is_floating_point or cells.dtype == torch.bool:
@@ -81,9 +58,9 @@ def triangulate(comb_values, isovalue: float = 0.0, res: int = 100, size: float 
         raise ValueError(f"comb_values has {comb.numel()} values, expected {m} cells x {N_COMBS}")
     if u is not None and u.numel() != m * N_COMBS * 2:
         raise ValueError(f"udf has {u.numel()} values, expected {m} cells x {N_COMBS} x 2")
-    if m >= (1 << 31):
+    if m >= geomargs.LIMIT:
         raise ValueError(f"{m} cells exceed the 2^31 limit of one call")
-    dev = _device(device)
+    dev = geomargs.device(device, "mesh triangulation")
     dt = torch.float32 if comb.dtype == torch.float32 and (u is None or u.dtype == torch.float32) else torch.float64
     comb = comb.reshape(m, N_COMBS).to(dev, dt).contiguous()
     if u is not None:
@@ -91,7 +68,7 @@ def triangulate(comb_values, isovalue: float = 0.0, res: int = 100, size: float 
     if cells is not None:
         cells = cells.to(dev, torch.int64).contiguous()
     if m == 0:
-        return torch.empty(0, 3, dtype=torch.float64, device=dev), torch.empty(0, 3, dtype=torch.int64, device=dev)
+        return geomargs.empty_mesh(dev)
     return lib.mesh_triangulate(lib.MESH_GENERAL, m, res, float(size), float(isovalue), comb=comb, udf=u, cells=cells, device=dev)
 
 
@@ -128,7 +105,7 @@ class FieldStages(NamedTuple):
 def field_stages(prediction: torch.Tensor, resolution: int, smooth_after: bool = False, smooth_all: bool = False) -> FieldStages:
     """evaluation/methods.py:212-255 on the device, up to the side bytes: smoothing (k=3 if smooth_all), divergence, smoothing (k=9 if
     smooth_after or smooth_all), norms + normalised field, side bytes."""
-    res = _check_res(resolution)
+    res = geomargs.positive_int(resolution, "resolution")
     _check_even(res)
     pred = _dev_field(prediction, res)
     if smooth_all:
@@ -144,7 +121,7 @@ def field_stages(prediction: torch.Tensor, resolution: int, smooth_after: bool =
 def field_to_mesh(prediction: torch.Tensor, resolution: int, smooth_after: bool = False, smooth_all: bool = False):
     """Device field [res^3,3] -> (vertices float64 [V,3], faces int64 [F,3], 0-based): evaluation/methods.py:212-290 in the reference's
     order, the triangulation in its FUSED form (side bytes + norms).  Refuses a non-finite norm anywhere in the grid."""
-    res = _check_res(resolution)
+    res = geomargs.positive_int(resolution, "resolution")
     st = field_stages(prediction, res, smooth_after=smooth_after, smooth_all=smooth_all)
     return lib.mesh_triangulate(lib.MESH_FUSED, res ** 3, res, 2.0, 0.0, sides=st.sides, norms=st.norms)
 
@@ -177,11 +154,11 @@ def extract_mesh(decoder, resolution: int, scale: float = 1.0, translation=0, ce
     regenerated on the device from its axis tables (no res^3 host grid), the queries stay device-resident.  ``vertices_scaled`` is
     what the PLY's f4 vertices become after ``apply_scale`` / ``apply_translation(translation)`` / ``apply_translation(centroid)``
     (:314-316); trimesh's vertex merging is not reproduced."""
-    res = _check_res(resolution)
+    res = geomargs.positive_int(resolution, "resolution")
     _check_even(res)
     if res < 2:
         raise ValueError("resolution must be >= 2")
-    dev = _device(device)
+    dev = geomargs.device(device, "mesh triangulation")
     axes = tuple(a.to(dev) for a in lattice_axes(res, scale, translation, centroid))
     n = res ** 3
     pred = torch.empty(n, 3, device=dev)

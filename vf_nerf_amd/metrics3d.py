@@ -22,37 +22,24 @@ numpy's: a sampled point set is distributed as trimesh's, it is not the same set
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import lib
-from .mesh import Mesh
+from . import geomargs, lib
+from .geomargs import LIMIT
 
-LIMIT = 1 << 31
-
-
-def _device(device=None) -> torch.device:
-    if device is not None:
-        return torch.device(device)
-    if not torch.cuda.is_available():
-        raise lib.VfnError("mesh scoring runs on the device (no CPU fallback) and no GPU is visible")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _as_tensor(x, name: str) -> torch.Tensor:
-    if isinstance(x, torch.Tensor):
-        return x.detach()
-    if isinstance(x, np.ndarray):
-        return torch.from_numpy(np.ascontiguousarray(x))
-    raise TypeError(f"{name}: expected a numpy array or a torch tensor, got {type(x).__name__}")
+# this unit's forms of the shared checks (module attributes, so a test can stand in for the device)
+_device = functools.partial(geomargs.device, what="mesh scoring")
+_check_mesh = functools.partial(geomargs.check_mesh, allow_empty=False)          # nothing can be sampled on an empty mesh
 
 
 def _check_points(x, name: str) -> torch.Tensor:
     """Shape / dtype / size checks on the host tensor, before any device call."""
-    t = _as_tensor(x, name)
+    t = geomargs.as_tensor(x, name)
     if t.dim() != 2 or t.shape[1] != 3:
         raise ValueError(f"{name} must be [n,3], got {tuple(t.shape)}")
     if not (t.dtype.is_floating_point or t.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)):
@@ -62,40 +49,6 @@ def _check_points(x, name: str) -> torch.Tensor:
     if t.shape[0] >= LIMIT:
         raise ValueError(f"{name}: {t.shape[0]} rows exceed the 2^31 limit of one call")
     return t
-
-
-def _check_mesh(m, name: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    if isinstance(m, Mesh):
-        vertices, faces = m.vertices_scaled, m.faces
-    elif isinstance(m, (tuple, list)) and len(m) == 2:
-        vertices, faces = m
-    else:
-        raise TypeError(f"{name}: expected a mesh.Mesh or a (vertices, faces) pair, got {type(m).__name__}")
-    v = _as_tensor(vertices, f"{name} vertices")
-    f = _as_tensor(faces, f"{name} faces")
-    if v.dim() != 2 or v.shape[1] != 3:
-        raise ValueError(f"{name} vertices must be [V,3], got {tuple(v.shape)}")
-    if not v.dtype.is_floating_point:
-        raise ValueError(f"{name} vertices must be floating point, got {v.dtype}")
-    if f.dim() != 2 or f.shape[1] != 3:
-        raise ValueError(f"{name} faces must be [F,3], got {tuple(f.shape)}")
-    if f.dtype.is_floating_point or f.dtype in (torch.bool, torch.complex64, torch.complex128):
-        raise ValueError(f"{name} faces must be integers, got {f.dtype}")
-    if f.shape[0] < 1:
-        raise ValueError(f"{name} has no faces")
-    if v.shape[0] < 1:
-        raise ValueError(f"{name} has no vertices")
-    if v.shape[0] >= LIMIT or f.shape[0] >= LIMIT:
-        raise ValueError(f"{name}: {v.shape[0]} vertices / {f.shape[0]} faces exceed the 2^31 limit")
-    return v, f
-
-
-def _check_count(count, name: str = "count") -> int:
-    if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or int(count) < 1:
-        raise ValueError(f"{name} must be a positive integer, got {count!r}")
-    if int(count) >= LIMIT:
-        raise ValueError(f"{name} {count} exceeds the 2^31 limit of one call")
-    return int(count)
 
 
 def _check_threshold(threshold) -> float:
@@ -131,10 +84,10 @@ def sample_surface(vertices, faces, count: int, generator: Optional[torch.Genera
     ([count,3] in [0,1)) replaces the device's own random numbers; otherwise they come from ``generator`` (a device generator, or the
     device's default one).  ValueError on no faces, on zero total area and on count < 1."""
     v, f = _check_mesh((vertices, faces), "mesh")
-    count = _check_count(count)
+    count = geomargs.positive_int(count, "count")
     u = None
     if uniforms is not None:
-        u = _as_tensor(uniforms, "uniforms")
+        u = geomargs.as_tensor(uniforms, "uniforms")
         if tuple(u.shape) != (count, 3) or not u.dtype.is_floating_point:
             raise ValueError(f"uniforms must be floating point [{count},3], got {u.dtype} {tuple(u.shape)}")
     dev = _device(device)
@@ -222,7 +175,7 @@ def chamfer_distance(pred_mesh, ref_mesh, num_points: int = 2500000, generator: 
     ``chamfer_from_points``."""
     pv, pf = _check_mesh(pred_mesh, "pred_mesh")
     rv, rf = _check_mesh(ref_mesh, "ref_mesh")
-    num_points = _check_count(num_points, "num_points")
+    num_points = geomargs.positive_int(num_points, "num_points")
     pred_points, _ = sample_surface(pv, pf, num_points, generator=generator, device=device)
     ref_points, _ = sample_surface(rv, rf, num_points, generator=generator, device=device)
     return chamfer_from_points(pred_points, ref_points, device=device)
@@ -246,7 +199,7 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
     by both metrics.  ``uniforms`` ([num_points,3]) is used for BOTH meshes when given."""
     pv, pf = _check_mesh(pred_mesh, "pred_mesh")
     rv, rf = _check_mesh(ref_mesh, "ref_mesh")
-    num_points = _check_count(num_points, "num_points")
+    num_points = geomargs.positive_int(num_points, "num_points")
     threshold = _check_threshold(distance_thresh)
     pred_points, _ = sample_surface(pv, pf, num_points, generator=generator, uniforms=uniforms, device=device)
     ref_points, _ = sample_surface(rv, rf, num_points, generator=generator, uniforms=uniforms, device=device)

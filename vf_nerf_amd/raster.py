@@ -20,76 +20,29 @@ shared or per view) and camera-to-world poses ([V,4,4]; +z forward, x right, y d
 """
 from __future__ import annotations
 
-import math
 from typing import Tuple
 
-import numpy as np
 import torch
 
-from . import lib
-from .mesh import Mesh
-from .tsdf import _as_tensor, extrinsics_from_poses, split_intrinsics
+from . import geomargs, lib
+from .geomargs import LIMIT
+from .tsdf import extrinsics_from_poses, split_intrinsics
 
-LIMIT = 1 << 31
 NEAR, FAR, PIXEL_CENTRE = 0.05, 100.0, 0.5
 
 
-def _device(device=None) -> torch.device:
-    if device is not None:
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise lib.VfnError(f"the depth rasteriser runs on the device (no CPU fallback), got device {dev}")
-        return dev
-    if not torch.cuda.is_available():
-        raise lib.VfnError("the depth rasteriser runs on the device (no CPU fallback) and no GPU is visible")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def check_mesh(m, name: str = "mesh") -> Tuple[torch.Tensor, torch.Tensor]:
-    """-> (vertices, faces) as given (any device), shapes and dtypes checked; an empty face or vertex array is a mesh (of nothing)."""
-    if isinstance(m, Mesh):
-        vertices, faces = m.vertices_scaled, m.faces
-    elif isinstance(m, (tuple, list)) and len(m) == 2:
-        vertices, faces = m
-    else:
-        raise TypeError(f"{name}: expected a mesh.Mesh or a (vertices, faces) pair, got {type(m).__name__}")
-    v, f = _as_tensor(vertices, f"{name} vertices"), _as_tensor(faces, f"{name} faces")
-    if v.dim() != 2 or v.shape[1] != 3 or not v.dtype.is_floating_point:
-        raise ValueError(f"{name} vertices must be floating point [n,3], got {v.dtype} {tuple(v.shape)}")
-    if f.dim() != 2 or f.shape[1] != 3 or f.dtype.is_floating_point or f.dtype in (torch.bool, torch.complex64, torch.complex128):
-        raise ValueError(f"{name} faces must be integers [m,3], got {f.dtype} {tuple(f.shape)}")
-    if v.shape[0] >= LIMIT or f.shape[0] >= LIMIT:
-        raise ValueError(f"{name}: {v.shape[0]} vertices / {f.shape[0]} faces exceed the 2^31 limit")
-    return v, f
-
-
-def _size(x, name: str) -> int:
-    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or int(x) < 1:
-        raise ValueError(f"{name} must be a positive integer, got {x!r}")
-    return int(x)
-
-
-def _real32(x, name: str) -> float:
-    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not math.isfinite(float(x)):
-        raise ValueError(f"{name} must be a finite number, got {x!r}")
-    f = float(np.float32(x))
-    if not math.isfinite(f):
-        raise ValueError(f"{name} = {x!r} is not a finite float32")
-    return f
-
-
 def check_view_args(n_views: int, height, width, near, far, pixel_centre) -> Tuple[int, int, float, float, float]:
-    h, w = _size(height, "height"), _size(width, "width")
+    h, w = geomargs.positive_int(height, "height"), geomargs.positive_int(width, "width")
     if n_views * h * w >= LIMIT:
         raise ValueError(f"{n_views} views of {h} x {w} pixels reach the 2^31 limit of one call")
-    near, far, c = _real32(near, "near"), _real32(far, "far"), _real32(pixel_centre, "pixel_centre")
+    near, far, c = geomargs.real32(near, "near"), geomargs.real32(far, "far"), geomargs.real32(pixel_centre, "pixel_centre")
     if not (0.0 < near < far):
         raise ValueError(f"need 0 < near < far as float32, got near {near!r} and far {far!r}")
     return h, w, near, far, c
 
 
 def _n_views(poses) -> int:
-    p = _as_tensor(poses, "poses")
+    p = geomargs.as_tensor(poses, "poses")
     if p.dim() == 2:
         return 1
     if p.dim() != 3:
@@ -101,12 +54,13 @@ def rasterize_depth_counted(mesh, intrinsics, poses, height: int, width: int, ne
                             pixel_centre: float = PIXEL_CENTRE, device=None):
     """``rasterize_depth`` with the kernel's counters: -> (depth, {"fragments": kept (face, pixel) candidates, "atomics": atomics sent,
     "cooperative": (face, view) pairs walked by a whole wave})."""
-    v, f = check_mesh(mesh)
+    v, f = geomargs.check_mesh(mesh)
     n = _n_views(poses)
     k = split_intrinsics(intrinsics, n)
     e = extrinsics_from_poses(poses, n)
     h, w, near, far, c = check_view_args(n, height, width, near, far, pixel_centre)
-    dev = _device(device if device is not None else (v.device if v.is_cuda else None))        # every refusal above needs no device
+    # (every refusal above needs no device)
+    dev = geomargs.device(device if device is not None else (v.device if v.is_cuda else None), "the depth rasteriser")
     if n == 0 or f.shape[0] == 0:
         return torch.zeros(n, h, w, dtype=torch.float32, device=dev), {"fragments": 0, "atomics": 0, "cooperative": 0}
     return lib.raster_depth(v.to(dev, torch.float64).contiguous(), f.to(dev, torch.int64).contiguous(), k.to(dev), e.to(dev), h, w, near, far, c)

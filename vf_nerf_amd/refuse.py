@@ -24,7 +24,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from . import lib, metrics3d, raster, tsdf
+from . import geomargs, lib, metrics3d, raster, tsdf
 
 DEPTH_TRUNC = 5.0                  # evaluation/methods.py:62
 ITERATIONS, LAM = 10, 0.5
@@ -39,9 +39,9 @@ def refuse(mesh, intrinsics, poses, height: int, width: int, bounds=None, voxel_
     sees anything."""
     if isinstance(depth_trunc, bool) or not isinstance(depth_trunc, (int, float, np.integer, np.floating)) or not float(depth_trunc) > 0:
         raise ValueError(f"depth_trunc must be a positive number, got {depth_trunc!r}")
-    vl, _ = tsdf._positive(voxel_length, "voxel_length"), tsdf._positive(sdf_trunc, "sdf_trunc")
+    vl, _ = geomargs.positive32(voxel_length, "voxel_length"), geomargs.positive32(sdf_trunc, "sdf_trunc")
     if bounds is not None:
-        tsdf._box(bounds, vl)                                              # every refusal that needs no device comes before the first launch
+        tsdf.bounds_box(bounds, vl)                                        # every refusal that needs no device comes before the first launch
     depth = raster.rasterize_depth_counted(mesh, intrinsics, poses, height, width, near=near, far=far, pixel_centre=pixel_centre, device=device)[0]
     depth = torch.where(depth >= float(depth_trunc), torch.zeros_like(depth), depth)
     return tsdf.fuse_depth_maps(depth, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depth.device)
@@ -63,12 +63,12 @@ def vertex_adjacency(faces: torch.Tensor, n_vertices: int) -> Tuple[torch.Tensor
 def smooth_laplacian(mesh, iterations: int = ITERATIONS, lam: float = LAM, device=None):
     """``iterations`` Jacobi steps of uniform Laplacian smoothing -> (vertices, faces) on the device; the faces are the input's.  A vertex
     that no face uses (or only degenerate ones) stays where it is."""
-    v, f = raster.check_mesh(mesh)
+    v, f = geomargs.check_mesh(mesh)
     if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 0:
         raise ValueError(f"iterations must be a non-negative integer, got {iterations!r}")
     if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)) or not math.isfinite(float(lam)):
         raise ValueError(f"lam must be a finite number, got {lam!r}")
-    dev = raster._device(device if device is not None else (v.device if v.is_cuda else None))
+    dev = geomargs.device(device if device is not None else (v.device if v.is_cuda else None), "Laplacian smoothing")
     v, f = v.to(dev, torch.float64).contiguous(), f.to(dev, torch.int64).contiguous()
     n = v.shape[0]
     if f.numel() and (int(f.min()) < 0 or int(f.max()) >= n):
@@ -84,7 +84,7 @@ def reconstruction_meshes(tsdf_mesh, intrinsics, poses, height: int, width: int,
     ``refuse`` (bounds, voxel_length, sdf_trunc, depth_trunc, near, far, pixel_centre, device)."""
     smoothed = smooth_laplacian(tsdf_mesh, iterations=iterations, lam=lam, device=refuse_args.get("device"))
     dev = smoothed[0].device
-    v, f = raster.check_mesh(tsdf_mesh)
+    v, f = geomargs.check_mesh(tsdf_mesh)
     plain = (v.to(dev, torch.float64).contiguous(), smoothed[1])
     return {"tsdf": plain, "tsdf_smoothed": smoothed,
             "refused_tsdf": refuse(plain, intrinsics, poses, height, width, **refuse_args),

@@ -31,40 +31,12 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import lib
+from . import geomargs, lib
+from .geomargs import LIMIT
 
-LIMIT = 1 << 31
 VOXEL_LENGTH = 4.0 / 512.0        # evaluation/methods.py:624
 SDF_TRUNC = 0.04                  # :625
 DEPTH_SCALE, DEPTH_TRUNC = 1000.0, 10.0
-
-
-def _device(device=None) -> torch.device:
-    if device is not None:
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise lib.VfnError(f"TSDF fusion runs on the device (no CPU fallback), got device {dev}")
-        return dev
-    if not torch.cuda.is_available():
-        raise lib.VfnError("TSDF fusion runs on the device (no CPU fallback) and no GPU is visible")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _as_tensor(x, name: str) -> torch.Tensor:
-    if isinstance(x, torch.Tensor):
-        return x.detach()
-    if isinstance(x, np.ndarray):
-        return torch.from_numpy(np.ascontiguousarray(x))
-    raise TypeError(f"{name}: expected a numpy array or a torch tensor, got {type(x).__name__}")
-
-
-def _positive(x, name: str) -> float:
-    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not math.isfinite(float(x)) or float(x) <= 0:
-        raise ValueError(f"{name} must be a positive finite number, got {x!r}")
-    f = float(np.float32(x))
-    if not (f > 0 and math.isfinite(f)):
-        raise ValueError(f"{name} = {x!r} is not a positive float32")
-    return f
 
 
 def _check_dims(dims) -> Tuple[int, int, int]:
@@ -86,11 +58,11 @@ def _check_depth_values(d: torch.Tensor, name: str) -> None:
 def split_intrinsics(intrinsics, n_views: int) -> torch.Tensor:
     """[3,3] / [4,4] shared or [V,3,3] / [V,4,4] per view -> float32 [V,4] = fx fy cx cy (host).  Skew is refused: the projection of
     include/vfn.h has none."""
-    k = _as_tensor(intrinsics, "intrinsics").cpu()
+    k = geomargs.as_tensor(intrinsics, "intrinsics").cpu()
     if k.dim() == 2:
         k = k.unsqueeze(0).expand(n_views, -1, -1)
     if k.dim() != 3 or k.shape[0] != n_views or tuple(k.shape[1:]) not in ((3, 3), (4, 4)):
-        raise ValueError(f"intrinsics must be [3,3], [4,4] or one of those per view ({n_views}), got {tuple(_as_tensor(intrinsics, 'intrinsics').shape)}")
+        raise ValueError(f"intrinsics must be [3,3], [4,4] or one of those per view ({n_views}), got {tuple(geomargs.as_tensor(intrinsics, 'intrinsics').shape)}")
     k = k.to(torch.float32)
     out = torch.stack([k[:, 0, 0], k[:, 1, 1], k[:, 0, 2], k[:, 1, 2]], dim=1).contiguous()
     if not bool(torch.isfinite(out).all()) or not bool((out[:, :2] > 0).all()):
@@ -102,11 +74,11 @@ def split_intrinsics(intrinsics, n_views: int) -> torch.Tensor:
 
 def extrinsics_from_poses(poses, n_views: int) -> torch.Tensor:
     """Camera-to-world poses [4,4] / [V,4,4] -> float32 [V,12]: the first three rows of float32(inv(float64 pose)) (host)."""
-    p = _as_tensor(poses, "pose").cpu()
+    p = geomargs.as_tensor(poses, "pose").cpu()
     if p.dim() == 2:
         p = p.unsqueeze(0)
     if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4) or p.shape[0] != n_views:
-        raise ValueError(f"poses must be [4,4] per view ({n_views}), got {tuple(_as_tensor(poses, 'pose').shape)}")
+        raise ValueError(f"poses must be [4,4] per view ({n_views}), got {tuple(geomargs.as_tensor(poses, 'pose').shape)}")
     p64 = p.to(torch.float64).numpy()
     if not np.isfinite(p64).all():
         raise ValueError("a pose holds non-finite values")
@@ -124,13 +96,13 @@ def extrinsics_from_poses(poses, n_views: int) -> torch.Tensor:
 
 
 def _stack_depths(depth, name: str = "depth") -> torch.Tensor:
-    d = _as_tensor(depth, name)
+    d = geomargs.as_tensor(depth, name)
     if d.dim() == 2:
         d = d.unsqueeze(0)
     if d.dim() == 4 and d.shape[-1] == 1:
         d = d[..., 0]
     if d.dim() != 3 or d.shape[1] < 1 or d.shape[2] < 1:
-        raise ValueError(f"{name} must be [H,W] or [V,H,W], got {tuple(_as_tensor(depth, name).shape)}")
+        raise ValueError(f"{name} must be [H,W] or [V,H,W], got {tuple(geomargs.as_tensor(depth, name).shape)}")
     if not d.dtype.is_floating_point:
         raise ValueError(f"{name} must be floating point (metres), got {d.dtype}")
     if d.shape[1] * d.shape[2] >= LIMIT:
@@ -143,7 +115,7 @@ def reference_depth(depth_map, depth_scale: float = DEPTH_SCALE, depth_trunc: fl
     uint16, d = float32(q) / float32(depth_scale), d = 0 where d >= depth_trunc.  Non-finite, negative or >= 65.536 m (at the default
     scale: anything whose q leaves uint16) inputs are refused — NumPy's out-of-range cast is undefined and not inherited.  Stays on
     the input's device."""
-    d = _as_tensor(depth_map, "depth_map")
+    d = geomargs.as_tensor(depth_map, "depth_map")
     if not d.dtype.is_floating_point:
         raise ValueError(f"depth_map must be floating point (metres), got {d.dtype}")
     _check_depth_values(d, "depth_map")
@@ -161,13 +133,13 @@ class TSDFVolume:
 
     def __init__(self, origin, dims, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC, device=None):
         self.dims = _check_dims(dims)
-        self.voxel_length = _positive(voxel_length, "voxel_length")
-        self.sdf_trunc = _positive(sdf_trunc, "sdf_trunc")
+        self.voxel_length = geomargs.positive32(voxel_length, "voxel_length")
+        self.sdf_trunc = geomargs.positive32(sdf_trunc, "sdf_trunc")
         o = np.asarray(origin.detach().cpu() if isinstance(origin, torch.Tensor) else origin, dtype=np.float64).reshape(-1)
         if o.shape != (3,) or not np.isfinite(o.astype(np.float32)).all():
             raise ValueError(f"origin must be three finite numbers, got {origin!r}")
         self.origin = tuple(float(x) for x in o.astype(np.float32))
-        self.device = _device(device)
+        self.device = geomargs.device(device, "TSDF fusion")
         self.tsdf = torch.zeros(self.dims, dtype=torch.float32, device=self.device)
         self.weight = torch.zeros(self.dims, dtype=torch.float32, device=self.device)
 
@@ -216,7 +188,7 @@ def depth_bounds(depths: torch.Tensor, k: torch.Tensor, poses: torch.Tensor) -> 
     return lo.cpu(), hi.cpu()
 
 
-def _box(bounds, vl: float):
+def bounds_box(bounds, vl: float):
     """(min[3], max[3]) -> (origin float64 [3], dims): ceil(extent / voxel_length) voxels per axis, at least one."""
     if len(bounds) != 2:
         raise ValueError("bounds must be (min[3], max[3])")
@@ -229,25 +201,28 @@ def _box(bounds, vl: float):
     return lo, _check_dims(tuple(max(1, int(math.ceil(float(x)))) for x in extent))
 
 
+_box = bounds_box          # (the name before it became public)
+
+
 def fuse_depth_maps(depths, intrinsics, poses, bounds=None, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC, device=None):
     """Depth maps [V,H,W] (or one [H,W]) with their cameras -> (vertices, faces): one volume, one integration pass, one extraction.
     ``bounds`` = (min[3], max[3]) of the box; None: the min / max of the back-projected valid depth points, padded by ``sdf_trunc``.
     The box is covered by ceil(extent / voxel_length) voxels per axis (at least one)."""
-    vl, tr = _positive(voxel_length, "voxel_length"), _positive(sdf_trunc, "sdf_trunc")
+    vl, tr = geomargs.positive32(voxel_length, "voxel_length"), geomargs.positive32(sdf_trunc, "sdf_trunc")
     d = _stack_depths(depths, "depths")
     v = d.shape[0]
     k = split_intrinsics(intrinsics, v)
     e = extrinsics_from_poses(poses, v)
     _check_depth_values(d, "depths")                           # (on whatever device the maps live)
-    box = None if bounds is None else _box(bounds, vl)         # every refusal that needs no device comes before the device is asked for
-    dev = _device(device if device is not None else (d.device if d.is_cuda else None))
+    box = None if bounds is None else bounds_box(bounds, vl)         # every refusal that needs no device comes before the device is asked for
+    dev = geomargs.device(device if device is not None else (d.device if d.is_cuda else None), "TSDF fusion")
     d = d.to(dev, torch.float32).contiguous()
     if box is None:
-        p = _as_tensor(poses, "poses").cpu()
+        p = geomargs.as_tensor(poses, "poses").cpu()
         found = depth_bounds(d, k, p.unsqueeze(0) if p.dim() == 2 else p)
         if found is None:
-            return torch.empty(0, 3, dtype=torch.float64, device=dev), torch.empty(0, 3, dtype=torch.int64, device=dev)
-        box = _box((found[0].numpy() - tr, found[1].numpy() + tr), vl)
+            return geomargs.empty_mesh(dev)
+        box = bounds_box((found[0].numpy() - tr, found[1].numpy() + tr), vl)
     vol = TSDFVolume(box[0], box[1], voxel_length=vl, sdf_trunc=tr, device=dev)
     lib.tsdf_integrate(vol.tsdf, vol.weight, vol.origin, vol.voxel_length, vol.sdf_trunc, d, k.to(dev), e.to(dev))
     return vol.extract_mesh()
@@ -259,12 +234,12 @@ def render_depth_maps(model, poses, intrinsics, height: int, width: int, epoch: 
     """Every pixel of every view rendered as ``evaluator.render_view`` renders it (``VectorFieldNerf.render_chunked`` with sparse
     colours, chunks of max(split_size, min_chunk) rays) -> depth maps [V,height,width] float32 that stay on the device."""
     from . import evaluator
-    p = _as_tensor(poses, "poses").to(torch.float32)
+    p = geomargs.as_tensor(poses, "poses").to(torch.float32)
     p = p.unsqueeze(0) if p.dim() == 2 else p
     if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4):
         raise ValueError(f"poses must be [V,4,4], got {tuple(p.shape)}")
     v = p.shape[0]
-    k = _as_tensor(intrinsics, "intrinsics").to(torch.float32)
+    k = geomargs.as_tensor(intrinsics, "intrinsics").to(torch.float32)
     if k.dim() == 2:
         k = k.unsqueeze(0).expand(v, -1, -1)
     if k.dim() != 3 or k.shape[0] != v or tuple(k.shape[1:]) not in ((3, 3), (4, 4)):
@@ -275,7 +250,7 @@ def render_depth_maps(model, poses, intrinsics, height: int, width: int, epoch: 
         k = k4
     if height < 1 or width < 1:
         raise ValueError(f"bad image size {height} x {width}")
-    dev = _device(getattr(model.config.cuda_config, "device", None))
+    dev = geomargs.device(getattr(model.config.cuda_config, "device", None), "TSDF fusion")
     vv, uu = torch.meshgrid(torch.arange(height, dtype=torch.float32), torch.arange(width, dtype=torch.float32), indexing="ij")
     uv = torch.stack([uu.reshape(-1), vv.reshape(-1)], dim=1).to(dev)
     chunk = max(int(split_size), int(evaluator.MIN_CHUNK if min_chunk is None else min_chunk))
