@@ -762,6 +762,55 @@ int64_t vfn_reduce_stats_workspace_bytes(int64_t n);
 int vfn_reduce_stats(const double* x, int64_t n, double threshold, double* stats, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* =============================================================================================
+ * Aligning two point sets (csrc/vfn_icp.hip): the device half of point-to-point ICP, the `icp_align` step of evaluation/methods.py:747-801
+ * that the reference leaves to an external package.  A SPECIFICATION, not a recording: neither Open3D nor that package publishes its
+ * arithmetic.  Everything is float64, evaluated without contraction in the association written here; no result depends on the order
+ * in which workgroups arrive.  `info` as above: zero-filled by the caller, bit 1 = a non-finite coordinate, bit 2 = an index outside
+ * [0, m).  1 <= n, m < 2^31.
+ *   A transform is 12 doubles in HOST memory, r00 r01 r02 r10 .. r22 (row-major) then t0 t1 t2; NULL is the identity and skips the
+ *   arithmetic (q' = q to the bit).  Otherwise q'x = ((r00 x + r01 y) + r02 z) + t0, q'y and q'z alike with rows 1 and 2.  The points
+ *   are transformed on the fly and never rewritten.  A non-finite entry is refused before any launch.
+ *   vfn_transform_points  out[n, 3] = q' for points[n, 3], one lane per point.
+ *   vfn_nn_radius     for every query i: among the targets j with d2(j) <= rr, where d2(j) = (dx dx + dy dy) + dz dz, dx = q'x - t_j.x,
+ *                     dy = q'y - t_j.y, dz = q'z - t_j.z and rr = radius radius (rounded once), the minimum of d2, ties to the LOWEST
+ *                     target index: index[i] = that j, sqdist[i] = its d2; no such target: index[i] = -1, sqdist[i] = +inf.  radius
+ *                     must be finite and > 0 with a normal square.  The definition does not mention a grid and the grid does not
+ *                     change a bit of the result; it only bounds the work.  The caller provides it: box[7] (HOST memory) = the
+ *                     targets' componentwise minimum o[3], their maximum e[3], the cell edge h >= radius (1 + 2^-20) with
+ *                     (e - o) / h <= 129 on every axis; nx, ny, nz in [1, VFN_ICP_GRID_CAP = 128] cells; with
+ *                       cell(x) = min(max(floor((min(max(x, o), e) - o) / h), 0), dim - 1)    per axis,
+ *                       key = (cell_x ny + cell_y) nz + cell_z,
+ *                     sorted_targets[m, 3] = the targets in ascending key order, perm[m] = their original indices (what `index`
+ *                     reports), cell_start[nx ny nz + 1] (int32) = the first sorted position of every key, cell_start[last] = m.
+ *                     The argument that the 27 cells around a query's cell hold every admissible target under this rounding is in
+ *                     csrc/vfn_icp.hip.  order[n] (may be NULL) is a permutation of the queries: lane k serves query order[k]
+ *                     (neighbouring lanes then read neighbouring cells); it changes no bit.  check_finite != 0: info[0] |= 1 when a
+ *                     coordinate of either set is not finite (the outputs are then meaningless); 0 skips that pass over the
+ *                     3 (n + m) coordinates — for a caller that searches the same two arrays again (the ICP loop checks once).
+ *   vfn_icp_accumulate  reads queries[n, 3], the transform, targets[m, 3] (ORIGINAL order), index[n], sqdist[n] and anchor[3] (HOST
+ *                     memory); writes sums[17] over the rows with index[i] >= 0, with p = q'_i - anchor and s = t_index[i] - anchor
+ *                     (each difference rounded once):
+ *                       sums[0] = the number of rows (exact), sums[1] = sum sqdist[i], sums[2 + a] = sum p_a, sums[5 + a] = sum s_a,
+ *                       sums[8 + 3 a + b] = sum p_a s_b (the product rounded once).
+ *                     The fixed two-level tree of vfn_reduce_stats, no floating-point atomics: block b joins the rows
+ *                     [4096 b, 4096 (b + 1)) — a lane's 16 rows as a balanced tree (4 levels), 256 lanes as a balanced tree (8 levels);
+ *                     one block of 1024 lanes joins the P = ceil(n / 4096) partials, a lane its partials l, l + 1024, ... serially,
+ *                     then a balanced tree (10 levels): every sum is 4 + 8 + (ceil(P / 1024) - 1) + 10 additions deep, a function of
+ *                     n alone.  Rows without a neighbour and rows past n join as the identity (+ 0.0).  An index >= m: info[0] |= 2,
+ *                     the row is skipped.  workspace: vfn_icp_accumulate_workspace_bytes(n) bytes (the partials); -1 on error.
+ * ============================================================================================= */
+#define VFN_ICP_GRID_CAP 128          /* cells per axis at most */
+#define VFN_ICP_GRID_MARGIN_LOG2 20   /* the cell edge is at least radius (1 + 2^-20) */
+int vfn_transform_points(const double* points, int64_t n, const double* transform, double* out, void* stream);
+int vfn_nn_radius(const double* queries, int64_t n, const double* transform, const double* sorted_targets, const int64_t* perm,
+                  int64_t m, const int32_t* cell_start, const double* box, int32_t nx, int32_t ny, int32_t nz, double radius,
+                  const int64_t* order, int32_t check_finite, int64_t* index, double* sqdist, int64_t* info, void* stream);
+int64_t vfn_icp_accumulate_workspace_bytes(int64_t n);
+int vfn_icp_accumulate(const double* queries, int64_t n, const double* transform, const double* targets, int64_t m,
+                       const int64_t* index, const double* sqdist, const double* anchor, double* sums, int64_t* info,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
+/* =============================================================================================
  * Fusing depth maps into a mesh (csrc/vfn_tsdf.hip): the stage of evaluation/methods.py:613-665 (tsdf_mesh) between the rendered depth
  * maps and the mesh that metrics_3d scores, with the semantics of a uniform TSDF volume — projective integration with a running mean,
  * classic marching cubes on the zero level set.  Two deliberate differences: the volume is DENSE over a box the caller gives (not

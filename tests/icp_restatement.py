@@ -1,0 +1,203 @@
+"""A CPU restatement of point-set alignment (vf_nerf_amd/icp.py, csrc/vfn_icp.hip), written from the contract of include/vfn.h in numpy
+float64: numpy's elementwise operations round every product and sum once, in the association written here, which is what the unit does
+without contraction.  The search is brute force over all pairs (no grid: the contract does not mention one), the sums are math.fsum
+over the terms of the contract, the rigid solve and the loop are this file's own.  tests/test_icp_host.py pins the search to scipy's
+cKDTree; the GPU tests then hold the device to this file.  Not part of the package: tests only."""
+from __future__ import annotations
+
+import math
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+SUMS = 17
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the shared input: the corner-room cloud and the motion M
+# ---------------------------------------------------------------------------------------------------------------------------------
+def corner_room(n: int, seed: int) -> np.ndarray:
+    """n points: a quarter on each of the rectangles [0,1]x[0,0.7]x{0}, [0,1]x{0}x[0,0.5], {0}x[0,0.7]x[0,0.5] (a floor and two walls
+    meeting in a corner), the rest on an ellipsoid with semi-axes (0.15, 0.105, 0.075) about (0.6, 0.4, 0.3); all shifted by
+    -(0.4, 0.3, 0.2).  Three planes with independent normals and a closed surface: every rigid motion is observable."""
+    g = np.random.default_rng(seed)
+    k = n // 4
+    floor = np.stack((g.uniform(0, 1, k), g.uniform(0, 0.7, k), np.zeros(k)), axis=1)
+    wall_y = np.stack((g.uniform(0, 1, k), np.zeros(k), g.uniform(0, 0.5, k)), axis=1)
+    wall_x = np.stack((np.zeros(k), g.uniform(0, 0.7, k), g.uniform(0, 0.5, k)), axis=1)
+    d = g.standard_normal((n - 3 * k, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    blob = d * np.array([0.15, 0.105, 0.075]) + np.array([0.6, 0.4, 0.3])
+    return np.concatenate((floor, wall_y, wall_x, blob)) - np.array([0.4, 0.3, 0.2])
+
+
+def rotation(axis, degrees: float) -> np.ndarray:
+    """Rodrigues' formula -> [3,3]."""
+    a = np.asarray(axis, dtype=np.float64)
+    a = a / np.linalg.norm(a)
+    k = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    th = math.radians(degrees)
+    return np.eye(3) + math.sin(th) * k + (1.0 - math.cos(th)) * (k @ k)
+
+
+def rigid(axis, degrees: float, translation) -> np.ndarray:
+    m = np.eye(4)
+    m[:3, :3] = rotation(axis, degrees)
+    m[:3, 3] = translation
+    return m
+
+
+def motion() -> np.ndarray:
+    """M: 5 degrees about (1, 2, 3) and a translation of 0.03 (1, -0.5, 0.7)."""
+    return rigid((1.0, 2.0, 3.0), 5.0, 0.03 * np.array([1.0, -0.5, 0.7]))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the contract
+# ---------------------------------------------------------------------------------------------------------------------------------
+def transform(points, t) -> np.ndarray:
+    """q'x = ((r00 x + r01 y) + r02 z) + t0, ...; t None: the points as they are."""
+    p = np.ascontiguousarray(points, dtype=np.float64)
+    if t is None:
+        return p
+    t = np.asarray(t, dtype=np.float64)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return np.stack([((t[a, 0] * x + t[a, 1] * y) + t[a, 2] * z) + t[a, 3] for a in range(3)], axis=1)
+
+
+def _nearest_rows(q, tx, ty, tz, rr, tile):
+    index, sqdist = np.full(q.shape[0], -1, dtype=np.int64), np.full(q.shape[0], np.inf)
+    qx, qy, qz = q[:, 0:1], q[:, 1:2], q[:, 2:3]
+    for lo in range(0, tx.shape[0], tile):
+        dx, dy, dz = qx - tx[lo:lo + tile], qy - ty[lo:lo + tile], qz - tz[lo:lo + tile]
+        d = (dx * dx + dy * dy) + dz * dz
+        d[~(d <= rr)] = np.inf
+        j = np.argmin(d, axis=1)
+        dj = d[np.arange(d.shape[0]), j]
+        take = dj < sqdist
+        index[take], sqdist[take] = j[take] + lo, dj[take]
+    return index, sqdist
+
+
+def nearest_within(queries, targets, radius: float, t=None, rows: int = 256, tile: int = 4096, workers: int = 1):
+    """-> (index int64 [n], sqdist [n]): over the targets with d2 <= fl(r r), d2 = (dx dx + dy dy) + dz dz on q', the minimum d2, ties to
+    the lowest index; none: -1, +inf.  All pairs, in tiles visited in ascending index (a later tile replaces only on a strictly smaller
+    d2, np.argmin returns the first minimum: the lowest index wins).  Neither the tiling nor the threads change a bit."""
+    q = transform(queries, t)
+    tg = np.ascontiguousarray(targets, dtype=np.float64)
+    rr = np.float64(radius) * np.float64(radius)
+    tx, ty, tz = (np.ascontiguousarray(tg[:, c]) for c in range(3))
+    chunks = [q[lo:lo + rows] for lo in range(0, q.shape[0], rows)]
+    if workers > 1:
+        with ThreadPoolExecutor(workers) as pool:          # numpy releases the GIL inside its loops
+            parts = list(pool.map(lambda c: _nearest_rows(c, tx, ty, tz, rr, tile), chunks))
+    else:
+        parts = [_nearest_rows(c, tx, ty, tz, rr, tile) for c in chunks]
+    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+
+def bounded(free_index, free_sqdist, radius: float):
+    """The search within ``radius`` from the unbounded one (a radius beyond every pair): the minimum over the admissible targets is the
+    minimum over all of them when that one is admissible, with the same lowest index; otherwise nothing is admissible."""
+    rr = np.float64(radius) * np.float64(radius)
+    ok = free_sqdist <= rr
+    return np.where(ok, free_index, -1), np.where(ok, free_sqdist, np.inf)
+
+
+def terms(queries, t, targets, index, sqdist, anchor) -> np.ndarray:
+    """The rows with a neighbour -> [k,17]: 1, d2, p = q' - a (3), s = target - a (3), p_a s_b (9), every difference and product
+    rounded once."""
+    index = np.asarray(index)
+    keep = index >= 0
+    a = np.asarray(anchor, dtype=np.float64)
+    p = transform(queries, t)[keep] - a
+    s = np.asarray(targets, dtype=np.float64)[index[keep]] - a
+    out = np.empty((int(keep.sum()), SUMS))
+    out[:, 0] = 1.0
+    out[:, 1] = np.asarray(sqdist, dtype=np.float64)[keep]
+    out[:, 2:5], out[:, 5:8] = p, s
+    for i in range(3):
+        for j in range(3):
+            out[:, 8 + 3 * i + j] = p[:, i] * s[:, j]
+    return out
+
+
+def sums_of(term_rows, how: str = "fsum") -> np.ndarray:
+    """Column sums of ``terms``: math.fsum (the exact sum rounded once) or numpy's own pairwise sum."""
+    if how == "fsum":
+        return np.array([math.fsum(term_rows[:, c].tolist()) for c in range(SUMS)])
+    return term_rows.sum(axis=0)
+
+
+def bounding_anchor(targets) -> np.ndarray:
+    tg = np.asarray(targets, dtype=np.float64)
+    return 0.5 * (tg.min(axis=0) + tg.max(axis=0))
+
+
+class SolveError(ValueError):
+    pass
+
+
+def solve(sums, anchor) -> np.ndarray:
+    """17 sums about the anchor -> the [4,4] rigid update (no scale) that minimises sum |R p + t - s|^2: the Kabsch solution."""
+    s = np.asarray(sums, dtype=np.float64)
+    a = np.asarray(anchor, dtype=np.float64)
+    c = s[0]
+    if c < 3:
+        raise SolveError("fewer than 3 pairs")
+    mp, ms = s[2:5] / c, s[5:8] / c
+    cov = s[8:17].reshape(3, 3) - c * mp[:, None] * ms[None, :]
+    u, w, vt = np.linalg.svd(cov)
+    if not w[1] > 1e-12 * w[0]:
+        raise SolveError("collinear pairs")
+    v = vt.T
+    flip = 1.0 if np.linalg.det(v @ u.T) > 0 else -1.0
+    r = v @ np.diag([1.0, 1.0, flip]) @ u.T
+    out = np.eye(4)
+    out[:3, :3] = r
+    out[:3, 3] = (ms + a) - r @ (mp + a)
+    return out
+
+
+def solve_pairs(p, s) -> np.ndarray:
+    """The same from two arrays of paired points (anchor = the centre of s's bounding box)."""
+    p, s = np.asarray(p, dtype=np.float64), np.asarray(s, dtype=np.float64)
+    a = bounding_anchor(s)
+    return solve(sums_of(terms(p, None, s, np.arange(len(p)), np.zeros(len(p)), a)), a)
+
+
+def step(source, t_k, targets, radius, anchor, how: str = "fsum", workers: int = 1):
+    """One iteration at T_k -> (index, sqdist, sums)."""
+    index, sqdist = nearest_within(source, targets, radius, t_k, workers=workers)
+    return index, sqdist, sums_of(terms(source, t_k, targets, index, sqdist, anchor), how)
+
+
+def stop_rule(history, relative_fitness, relative_rmse) -> bool:
+    """Both |fitness - previous| and |rmse - previous| below their criteria (never before the second entry)."""
+    if len(history) < 2:
+        return False
+    a, b = history[-2], history[-1]
+    return abs(b["fitness"] - a["fitness"]) < relative_fitness and abs(b["inlier_rmse"] - a["inlier_rmse"]) < relative_rmse
+
+
+def align(source, targets, radius, init=None, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6):
+    """-> dict(transformation, fitness, inlier_rmse, iterations, converged, history)."""
+    src, tg = np.asarray(source, dtype=np.float64), np.asarray(targets, dtype=np.float64)
+    a = bounding_anchor(tg)
+    t_k = np.eye(4) if init is None else np.array(init, dtype=np.float64)
+    history, updates, converged = [], 0, False
+    while True:
+        index, sqdist, s = step(src, t_k, tg, radius, a)
+        count = int(s[0])
+        entry = {"transformation": t_k.copy(), "count": count, "fitness": count / len(src),
+                 "inlier_rmse": math.sqrt(s[1] / count) if count else 0.0}
+        history.append(entry)
+        if stop_rule(history, relative_fitness, relative_rmse):
+            converged = True
+            break
+        if updates >= max_iteration:
+            break
+        t_k = solve(s, a) @ t_k
+        updates += 1
+    return {"transformation": t_k, "fitness": entry["fitness"], "inlier_rmse": entry["inlier_rmse"], "iterations": updates,
+            "converged": converged, "history": history}

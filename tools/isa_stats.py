@@ -20,7 +20,7 @@ root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function"]
 if unit in ("vfn_mlp16", "vfn_bwd16"):
     flags += ["-mllvm", "-amdgpu-mfma-vgpr-form", "-mllvm", "-pragma-unroll-threshold=10000000"]
-if unit in ("vfn_rays", "vfn_grid", "vfn_mesh", "vfn_metrics", "vfn_tsdf"):
+if unit in ("vfn_rays", "vfn_grid", "vfn_mesh", "vfn_metrics", "vfn_tsdf", "vfn_raster", "vfn_icp"):
     flags += ["-ffp-contract=off"]
 flags += os.environ.get("VFN_%s_EXTRA" % unit[4:].upper(), "").split()
 asm = f"/tmp/{unit}.isa.s"

@@ -24,6 +24,13 @@ static inline int vfn_check_launch(const char* what) {
     return VFN_OK;
 }
 
+// The squared distance of include/vfn.h (vfn_nn_sqdist, vfn_nn_radius): ONE definition, so that the two searches cannot drift apart —
+// their outputs are compared bit for bit.  Both units are compiled with -ffp-contract=off (build.sh).
+__device__ __forceinline__ double vfn_pair_sqdist(double qx, double qy, double qz, double tx, double ty, double tz) {
+    const double dx = qx - tx, dy = qy - ty, dz = qz - tz;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
 // launches shared between translation units, not part of the ABI (csrc/vfn_rays.hip, used by csrc/vfn_render.hip)
 int vfn_internal_raygen(const vfn_raygen_params* p, const float* uv, const float* pose, const float* intrinsics, const float* k_sign,
                         const float* t_vals, const float* far_per_ray, const float* u_coarse, int gen_u, long long u_base, uint64_t seed,

@@ -46,11 +46,6 @@ __global__ __launch_bounds__(256) void vfn_nn_prepare_kernel(const double* __res
     if (bad) atomicOr(info, 1ull);
 }
 
-__device__ __forceinline__ double pair_sqdist(double qx, double qy, double qz, double tx, double ty, double tz) {
-    const double dx = qx - tx, dy = qy - ty, dz = qz - tz;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
 // grid (query blocks, target slices); slice s covers targets [s slice_len, min((s + 1) slice_len, m)); slice_len is a multiple of NN_TB
 __global__ __launch_bounds__(NN_BLOCK) void vfn_nn_sqdist_kernel(const double* __restrict__ q, long long n, const double* __restrict__ t,
                                                                  long long m, long long slice_len, unsigned long long* __restrict__ best) {
@@ -74,12 +69,12 @@ __global__ __launch_bounds__(NN_BLOCK) void vfn_nn_sqdist_kernel(const double* _
 #pragma unroll
         for (int u = 0; u < NN_TB; ++u)
 #pragma unroll
-            for (int k = 0; k < NN_QPL; ++k) b[k] = fmin(b[k], pair_sqdist(qx[k], qy[k], qz[k], tv[3 * u], tv[3 * u + 1], tv[3 * u + 2]));
+            for (int k = 0; k < NN_QPL; ++k) b[k] = fmin(b[k], vfn_pair_sqdist(qx[k], qy[k], qz[k], tv[3 * u], tv[3 * u + 1], tv[3 * u + 2]));
     }
     for (; j < j1; ++j) {
         const double tx = t[3 * j], ty = t[3 * j + 1], tz = t[3 * j + 2];
 #pragma unroll
-        for (int k = 0; k < NN_QPL; ++k) b[k] = fmin(b[k], pair_sqdist(qx[k], qy[k], qz[k], tx, ty, tz));
+        for (int k = 0; k < NN_QPL; ++k) b[k] = fmin(b[k], vfn_pair_sqdist(qx[k], qy[k], qz[k], tx, ty, tz));
     }
 #pragma unroll
     for (int k = 0; k < NN_QPL; ++k) {

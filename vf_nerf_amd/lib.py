@@ -7,6 +7,7 @@ library binds to is the one PyTorch already loaded (same ``libamdhip64.so.7`` SO
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 from typing import List, Optional, Sequence
 
@@ -44,6 +45,7 @@ EXPORTS = (
     "vfn_reduce_stats_workspace_bytes", "vfn_reduce_stats",
     "vfn_tsdf_integrate", "vfn_tsdf_count", "vfn_tsdf_emit",
     "vfn_raster_depth", "vfn_smooth_laplacian_step",
+    "vfn_transform_points", "vfn_nn_radius", "vfn_icp_accumulate_workspace_bytes", "vfn_icp_accumulate",
 )
 
 
@@ -1440,6 +1442,98 @@ def reduce_sum_levels(n: int) -> int:
     level (ceil(P / 1024) - 1, P = ceil(n / 4096) partials) + 10 (1024 lanes)."""
     p = (n + REDUCE_TILE - 1) // REDUCE_TILE
     return 4 + 8 + ((p + REDUCE_TOP - 1) // REDUCE_TOP - 1) + 10
+
+
+# ------------------------------------------------------------------------------------------------
+# point-set alignment (csrc/vfn_icp.hip; vf_nerf_amd/icp.py is the public surface).  Everything float64, contiguous, on one device.
+# ------------------------------------------------------------------------------------------------
+ICP_SUMS = 17                      # count, sum d2, sum p[3], sum s[3], sum p s^T [9] (include/vfn.h: vfn_icp_accumulate)
+
+
+@functools.lru_cache(maxsize=None)
+def header_constant(name: str) -> int:
+    """An integer ``#define`` of include/vfn.h (the header is the single source the kernels are compiled from)."""
+    import re
+    return int(re.search(r"#define\s+" + name + r"\s+(\d+)", _header_raw()).group(1))
+
+
+def icp_grid_limits():
+    """-> (cells per axis at most, the least ratio of the cell edge to the radius): VFN_ICP_GRID_CAP, 1 + 2^-VFN_ICP_GRID_MARGIN_LOG2."""
+    return header_constant("VFN_ICP_GRID_CAP"), 1.0 + 2.0 ** -header_constant("VFN_ICP_GRID_MARGIN_LOG2")
+
+
+def _transform12(transform):
+    """None, or 12 Python floats (r00 .. r22 row-major, t0 t1 t2) -> the HOST pointer the entry points take."""
+    return None if transform is None else (C.c_double * 12)(*transform)
+
+
+def transform_points(points: torch.Tensor, transform=None) -> torch.Tensor:
+    """points[n,3] -> [n,3]: ((r00 x + r01 y) + r02 z) + t0, ... per point; ``transform`` None is the identity (a copy)."""
+    n = points.shape[0]
+    out = torch.empty(n, 3, dtype=torch.float64, device=points.device)
+    _check(load().vfn_transform_points(_ptr(points, "points", torch.float64), C.c_int64(n), _transform12(transform),
+                                       _ptr(out, "out", torch.float64), _stream()), "vfn_transform_points")
+    return out
+
+
+def nn_radius(queries: torch.Tensor, transform, grid, radius: float, order: Optional[torch.Tensor] = None,
+              info: Optional[torch.Tensor] = None, check_finite: bool = True):
+    """-> (index[n] int64, sqdist[n]) of every transformed query's nearest target within ``radius`` (-1 / +inf when there is none).
+    ``grid`` = (sorted_targets[m,3], perm[m] int64, cell_start[cells+1] int32, box: 7 floats, dims: 3 ints) as include/vfn.h describes.
+    ``info`` as in ``nn_sqdist``; ``check_finite=False`` skips the pass over the coordinates (a caller that has searched these two
+    arrays before)."""
+    sorted_targets, perm, cell_start, box, dims = grid
+    n, m = queries.shape[0], sorted_targets.shape[0]
+    if perm.shape[0] != m or cell_start.shape[0] != dims[0] * dims[1] * dims[2] + 1 or (order is not None and order.shape[0] != n):
+        raise VfnError("nn_radius: perm / cell_start / order do not have the lengths the grid and the queries give")
+    index = torch.empty(n, dtype=torch.int64, device=queries.device)
+    sqdist = torch.empty(n, dtype=torch.float64, device=queries.device)
+    own = info is None
+    if own:
+        info = torch.zeros(1, dtype=torch.int64, device=queries.device)
+    _check(load().vfn_nn_radius(_ptr(queries, "queries", torch.float64), C.c_int64(n), _transform12(transform),
+                                _ptr(sorted_targets, "sorted_targets", torch.float64), _ptr(perm, "perm", torch.int64), C.c_int64(m),
+                                _ptr(cell_start, "cell_start", torch.int32), (C.c_double * 7)(*box), C.c_int32(dims[0]), C.c_int32(dims[1]),
+                                C.c_int32(dims[2]), C.c_double(radius), _ptr(order, "order", torch.int64), C.c_int32(int(check_finite)),
+                                _ptr(index, "index", torch.int64),
+                                _ptr(sqdist, "sqdist", torch.float64), _ptr(info, "info", torch.int64), _stream()), "vfn_nn_radius")
+    if own:
+        nn_check(int(info.cpu()))
+    return index, sqdist
+
+
+def icp_accumulate(queries: torch.Tensor, transform, targets: torch.Tensor, index: torch.Tensor, sqdist: torch.Tensor, anchor,
+                   info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> sums[17] on the device over the rows with index >= 0 (include/vfn.h: vfn_icp_accumulate).  An index >= m raises — or, with
+    the caller's ``info``, sets GEOM_STATUS_INDEX in it (``icp_check``)."""
+    n, m = queries.shape[0], targets.shape[0]
+    if index.shape[0] != n or sqdist.shape[0] != n:
+        raise VfnError(f"icp_accumulate: index / sqdist must have the queries' {n} rows")
+    dev = queries.device
+    sums = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
+    ws = _bytes_ws("vfn_icp_accumulate_workspace_bytes", n, dev)
+    own = info is None
+    if own:
+        info = torch.zeros(1, dtype=torch.int64, device=dev)
+    _check(load().vfn_icp_accumulate(_ptr(queries, "queries", torch.float64), C.c_int64(n), _transform12(transform),
+                                     _ptr(targets, "targets", torch.float64), C.c_int64(m), _ptr(index, "index", torch.int64),
+                                     _ptr(sqdist, "sqdist", torch.float64), (C.c_double * 3)(*anchor), _ptr(sums, "sums", torch.float64),
+                                     _ptr(info, "info", torch.int64), _ptr(ws, "workspace", torch.uint8), C.c_int64(ws.numel()), _stream()),
+           "vfn_icp_accumulate")
+    if own:
+        icp_check(int(info.cpu()))
+    return sums
+
+
+def icp_check(status: int) -> None:
+    nn_check(status)
+    if status & GEOM_STATUS_INDEX:
+        raise VfnError("point-set alignment: a neighbour index lies outside the targets")
+
+
+def icp_sum_levels(n: int) -> int:
+    """Addition levels of every sum of vfn_icp_accumulate over n rows: the tree of vfn_reduce_stats."""
+    return reduce_sum_levels(n)
 
 
 # ------------------------------------------------------------------------------------------------

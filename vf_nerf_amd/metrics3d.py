@@ -16,7 +16,10 @@ The mesh that ``metrics_3d`` scores for a VF-NeRF run, ``tsdf_mesh``'s, comes fr
 ``fuse_rendered_views``) in the form ``score_mesh`` accepts; the other three meshes it scores (smoothed, refused, both) and its whole
 dictionary come from ``vf_nerf_amd.refuse`` (``reconstruction_meshes``, ``metrics_3d``).
 
-Out of scope: ICP alignment, the voxel down-sampling of
+``score_mesh(..., icp_align=True)`` first aligns the pred samples to the ref samples with ``vf_nerf_amd.icp.align`` (point-to-point ICP,
+a specification of ours: not verified against Open3D or the ``evaluate_3d_reconstruction`` package).
+
+Out of scope: the voxel down-sampling of
 the ``evaluate_3d_reconstruction`` package, trimesh's vertex merging, and PLY reading / writing.  The random numbers are torch's, not
 numpy's: a sampled point set is distributed as trimesh's, it is not the same set.
 """
@@ -193,18 +196,35 @@ def precision_recall_fscore(pred_points, ref_points, threshold: float, device=No
 
 
 def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: float = 0.05, generator: Optional[torch.Generator] = None,
-               uniforms=None, device=None) -> dict:
+               uniforms=None, device=None, icp_align: bool = False, icp_threshold: Optional[float] = None) -> dict:
     """One entry of the reference's ``3d-metrics.json`` (methods.py:794-801): {"chamfer distance": {mean, median, min, max}, "precision",
     "recall", "fscore"} (plus the two counts), from ONE sampling of each mesh and ONE nearest-neighbour search per direction shared
-    by both metrics.  ``uniforms`` ([num_points,3]) is used for BOTH meshes when given."""
+    by both metrics.  ``uniforms`` ([num_points,3]) is used for BOTH meshes when given.
+
+    ``icp_align=True``: the pred samples are aligned to the ref samples with ``icp.align`` (correspondences within ``icp_threshold``;
+    None = ``distance_thresh`` — that default is ours, not the external package's), moved by the result and scored as above; the
+    entry gains "icp": {"transformation" (nested lists), "fitness", "inlier_rmse", "iterations"}.  With ``icp_align=False`` nothing
+    changes: the same keys, values and draws from the generator as without the keyword."""
     pv, pf = _check_mesh(pred_mesh, "pred_mesh")
     rv, rf = _check_mesh(ref_mesh, "ref_mesh")
     num_points = geomargs.positive_int(num_points, "num_points")
     threshold = _check_threshold(distance_thresh)
+    if not isinstance(icp_align, (bool, np.bool_)):
+        raise ValueError(f"icp_align must be a bool, got {icp_align!r}")
+    if icp_align:
+        from . import icp
+        icp_radius = icp._check_radius(threshold if icp_threshold is None else icp_threshold, "icp_threshold")
     pred_points, _ = sample_surface(pv, pf, num_points, generator=generator, uniforms=uniforms, device=device)
     ref_points, _ = sample_surface(rv, rf, num_points, generator=generator, uniforms=uniforms, device=device)
+    aligned = None
+    if icp_align:
+        aligned = icp.align(pred_points, ref_points, icp_radius, device=pred_points.device)
+        pred_points = icp.transform_points(pred_points, aligned.transformation, device=pred_points.device)
     rows = _both_directions(pred_points, ref_points, threshold, device)
     mean, median, mn, mx = _chamfer(rows[0], rows[1])
     out = {"chamfer distance": {"mean": mean, "median": median, "min": mn, "max": mx}}
     out.update(_prf(rows[1], rows[0]))
+    if aligned is not None:
+        out["icp"] = {"transformation": aligned.transformation.tolist(), "fitness": aligned.fitness, "inlier_rmse": aligned.inlier_rmse,
+                      "iterations": aligned.iterations}
     return out

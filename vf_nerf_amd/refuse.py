@@ -13,8 +13,11 @@
 
 Everything stays on the device between the stages; a mesh is ``(vertices float64 [n,3], faces int64 [m,3])``.  No CPU fallback.
 
-Out of scope: colour (the reference fuses the dataset's RGB along with the depth; nothing it reports depends on it), ICP alignment
-(``icp_align``), PLY reading / writing.
+``metrics_3d(..., icp_align=True)`` aligns every mesh's samples to the ground truth's before scoring (``vf_nerf_amd.icp``, a
+specification of ours, not verified against Open3D).
+
+Out of scope: colour (the reference fuses the dataset's RGB along with the depth; nothing it reports depends on it), PLY reading /
+writing.
 """
 from __future__ import annotations
 
@@ -93,11 +96,13 @@ def reconstruction_meshes(tsdf_mesh, intrinsics, poses, height: int, width: int,
 
 def metrics_3d(tsdf_mesh, gt_mesh, intrinsics, poses, height: int, width: int, num_points: int = 1000000, distance_thresh: float = 0.01,
                generator: Optional[torch.Generator] = None, uniforms=None, iterations: int = ITERATIONS, lam: float = LAM,
-               **refuse_args) -> Dict[str, dict]:
+               icp_align: bool = False, icp_threshold: Optional[float] = None, **refuse_args) -> Dict[str, dict]:
     """The dictionary the reference writes to ``3d-metrics.json`` (methods.py:732-741): keys ``tsdf``, ``refused_tsdf``,
     ``tsdf_smoothed``, ``refused_tsdf_smoothed``, each ``metrics3d.score_mesh(mesh, gt_mesh)`` — {"chamfer distance": {mean, median,
-    min, max}, "precision", "recall", "fscore", ...} — scored in that order with the one ``generator`` (or the same ``uniforms``)."""
+    min, max}, "precision", "recall", "fscore", ...} — scored in that order with the one ``generator`` (or the same ``uniforms``).  ``icp_align`` / ``icp_threshold`` go to
+    ``metrics3d.score_mesh`` (every entry then has an "icp" key)."""
     meshes = reconstruction_meshes(tsdf_mesh, intrinsics, poses, height, width, iterations=iterations, lam=lam, **refuse_args)
     dev = meshes["tsdf"][0].device
     return {name: metrics3d.score_mesh(meshes[name], gt_mesh, num_points=num_points, distance_thresh=distance_thresh, generator=generator,
-                                       uniforms=uniforms, device=dev) for name in MESH_NAMES}
+                                       uniforms=uniforms, device=dev, icp_align=icp_align, icp_threshold=icp_threshold)
+            for name in MESH_NAMES}
