@@ -138,20 +138,10 @@ int check_shipped(int net_kind, const vfn_net_geom* g, const char* what) {
 // ------------------------------------------------------------------------------------------------
 // kernel
 // ------------------------------------------------------------------------------------------------
-#ifndef BW16_EARLY_EPI
-#define BW16_EARLY_EPI 1
-#endif
-#ifndef BW16_LATE_STORES
-#define BW16_LATE_STORES 1
-#endif
-#ifndef BW16_STORE_AUX
-#define BW16_STORE_AUX 2          // cache policy bits of the dY stores: 2 = nt (streaming).  With fragment-ordered slots every store is
-                                  // eight whole 128-byte lines; nt keeps 7 GB of write-once data from washing through the L2s:
-                                  // training step 12.5 -> 11.5 ms (0 = default write-back)
-#endif
-#ifndef BW_RING
-#define BW_RING 4                 // LDS ring slots of 32 KiB: a chunk's pieces are issued BW_RING - 1 chunks ahead
-#endif
+constexpr int BW16_STORE_AUX = 2;   // cache policy bits of the dY stores: 2 = nt (streaming).  With fragment-ordered slots every store is
+                                    // eight whole 128-byte lines; nt keeps 7 GB of write-once data from washing through the L2s:
+                                    // training step 12.5 -> 11.5 ms (0 = default write-back)
+constexpr int BW_RING = 4;          // LDS ring slots of 32 KiB: a chunk's pieces are issued BW_RING - 1 chunks ahead
 #define BW_SLOT_KB 32
 #define BW_SLOT (BW_SLOT_KB * 64)       // uint4 elements per ring slot
 #define BW_WAVES 4
@@ -319,9 +309,6 @@ __device__ __forceinline__ void store_tile_f16s(const Pipe& p, int b, const u32x
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.dy + (long long)SLOT * p.slot_floats, 0, (int)p.slot_bytes, 0x00020000);
     __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(p.live ? b : 255), rs, (int)p.evoff, TILE * 64, 0);
     if constexpr (SLOT == 3 && TILE == 6) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)255, rs, (int)p.evoff, 7 * 64, 0);   // see store_tile
-#ifdef BW16_ABL_NOSTORE      // timing only: the encode stays, the pieces do not leave
-    asm volatile("" :: "v"(eq[0]), "v"(eq[1]), "v"(eq[2]), "v"(eq[3]));
-#else
     // Round 5: the scalar offsets are compile-time constants (scaled f16 = fragment order: 2048 B per tile, 512 B per register quad).  They
     // used to come from the Pipe's runtime strides, which hipcc did not know to be uniform: each of the four stores of every tile sat in a
     // waterfall loop (v_readfirstlane / v_cmp / s_and_saveexec / store / s_cbranch_execnz: 245 loops in the vector-only kernel), i.e. four
@@ -329,7 +316,6 @@ __device__ __forceinline__ void store_tile_f16s(const Pipe& p, int b, const u32x
 #pragma unroll
     for (int q = 0; q < 4; ++q)
         __builtin_amdgcn_raw_buffer_store_b64(eq[q], rs, (int)p.dvoff, (TILE * 4096 + q * 1024) / 2, BW16_STORE_AUX);
-#endif
 }
 // a whole finished tile: (scaled f16: the lane's exponent byte first, so that the four piece stores stay the youngest
 // vector-memory operations of the chunk), then its four register quads
@@ -436,20 +422,11 @@ __device__ __forceinline__ void step16(const X16& xin, X16& xout, X16& xpend, Ca
     constexpr bool F16S = (MX & BM_F16S) != 0;
     constexpr bool P1 = (MX & BM_P1) != 0;
     constexpr int H = NB / 2;                         // hand-over after step H-1
-#if BW16_EARLY_EPI
     // The pending tile's epilogue runs in the FIRST half of the chunk (its masks are register-resident sign bits; only the
-    // tanh'ed feature tiles load values, and wait for them) and its dY stores go out right after the hand-over: they then have
-    // a whole chunk to retire before the next vmcnt(0) instead of half of one.
+    // tanh'ed feature tiles load values, and wait for them); its dY stores are the chunk's last vector-memory instructions.
     constexpr int E = H;                              // steps 0 .. E-1 carry the pending tile's epilogue
-    constexpr int EPI0 = 0;                           // first epilogue step
-    [[maybe_unused]] constexpr int ST0 = H;           // first store step (builds without BW16_LATE_STORES)
-#else
-    constexpr int E = NB - 2 - H;                     // steps H .. H+E-1 carry the pending tile's epilogue
-    constexpr int EPI0 = H;
-    [[maybe_unused]] constexpr int ST0 = H + E;
-#endif
     constexpr int DSTEPS = NB - H;
-    static_assert(2 * PT >= EPI0 + E || PT < 0, "the pending tile must be complete before it is read");
+    static_assert(2 * PT >= E || PT < 0, "the pending tile must be complete before it is read");
     const int g = lane >> 5;
     static_for<NCH>([&](auto ich) {
         constexpr int ch = decltype(ich)::value;
@@ -469,7 +446,7 @@ __device__ __forceinline__ void step16(const X16& xin, X16& xout, X16& xpend, Ca
         float esc = 1.0f;
         int eb = 255;
         u32x2s eq[4] = {{0u, 0u}, {0u, 0u}, {0u, 0u}, {0u, 0u}};
-        constexpr bool ENC_SPREAD = BW16_EARLY_EPI && BW16_LATE_STORES && H + 5 < NB;
+        constexpr bool ENC_SPREAD = H + 5 < NB;
         f32x4v mnext[4];
 #pragma unroll
         for (int st = 0; st < NB; ++st) {
@@ -479,13 +456,11 @@ __device__ __forceinline__ void step16(const X16& xin, X16& xout, X16& xpend, Ca
             }
             const bf8 a_hi = fh[st & 1];
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, xin.hi[st], acc, 0, 0, 0);
-#ifndef ABL_P1
             if constexpr (!P1) {
                 const bf8 a_lo = fl[st & 1];
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, xin.lo[st], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, xin.hi[st], acc, 0, 0, 0);
             }
-#endif
             // -- middle: ring hand-over.  The wave must see ITS pieces of chunk c+1 landed (issued in the previous chunk's second
             // half); the barrier then extends that to everybody's pieces and frees the slot of chunk c-1.  Vector-memory
             // operations retire in issue order (MI355X_MICROARCH.md, s_waitcnt), and the only operations issued AFTER those DMA
@@ -493,7 +468,6 @@ __device__ __forceinline__ void step16(const X16& xin, X16& xout, X16& xpend, Ca
             // exactly those in flight, so a tile's stores have a chunk and a half to retire instead of stalling every hand-over —
             // the chain was bound by that store round trip, not by store bandwidth (3.8 ms -> see DESIGN.md).
             if (st == H - 1 && dnext.kb > 0) {
-#if BW16_LATE_STORES
                 // operations younger than this wave's pieces of chunk c+1, which may stay in flight: the four dY stores at the end
                 // of a chunk (every chunk but the launch's first has a pending tile), and with a four-slot ring the pieces of
                 // chunk c+2 between them.  (The tanh tiles' value loads sit among them too: uncounted, so the wait is merely
@@ -504,15 +478,12 @@ __device__ __forceinline__ void step16(const X16& xin, X16& xout, X16& xpend, Ca
                 static_assert(young < 64, "vmcnt is a 6-bit field");
                 if constexpr (young == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(young) : "memory");
-#else
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
                 __builtin_amdgcn_s_barrier();
             }
-            // -- second half: the pending tile's epilogue ...
-            if (st >= EPI0 && st < EPI0 + E && (ch > 0 || PSLOT >= 0)) {
+            // -- first half: the pending tile's epilogue
+            if (st < E && (ch > 0 || PSLOT >= 0)) {
 #pragma unroll
-                for (int pr = (st - EPI0) * 8 / E; pr < (st - EPI0 + 1) * 8 / E; ++pr) {
+                for (int pr = st * 8 / E; pr < (st + 1) * 8 / E; ++pr) {
                     const int sblk = pr >> 2, j = (pr & 3) * 2;
                     if (ch > 0) epi_pair<MASK, HEAD, (ch > 0 ? ch - 1 : 0), P1>(cy.pend, cy.mask, pr, p, HEAD == 1 ? dzc : dzv, g, ehi[sblk], elo[sblk], j);
                     else epi_pair<PMASK, PHEAD, (PT >= 0 ? PT : 0), P1>(cy.pend, cy.mask, pr, p, PHEAD == 1 ? dzc : dzv, g, ehi[sblk], elo[sblk], j);
@@ -524,16 +495,8 @@ __device__ __forceinline__ void step16(const X16& xin, X16& xout, X16& xpend, Ca
                     }
                 }
             }
-            // ... its dY stores, the mask loads of the tile being computed, and the DMA pieces of chunk c+2
-#if !BW16_LATE_STORES
-            if (st >= ST0 && st < ST0 + 2 && (ch > 0 || PSLOT >= 0)) {
-#pragma unroll
-                for (int q = (st - ST0) * 2; q < (st - ST0 + 1) * 2; ++q) {
-                    if (ch > 0) store_group<OSLOT, (ch > 0 ? ch - 1 : 0)>(p, cy.pend, q);
-                    else store_group<(PSLOT >= 0 ? PSLOT : 0), (PT >= 0 ? PT : 0)>(p, cy.pend, q);
-                }
-            }
-#endif
+            // -- second half: the scaled-f16 encode of the pending tile, the mask loads of the tile being computed, and the DMA pieces
+            // of chunk c+2
             if (ENC_SPREAD && F16S && (ch > 0 || PSLOT >= 0)) {
                 if (st == H) esc = tile_scale(cy.pend, eb, p.live);
                 if (st > H && st <= H + 4) eq[st - H - 1] = pack_quad_f16s(cy.pend, st - H - 1, esc);
@@ -553,7 +516,6 @@ __device__ __forceinline__ void step16(const X16& xin, X16& xout, X16& xpend, Ca
                 }
             }
             if (st == NB - 1 && dnext.kb > 0) prefetch_chunk<MODE, (dnext.kb > 0 ? C + 1 : C), P1>(cy, p, lane);
-#if BW16_LATE_STORES
             // the pending tile's dY: the LAST vector-memory instructions of the chunk (see the hand-over)
             if (st == NB - 1 && (ch > 0 || PSLOT >= 0)) {
                 __builtin_amdgcn_sched_barrier(0);
@@ -565,7 +527,6 @@ __device__ __forceinline__ void step16(const X16& xin, X16& xout, X16& xpend, Ca
                     else store_tile<(PSLOT >= 0 ? PSLOT : 0), (PT >= 0 ? PT : 0)>(p, cy.pend);
                 }
             }
-#endif
             // (Explicit instruction groups here — one MFMA, then n VALU instructions in its shadow, as the forward kernel's K steps have them —
             //  were measured in round 5 with n = 6, 8, 12: the vector-only chain within 0.5 % of the compiler's own order, the fused one 1-3 %
             //  slower.  Not the lever.)
@@ -853,9 +814,6 @@ int vfn_internal_bwd_chain_bf16_ws_at(const vfn_net_geom* vf_geom, const void* v
                 "67108863 per workspace (got %lld in %lld)", (long long)n_points, (long long)ws_points);
     VFN_REQUIRE(!(dy_flags & 12) || (dy_flags & 2), "vfn_mlp_bwd_chain_bf16: 16-bit gradients need the fragment-ordered layout");
     VFN_REQUIRE((dy_flags & 12) != 12, "vfn_mlp_bwd_chain_bf16: dy_flags asks for bf16 AND scaled f16 gradients");
-#if !BW16_LATE_STORES
-    VFN_REQUIRE(!(dy_flags & 8), "vfn_mlp_bwd_chain_bf16: this build stores a tile's quads in separate steps; scaled f16 gradients need BW16_LATE_STORES");
-#endif
     Bwd16Args a = {};
     a.vf_wt = (const uint4*)vf_packed_bwd16; a.rn_wt = (const uint4*)rn_packed_bwd16; a.vf_head = vf_head_w; a.rn_head = rn_head_w;
     a.feats = saved; a.dy_flags = dy_flags & 14; a.masks = masks; a.dy = (float*)dy; a.d_colors = d_colors; a.colors = colors; a.d_vec = d_vec; a.vec = vec; a.d_feats = d_feats;

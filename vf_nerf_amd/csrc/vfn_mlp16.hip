@@ -47,41 +47,18 @@ typedef float float2v __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
-// Scaling: accumulators hold 2^6 x the true pre-activation.  VFN16_ASCALE = 1 carries the factor on the ACTIVATIONS
-// (operand blocks hold 2^6 x, weights are packed unscaled, the ReLU epilogue needs no multiply); 0 carries it on the
-// weights (activations unscaled, one multiply per value in the epilogue).
-#ifndef VFN16_ASCALE
-#define VFN16_ASCALE 1
-#endif
-#define VFN16_WSCALE 64.0f
-#define VFN16_INV_WSCALE 0.015625f
-#define VFN16_PACK_WSCALE (VFN16_ASCALE ? 1.0f : VFN16_WSCALE)
-#define VFN16_XSCALE (VFN16_ASCALE ? VFN16_WSCALE : 1.0f)
-#ifndef VFN16_SAVE_AUX
-#define VFN16_SAVE_AUX 2         // cache policy bits of the training-mode workspace stores: 2 = nt (streaming; whole-line stores of the
-                                 // fragment-ordered workspace: -0.1 ms on the step; with the row-major 32-byte pieces of round 1 nt cost
-                                 // +33 %), 0 = default write-back
-#endif
-#ifndef VFN16_HANDOVER_NUM
-#define VFN16_HANDOVER_NUM 8     // ring hand-over after K step NKB * n / 16
-#endif
-#ifndef VFN16_DMA_STEPS
-#define VFN16_DMA_STEPS 16       // the DMA pieces of chunk c+2 are spread over at most this many K steps after it
-#endif
-#ifndef VFN16_EPI_PER_MFMA
-#define VFN16_EPI_PER_MFMA 6     // VALU instructions of the pending epilogue scheduled behind each MFMA
-#endif
-#ifndef VFN16_EPI_PER_MFMA2
-#define VFN16_EPI_PER_MFMA2 9    // the same for the two-product tiles of the colour branch (two MFMAs per K step)
-#endif
-#ifndef VFN16_LATE_STORES
-#define VFN16_LATE_STORES 1      // training modes: the stores of a finished tile are the LAST vector-memory instructions of a chunk (after
-                                 // its DMA pieces), so the next ring hand-over waits with vmcnt(4) — operations retire in issue order,
-                                 // the four youngest are those stores — instead of draining them
-#endif
-#ifndef VFN16_MASK_STEP
-#define VFN16_MASK_STEP(H, NKB) (H)     // K step of a tile that carries the sign-bit collection of the pending tile (training)
-#endif
+// Scaling: accumulators hold 2^6 x the true pre-activation and the factor rides on the ACTIVATIONS (operand blocks hold
+// 2^6 x, weights are packed unscaled, the bias block carries 2^6 x, the ReLU epilogue needs no multiply).
+constexpr float VFN16_WSCALE = 64.0f;
+constexpr float VFN16_INV_WSCALE = 0.015625f;
+constexpr float VFN16_XSCALE = 64.0f;
+constexpr int VFN16_SAVE_AUX = 2;       // cache policy bits of the training-mode workspace stores: 2 = nt (streaming; whole-line stores of the
+                                        // fragment-ordered workspace: -0.1 ms on the step; with the row-major 32-byte pieces of round 1 nt cost
+                                        // +33 %), 0 = default write-back
+constexpr int VFN16_HANDOVER_NUM = 8;   // ring hand-over after K step NKB * n / 16
+constexpr int VFN16_DMA_STEPS = 16;     // the DMA pieces of chunk c+2 are spread over at most this many K steps after it
+constexpr int VFN16_EPI_PER_MFMA = 6;   // VALU instructions of the pending epilogue scheduled behind each MFMA
+constexpr int VFN16_EPI_PER_MFMA2 = 9;  // the same for the two-product tiles of the colour branch (two MFMAs per K step)
 #define VFN16_MAX_CHUNK_KB 39     // (16 act + 3 aux) K-blocks x 2 planes + 1 bias block
 #define VFN16_STATS_WORDS 64      // tail of a pack (256 bytes): per-entry weight statistics, see Pack16Args::stats
 
@@ -143,7 +120,7 @@ __device__ __forceinline__ float folded_weight(const Pack16Entry& e, int n, int 
     const int row = e.row_off + n;
     float w = e.w[(size_t)row * e.in_dim + col];
     if (e.bn_w) w *= e.bn_w[row] / sqrtf(e.bn_var[row] + 1e-5f);
-    return w * e.scale * VFN16_PACK_WSCALE;
+    return w * e.scale;
 }
 
 // Range statistics: max |folded weight| of every pack entry (non-negative floats order like their bit patterns).  VFN16_STAT_WGS extra
@@ -322,9 +299,7 @@ enum : int { M16_FEAT = 1, M16_RENDER = 2, M16_TRAIN = 4, M16_BLKOUT = 8, M16_BL
              M16_VF_VEC = 0, M16_FUSED = M16_FEAT | M16_RENDER, M16_VF_BLK = M16_FEAT | M16_BLKOUT, M16_RN_BLK = M16_RENDER | M16_BLKIN,
              M16_VF_VEC_TRAIN = M16_TRAIN, M16_VF_FULL_TRAIN = M16_FEAT | M16_TRAIN, M16_FUSED_TRAIN = M16_FUSED | M16_TRAIN };
 
-#ifndef VFN16_FDEPTH
-#define VFN16_FDEPTH 2            // A-fragment ring: K steps in registers (1 ahead)
-#endif
+constexpr int VFN16_FDEPTH = 2;   // A-fragment ring: K steps in registers (1 ahead)
 #define VFN16_SLOT (VFN16_MAX_CHUNK_KB * 64)   // uint4 elements per LDS ring slot
 #define VFN16_WAVES 4
 #define VFN16_PTS 128                          // points per workgroup (32 per wave)
@@ -381,9 +356,7 @@ constexpr bool mode_one(int mode) { return (mode & M16_P1) != 0; }
 // <= 20 KiB), so five slots fit where three did and a chunk is requested FOUR ahead: with a third of the matrix work per chunk the
 // stores of a finished tile need more than the chunk and a half a three-slot ring gives them to retire (the hand-over's vmcnt leaves
 // the stores of the last three chunks in flight instead of one's; 942 -> see DESIGN.md section 3, Backward 5).
-#ifndef VFN16_P1_RING
-#define VFN16_P1_RING 5
-#endif
+constexpr int VFN16_P1_RING = 5;
 #define VFN16_P1_SLOT_KB 20
 constexpr int ring_of(int mode) { return mode_one(mode) ? VFN16_P1_RING : 3; }
 constexpr int slot_u4(int mode) { return mode_one(mode) ? VFN16_P1_SLOT_KB * 64 : VFN16_MAX_CHUNK_KB * 64; }      // uint4 elements per slot
@@ -445,11 +418,9 @@ struct Mlp16Args {
 
 // Range of the split-f16 operands: activations ride at 2^6 x their value (VFN16_XSCALE) and are clamped here, i.e. true
 // activations above ~937 saturate.  The clamp keeps inf - inf = NaN out of the split; the status word reports that it acted.
+// The kernels look for values at the clamp once per finished tile (+1.3 % on the fused launch; per epilogue pair cost +3.2 %, placing
+// it in the shadow of the next tile's first MFMAs measured the same).
 #define VFN16_CLAMP 60000.0f
-#ifndef VFN16_RANGE_TRACK
-#define VFN16_RANGE_TRACK 2       // where the kernels look for values at the clamp: 0 nowhere, 1 per epilogue pair (+3.2 % on the fused
-                                  // launch), 2 per finished tile (+1.3 %; placing it in the shadow of the next tile's first MFMAs measured the same)
-#endif
 
 struct X16 { half8 hi[16]; half8 lo[16]; };     // 256 activation columns x this lane's point, split (16 K-blocks of 16)
 struct A16 { half8 hi[3]; half8 lo[3]; };       // 48 auxiliary (encoding) columns
@@ -550,11 +521,7 @@ __device__ __forceinline__ void prefetch_chunk(Carry16& cy, const Pipe16& p, int
 template <int EPI, bool KEEP, bool LO = true>
 __device__ __forceinline__ void epi_pair(f32x16& pend, unsigned long long& sat, int pr, half8& hi, half8& lo, int j) {
     float v0 = pend[2 * pr], v1 = pend[2 * pr + 1];
-    // one compare per pair into a SCALAR accumulator (a vector accumulator carried through the pipelined loop made hipcc spill)
-#if VFN16_RANGE_TRACK == 1
-    if (EPI == EPI_RELU) sat |= __builtin_amdgcn_ballot_w64(fmaxf(v0, v1) >= VFN16_CLAMP);
-#endif
-    if (!VFN16_ASCALE || EPI != EPI_RELU) { v0 *= VFN16_INV_WSCALE; v1 *= VFN16_INV_WSCALE; }
+    if (EPI != EPI_RELU) { v0 *= VFN16_INV_WSCALE; v1 *= VFN16_INV_WSCALE; }
     // ReLU, saturated below the f16 range so that an out-of-family activation degrades instead of turning into
     // inf - inf = NaN in the split (activations of BatchNorm'ed layers are O(1..100)); one v_max3 per pair remembers
     // whether the clamp ever acted (reported through the status word at the end of the kernel)
@@ -589,11 +556,6 @@ __device__ __forceinline__ void save_group(const Pipe16& p, const f32x16& v, int
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, h), rs, (int)p.save_voff16, (TILE * 4096 + q * 1024) / 2, VFN16_SAVE_AUX);
         return;
     }
-#if defined(ABL_SAVE_COALESCED)
-    // timing only (WRONG layout): the same bytes as one 1-KiB run per instruction, to price the row-major store pattern
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, g), rs, (int)(((p.save_voff >> 15) << 15) + (threadIdx.x & 63) * 16),
-                                           (4 * TILE + q) * 1024, VFN16_SAVE_AUX);
-#elif !defined(ABL_NOSAVE)
     if (SLOT == 8) {                    // the tanh'ed features: row-major fp32 (returned to callers, read by the chain as values)
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, g), rs, (int)p.feat_voff, (32 * TILE + 8 * q) * 4, 0);
     } else if (p.save16) {              // 11-bit operands for the weight gradients, half the workspace traffic
@@ -607,9 +569,6 @@ __device__ __forceinline__ void save_group(const Pipe16& p, const f32x16& v, int
         if (p.st_q == 1024u) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, g), rs, (int)p.save_voff, (int)(TILE * p.st_tile + q * p.st_q), VFN16_SAVE_AUX);
         else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, g), rs, (int)p.save_voff, (int)(TILE * p.st_tile + q * p.st_q), 0);
     }
-#else
-    asm volatile("" :: "v"(g));
-#endif
 }
 
 // Training: the sign bits of a finished (activated) tile.  The dX chain needs of every ReLU output only whether it is
@@ -694,15 +653,15 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
     constexpr int DSTEPS = DSPAN < VFN16_DMA_STEPS ? DSPAN : VFN16_DMA_STEPS;          // steps that carry DMA pieces
     static_assert(PEPI < 0 || PKB >= E, "the pending tile must be complete before it is read");
     constexpr bool TRAIN = (MODE & M16_TRAIN) != 0;
-    constexpr bool LATE = TRAIN && VFN16_LATE_STORES;
-    // late stores: DMA pieces in steps [H, DEND), the (mask store and the) four stores of the pending tile in steps [DEND, NKB)
-    constexpr int DEND = LATE ? (NKB - 4 > H + 1 ? NKB - 4 : (H + 1 < NKB ? H + 1 : NKB - 1)) : 0;
-    constexpr int SBEG = LATE ? DEND : H;
-    constexpr int SSTEPS = LATE ? (NKB - DEND > 0 ? NKB - DEND : 1) : (DSPAN < 4 ? DSPAN : 4);      // steps that carry the 4 stores of a tile
-    constexpr int DST = LATE ? (DEND - H > 0 ? DEND - H : 1) : DSTEPS;                             // steps that carry DMA pieces
-    // late stores: the sign-bit collection of the pending tile in MPARTS pieces over the steps [H, H + MPARTS) in front of its stores
+    // training modes: the stores of a finished tile are the LAST vector-memory instructions of a chunk (after its DMA pieces), so the
+    // next ring hand-over waits with vmcnt(4) — operations retire in issue order, the four youngest are those stores — instead of
+    // draining them: DMA pieces in steps [H, DEND), the (mask store and the) four stores of the pending tile in steps [DEND, NKB)
+    constexpr int DEND = NKB - 4 > H + 1 ? NKB - 4 : (H + 1 < NKB ? H + 1 : NKB - 1);
+    constexpr int SSTEPS = NKB - DEND > 0 ? NKB - DEND : 1;                 // training: steps that carry the 4 stores of a tile
+    constexpr int DST = TRAIN ? (DEND - H > 0 ? DEND - H : 1) : DSTEPS;     // steps that carry DMA pieces
+    // training: the sign-bit collection of the pending tile in MPARTS pieces over the steps [H, H + MPARTS) in front of its stores
     // (the epilogue pairs are done by step E <= H; 0: in one piece at the first store step)
-    constexpr int MPARTS = (LATE && E <= H) ? (DEND - H >= 4 ? 4 : (DEND - H >= 2 ? 2 : (DEND - H >= 1 ? 1 : 0))) : 0;
+    constexpr int MPARTS = (TRAIN && E <= H) ? (DEND - H >= 4 ? 4 : (DEND - H >= 2 ? 2 : (DEND - H >= 1 ? 1 : 0))) : 0;
     static_for<NCH>([&](auto ich) {
         constexpr int ch = decltype(ich)::value;
         constexpr int C = C0 + ch;
@@ -727,10 +686,6 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
         half8 fh[VFN16_FDEPTH], fl[VFN16_FDEPTH];
         fh[0] = cy.fh0;
         if (!P1 && (!W2 || ACT == 0)) fl[0] = cy.fl0;
-        if (VFN16_FDEPTH == 3 && NKB > 1) {
-            fh[1] = __builtin_bit_cast(half8, cb[FB * 64 + lane]);
-            if (!W2 && !P1) fl[1] = __builtin_bit_cast(half8, cb[3 * 64 + lane]);
-        }
         half8 ehi[2], elo[2];
         [[maybe_unused]] unsigned mbits = 0;
 #pragma unroll
@@ -744,19 +699,12 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
             const half8 x_hi = st < ACT ? xin.hi[st < ACT ? st : 0] : aux.hi[st >= ACT ? st - ACT : 0];
             const half8 x_lo = st < ACT ? xin.lo[st < ACT ? st : 0] : aux.lo[st >= ACT ? st - ACT : 0];
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, x_hi, acc, 0, 0, 0);
-#ifndef ABL_P1
             if constexpr (!P1) {
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, x_lo, acc, 0, 0, 0);
                 if (!W2 || st >= ACT) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fl[st % VFN16_FDEPTH], x_hi, acc, 0, 0, 0);
             }
-#endif
             // -- first half: epilogue pairs of the pending tile
-#ifdef ABL_NOEPI
-            if (st == 0 && (ch > 0 || PEPI >= 0)) asm volatile("" :: "v"(cy.pend));
-            if (false) {
-#else
             if (st < E && (ch > 0 || PEPI >= 0)) {
-#endif
 #pragma unroll
                 for (int pr = st * 8 / E; pr < (st + 1) * 8 / E; ++pr) {
                     const int sblk = pr >> 2, j = (pr & 3) * 2;
@@ -769,7 +717,6 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
                         else { xpend.hi[PKB + sblk] = ehi[sblk]; if constexpr (!P1) xpend.lo[PKB + sblk] = elo[sblk]; }
                     }
                 }
-#ifndef VFN16_NOGROUPS
                 if constexpr (!P1) {
                 // one MFMA, then its share of the epilogue in that MFMA's shadow
                 __builtin_amdgcn_sched_group_barrier(0x100, W2 ? 1 : 2, 0);
@@ -782,19 +729,13 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
                     __builtin_amdgcn_sched_group_barrier(0x002, VFN16_EPI_PER_MFMA, 0);
                 }
                 }
-#endif
             }
             // -- middle: ring hand-over
             if (st == H - 1 && dnext.kb > 0) {
-#ifndef ABL_NOSYNC
-#ifdef ABL_LOOSE_WAIT      // timing-only: leave the four stores of a training tile in flight (not safe: see DESIGN.md)
-                if ((MODE & M16_TRAIN) != 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else
-#endif
-                // late stores: the previous chunk ended with the four stores of its pending tile (every chunk but the launch's
+                // training: the previous chunk ended with the four stores of its pending tile (every chunk but the launch's
                 // first and the one after a layer that starts without a pending tile); everything older — the DMA pieces of
                 // chunk c+1 among it — has landed once at most those four are outstanding
-                if constexpr (P1 && LATE) {
+                if constexpr (P1 && TRAIN) {
                     // five-slot ring: younger than this wave's pieces of chunk c+1 are the stores of the last RING-2 chunks and the
                     // pieces of chunks c+2 .. c+RING-2 between them (lower bounds: a smaller immediate only waits for more)
                     constexpr int young = young_ops(MODE, C);
@@ -802,13 +743,11 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
                     if constexpr (young == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(young) : "memory");
                 } else
-                if (LATE && C > 0 && (ch == 0 || ch > 1 || PEPI >= 0)) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+                if (TRAIN && C > 0 && (ch == 0 || ch > 1 || PEPI >= 0)) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
-#endif
             }
             // -- second half: this step's share of the DMA pieces of chunk c+2
-#ifndef ABL_NODMA
             if (st >= H && st < H + DST && ddma.kb > 0) {
 #pragma unroll
                 for (int i = (st - H) * PM / DST; i < (st - H + 1) * PM / DST; ++i) {
@@ -821,11 +760,8 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
                     }
                 }
             }
-#endif
-            // -- training: the finished (activated) pending tile goes out after the hand-over, so that the stores have
-            // half a chunk to retire before the next vmcnt(0)
-#ifndef ABL_NOMASK
-            // (late stores: the pending tile's sign bits are collected in the DMA steps, a quarter per step, ahead of its stores)
+            // -- training: the finished (activated) pending tile goes out after the DMA pieces, as the chunk's last vector-memory
+            // instructions (its sign bits are collected in the DMA steps, a quarter per step, ahead of its stores)
             if (TRAIN && MPARTS > 0 && st >= H && st < H + MPARTS && (ch > 0 || PEPI >= 0)) {
                 static_for<MPARTS>([&](auto ip) {
                     constexpr int part = decltype(ip)::value;
@@ -835,10 +771,8 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
                     }
                 });
             }
-#endif
-            if (TRAIN && st >= SBEG && st < SBEG + SSTEPS && (ch > 0 || PEPI >= 0)) {
-#ifndef ABL_NOMASK
-                if (st == (LATE ? SBEG : VFN16_MASK_STEP(H, NKB))) {       // its sign bits; the pending tile (ch == 0) is the last one of the previous layer
+            if (TRAIN && st >= DEND && st < DEND + SSTEPS && (ch > 0 || PEPI >= 0)) {
+                if (st == DEND) {       // its sign bits; the pending tile (ch == 0) is the last one of the previous layer
                     if constexpr (MPARTS > 0) {
                         if (ch == 0) store_mask<(PSLOT >= 0 ? PSLOT : 0)>(p, cy);
                     } else {
@@ -846,9 +780,8 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
                         else { collect_mask<PKB / 2, (PEPI >= 0 ? PEPI : 0)>(cy); store_mask<(PSLOT >= 0 ? PSLOT : 0)>(p, cy); }
                     }
                 }
-#endif
 #pragma unroll
-                for (int q = (st - SBEG) * 4 / SSTEPS; q < (st - SBEG + 1) * 4 / SSTEPS; ++q) {
+                for (int q = (st - DEND) * 4 / SSTEPS; q < (st - DEND + 1) * 4 / SSTEPS; ++q) {
                     if (ch > 0) save_group<(SLOT >= 0 ? SLOT : 0), (ch > 0 ? ch - 1 : 0), (MODE & M16_SF16) != 0>(p, cy.pend, q);
                     else save_group<(PSLOT >= 0 ? PSLOT : 0), PKB / 2, (MODE & M16_SF16) != 0>(p, cy.pend, q);
                 }
@@ -860,20 +793,18 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
             }
             // -- last step: the next chunk's bias and first fragments
             if (st == NKB - 1 && dnext.kb > 0) prefetch_chunk<MODE, (dnext.kb > 0 ? C + 1 : C)>(cy, p, lane);
-#ifndef VFN16_NOSCHED
             __builtin_amdgcn_sched_barrier(0);
-#endif
         }
         if (EPI == EPI_RELU || EPI == EPI_TANH) {
             cy.pend = acc;
-#if VFN16_RANGE_TRACK == 2
-            if (EPI == EPI_RELU) {        // the finished tile's largest (2^6-scaled) pre-activation: 8 v_max3 + one compare per tile
+            // the finished tile's largest (2^6-scaled) pre-activation: 8 v_max3 + one compare per tile, into a SCALAR accumulator
+            // (a vector accumulator carried through the pipelined loop made hipcc spill)
+            if (EPI == EPI_RELU) {
                 float mx = fmaxf(acc[0], acc[1]);
 #pragma unroll
                 for (int r = 2; r < 16; r += 2) mx = fmaxf(mx, fmaxf(acc[r], acc[r + 1]));
                 cy.sat |= __builtin_amdgcn_ballot_w64(mx >= VFN16_CLAMP);
             }
-#endif
         } else {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
@@ -1017,9 +948,6 @@ __global__ __launch_bounds__(256, 1) void vfn_mlp16_kernel(const Mlp16Args a) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 5;
-#ifdef VFN16_STAMPS
-    const unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
     // clock probe (fused VF + rendering launches only; scalar registers, a uniform branch): what the shader clock was while THIS
     // workgroup ran — the kernel is power-limited, so the clock is a result, not a constant (bench.py: roofline.effective_clock_ghz)
     unsigned long long ck_t0 = 0ull, ck_r0 = 0ull;
@@ -1090,18 +1018,8 @@ __global__ __launch_bounds__(256, 1) void vfn_mlp16_kernel(const Mlp16Args a) {
         for (int q = 0; q < 16; ++q) cy.pend[q] = 0.f;
         cy.lm[0] = 0; cy.lm[1] = 0; cy.lm[2] = 0; cy.lm[3] = 0; cy.sat = 0ull;
         prefetch_chunk<MODE, 0>(cy, p, lane);
-#ifdef VFN16_STAMPS
-        const unsigned long long st_t1 = __builtin_amdgcn_s_memtime();
-#endif
         render_tail<MODE>(a, p, cy, xa, xb, aux, nrm, live ? (long long)dpos : -1, live, wave, lane);
         report_range(a, cy.sat, ain_blk);
-#ifdef VFN16_STAMPS
-        if (threadIdx.x == 0 && live) {
-            const unsigned long long t2 = __builtin_amdgcn_s_memtime(), r2 = __builtin_amdgcn_s_memrealtime();
-            a.out_colors[(long long)dpos * 3 + 0] = (float)(st_t1 - st_t0); a.out_colors[(long long)dpos * 3 + 1] = (float)(t2 - st_t0);
-            a.out_colors[(long long)dpos * 3 + 2] = (float)(r2 - st_r0);
-        }
-#endif
     } else {
     // this lane's point (the two lane halves of a wave share the 32 points); loaded BEFORE any DMA
     float x[3] = {0.f, 0.f, 0.f};
@@ -1148,13 +1066,6 @@ __global__ __launch_bounds__(256, 1) void vfn_mlp16_kernel(const Mlp16Args a) {
     dma_chunk<MODE, 0>(p, wave, lane);
     dma_chunk<MODE, 1>(p, wave, lane);
     if constexpr (mode_one(MODE)) static_for<VFN16_P1_RING - 3>([&](auto ic) { dma_chunk<MODE, 2 + decltype(ic)::value>(p, wave, lane); });
-#ifdef ABL_NODMA
-    // timing only (WRONG results): no DMA inside the layers; the three slots keep three full-size chunks of real weights,
-    // so the matrix cores still see random operands (an empty ring would feed zeros, which raises the clock)
-    dma_chunk<MODE, 9>(p, wave, lane);      // chunk 9 -> slot 0, 10 -> slot 1, 11 -> slot 2 (tiles of VF layer 1, 33 KiB each)
-    dma_chunk<MODE, 10>(p, wave, lane);
-    dma_chunk<MODE, 11>(p, wave, lane);
-#endif
 
     // ---- positional encoding of the point -> aux operand (and its parked copy for the skip layer) -----------
     const int vf_multires = a.vf_multires;
@@ -1181,9 +1092,6 @@ __global__ __launch_bounds__(256, 1) void vfn_mlp16_kernel(const Mlp16Args a) {
     // are ever live
     X16 xa, xb;
     float vec[3] = {0.f, 0.f, 0.f};
-#ifdef VFN16_STAMPS
-    const unsigned long long st_t1 = __builtin_amdgcn_s_memtime();      // prologue done
-#endif
     constexpr int R = EPI_RELU, T = EPI_TANH, NONE = -1;
     layer16<MODE, 0, 0, 3, 8, R, NONE, 0, 0, -1>(xa, aux, xb, xb, cy, vec, p, wave, lane);        // L0: encoding only
     layer16<MODE, 8, 16, 0, 8, R, R, 14, 1, 0>(xb, aux, xa, xb, cy, vec, p, wave, lane);         // L1
@@ -1206,12 +1114,6 @@ __global__ __launch_bounds__(256, 1) void vfn_mlp16_kernel(const Mlp16Args a) {
     if constexpr (!(MODE & M16_RENDER)) {
         if (in && g == 0) { a.out_vec[m * 3 + 0] = vec[0]; a.out_vec[m * 3 + 1] = vec[1]; a.out_vec[m * 3 + 2] = vec[2]; }
         report_range(a, cy.sat, ain);
-#ifdef VFN16_STAMPS
-        if (threadIdx.x == 0) {   // timing-only build: prologue cycles, total cycles, total 100 MHz ticks of this workgroup
-            const unsigned long long t2 = __builtin_amdgcn_s_memtime(), r2 = __builtin_amdgcn_s_memrealtime();
-            a.out_vec[m * 3 + 0] = (float)(st_t1 - st_t0); a.out_vec[m * 3 + 1] = (float)(t2 - st_t0); a.out_vec[m * 3 + 2] = (float)(r2 - st_r0);
-        }
-#endif
     } else {
     // the head's outputs sit in the lanes < 32; the other lane half of the same point needs them for the aux operand
     float nrm[3];
@@ -1229,14 +1131,6 @@ __global__ __launch_bounds__(256, 1) void vfn_mlp16_kernel(const Mlp16Args a) {
             a.clock[2 * blockIdx.x] = t1 - ck_t0; a.clock[2 * blockIdx.x + 1] = r1 - ck_r0;
         }
     }
-    const long long mo = (long long)blockIdx.x * VFN16_PTS + (threadIdx.x >> 6) * 32 + (threadIdx.x & 31);
-    (void)mo;
-#ifdef VFN16_STAMPS
-    if (threadIdx.x == 0) {   // timing-only build: shader-clock and 100 MHz ticks of this workgroup, over its first colours
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        a.out_colors[mo * 3 + 0] = (float)(t1 - st_t0); a.out_colors[mo * 3 + 1] = (float)(r1 - st_r0);
-    }
-#endif
     }   // rendering net
     }   // feature block
     }   // not M16_BLKIN
