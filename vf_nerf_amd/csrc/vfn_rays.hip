@@ -1192,6 +1192,7 @@ extern "C" int vfn_ray_density_weights_bwd(const vfn_density_params* p, const fl
     VFN_REQUIRE(p && normals && ray_dirs && z_vals && density_scalars && d_normals, "vfn_ray_density_weights_bwd: NULL argument");
     VFN_REQUIRE(p->n_samples >= 2 && p->n_samples <= MAX_SAMPLES_BWD,
                 "vfn_ray_density_weights_bwd: n_samples=%d outside [2,%d]", p->n_samples, MAX_SAMPLES_BWD);
+    VFN_REQUIRE(p->n_window >= 1, "vfn_ray_density_weights_bwd: n_window must be >= 1");
     VFN_REQUIRE(!(d_rgb && !colors), "vfn_ray_density_weights_bwd: d_rgb given without colors");
     if (p->n_rays <= 0) return VFN_OK;
     DensityBwdArgs a{*p, normals, ray_dirs, z_vals, density_scalars, colors, d_rgb, d_depth, d_weights, nullptr, d_normals, d_colors, d_scalars};
@@ -1209,6 +1210,7 @@ extern "C" int vfn_ray_density_sigma_bwd(const vfn_density_params* p, const floa
     VFN_REQUIRE(p && normals && ray_dirs && z_vals && density_scalars && d_sigma && d_normals, "vfn_ray_density_sigma_bwd: NULL argument");
     VFN_REQUIRE(p->n_samples >= 2 && p->n_samples <= MAX_SAMPLES_BWD,
                 "vfn_ray_density_sigma_bwd: n_samples=%d outside [2,%d]", p->n_samples, MAX_SAMPLES_BWD);
+    VFN_REQUIRE(p->n_window >= 1, "vfn_ray_density_sigma_bwd: n_window must be >= 1");
     DensityBwdArgs a{*p, normals, ray_dirs, z_vals, density_scalars, nullptr, nullptr, nullptr, nullptr, d_sigma, d_normals, nullptr, d_scalars};
     const int rpb = bwd_rays_per_block(p->n_samples);
     const unsigned blocks = (unsigned)((p->n_rays + rpb - 1) / rpb);
