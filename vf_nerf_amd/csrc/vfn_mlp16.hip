@@ -418,9 +418,18 @@ struct Mlp16Args {
 
 // Range of the split-f16 operands: activations ride at 2^6 x their value (VFN16_XSCALE) and are clamped here, i.e. true
 // activations above ~937 saturate.  The clamp keeps inf - inf = NaN out of the split; the status word reports that it acted.
-// The kernels look for values at the clamp once per finished tile (+1.3 % on the fused launch; per epilogue pair cost +3.2 %, placing
-// it in the shadow of the next tile's first MFMAs measured the same).
+// The kernels look for pre-activations at the clamp once per finished ReLU tile, without a floating-point instruction: the
+// question is only "did any accumulator reach VFN16_CLAMP?", the clamp is positive, and for floats the signed-integer order of
+// the bit patterns is the float order wherever that matters here — negative values (and -0) are negative integers and lose,
+// +inf compares above the clamp's bits as it does as a float.  One difference, kept on purpose: a NaN with a clear sign bit
+// also compares above the clamp and IS flagged, where the ordered float compare `>=` said nothing about it (the safer reading).
+// Per tile: 8 v_max3_i32 on the bit-cast accumulators (one per epilogue pair, in the same MFMA shadow), one v_cmp_ge_i32 and
+// the ballot into a scalar mask.  As fmaxf on the tile boundary the same guard compiled to 16 canonicalising v_max_f32 v, v, v
+// + 12 v_max/v_max3 + compare + two v_writelane, all of it between a tile's last MFMA and the next tile's first
+// (profiles/r12/mlp16_instruction_mix.md).
 #define VFN16_CLAMP 60000.0f
+constexpr int VFN16_CLAMP_BITS = 0x476a6000;    // the bit pattern of VFN16_CLAMP
+static_assert(__builtin_bit_cast(int, VFN16_CLAMP) == VFN16_CLAMP_BITS, "VFN16_CLAMP_BITS is VFN16_CLAMP as an integer");
 
 struct X16 { half8 hi[16]; half8 lo[16]; };     // 256 activation columns x this lane's point, split (16 K-blocks of 16)
 struct A16 { half8 hi[3]; half8 lo[3]; };       // 48 auxiliary (encoding) columns
@@ -518,15 +527,21 @@ __device__ __forceinline__ void prefetch_chunk(Carry16& cy, const Pipe16& p, int
 }
 
 // Two accumulator values -> (hi, lo) halves of element pair (j, j+1) of an operand block.
+// `gmax` (ReLU tiles): the running maximum of the tile's pre-activations AS SIGNED INTEGERS, see VFN16_CLAMP_BITS.
 template <int EPI, bool KEEP, bool LO = true>
-__device__ __forceinline__ void epi_pair(f32x16& pend, unsigned long long& sat, int pr, half8& hi, half8& lo, int j) {
+__device__ __forceinline__ void epi_pair(f32x16& pend, int& gmax, int pr, half8& hi, half8& lo, int j) {
     float v0 = pend[2 * pr], v1 = pend[2 * pr + 1];
     if (EPI != EPI_RELU) { v0 *= VFN16_INV_WSCALE; v1 *= VFN16_INV_WSCALE; }
     // ReLU, saturated below the f16 range so that an out-of-family activation degrades instead of turning into
-    // inf - inf = NaN in the split (activations of BatchNorm'ed layers are O(1..100)); one v_max3 per pair remembers
-    // whether the clamp ever acted (reported through the status word at the end of the kernel)
+    // inf - inf = NaN in the split (activations of BatchNorm'ed layers are O(1..100)); one v_max3_i32 per pair remembers
+    // whether the clamp ever acted (reported through the status word at the end of the kernel).
+    // The clamp is v_med3_f32 on the accumulator registers themselves.  fminf(fmaxf(v, 0), CLAMP) compiles to the same
+    // v_med3_f32, but behind one v_max_f32 v, v, v per register: fmaxf is llvm.maxnum, which must quiet a signalling NaN, and
+    // hipcc cannot see that a matrix instruction never returns one (its NaNs are quiet, for which med3 gives 0 either way).
     if (EPI == EPI_RELU) {
-        v0 = fminf(fmaxf(v0, 0.f), VFN16_CLAMP); v1 = fminf(fmaxf(v1, 0.f), VFN16_CLAMP);
+        const int b0 = __builtin_bit_cast(int, v0), b1 = __builtin_bit_cast(int, v1);
+        gmax = pr == 0 ? max(b0, b1) : max(max(gmax, b0), b1);
+        v0 = __builtin_amdgcn_fmed3f(v0, 0.f, VFN16_CLAMP); v1 = __builtin_amdgcn_fmed3f(v1, 0.f, VFN16_CLAMP);
     }
     else { v0 = tanh_exp(v0) * VFN16_XSCALE; v1 = tanh_exp(v1) * VFN16_XSCALE; }
     if constexpr (LO) {
@@ -619,7 +634,7 @@ __device__ __forceinline__ void store_mask(const Pipe16& p, Carry16& cy) {
 //
 // With one wave per SIMD nothing else hides the epilogue, the DMA issue or the ring hand-over, so the chunk loop is
 // software-pipelined over the K steps of a tile (three MFMAs = 96 matrix-pipe cycles each, fenced by sched_barrier):
-//   first half   the epilogue of the PREVIOUS tile (8 register pairs);
+//   first half   the epilogue of the PREVIOUS tile (8 register pairs) and, with it, that tile's range guard;
 //   middle       s_waitcnt vmcnt(0) + s_barrier: chunk c+1 (issued half a chunk ago) has landed for everybody and
 //                everybody has left chunk c-1, whose slot is now free;
 //   second half  the LDS-DMA pieces of chunk c+2 into that slot;
@@ -687,6 +702,7 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
         fh[0] = cy.fh0;
         if (!P1 && (!W2 || ACT == 0)) fl[0] = cy.fl0;
         half8 ehi[2], elo[2];
+        [[maybe_unused]] int gmax = 0;               // the pending tile's largest pre-activation (bit pattern); lives for E steps of this tile
         [[maybe_unused]] unsigned mbits = 0;
 #pragma unroll
         for (int st = 0; st < NKB; ++st) {
@@ -708,8 +724,10 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
 #pragma unroll
                 for (int pr = st * 8 / E; pr < (st + 1) * 8 / E; ++pr) {
                     const int sblk = pr >> 2, j = (pr & 3) * 2;
-                    if (ch > 0) epi_pair<EPI, TRAIN, !P1>(cy.pend, cy.sat, pr, ehi[sblk], elo[sblk], j);
-                    else epi_pair<(PEPI >= 0 ? PEPI : 0), TRAIN, !P1>(cy.pend, cy.sat, pr, ehi[sblk], elo[sblk], j);
+                    if (ch > 0) epi_pair<EPI, TRAIN, !P1>(cy.pend, gmax, pr, ehi[sblk], elo[sblk], j);
+                    else epi_pair<(PEPI >= 0 ? PEPI : 0), TRAIN, !P1>(cy.pend, gmax, pr, ehi[sblk], elo[sblk], j);
+                    // the range guard of the pending tile, once its last pair has gone by: one integer compare into the SCALAR mask
+                    if (pr == 7 && (ch > 0 ? EPI : PEPI) == EPI_RELU) cy.sat |= __builtin_amdgcn_ballot_w64(gmax >= VFN16_CLAMP_BITS);
                     if ((pr & 3) == 3) {
                         asm volatile("" : "+a"(ehi[sblk]));   // operands live in AGPRs (MFMA reads them there)
                         if constexpr (!P1) asm volatile("" : "+a"(elo[sblk]));
@@ -796,15 +814,10 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
             __builtin_amdgcn_sched_barrier(0);
         }
         if (EPI == EPI_RELU || EPI == EPI_TANH) {
+            // Nothing else here: the next tile's first MFMA follows this tile's last one.  The finished tile's range guard
+            // rides with its epilogue (epi_pair), in the MFMA shadow of the next tile's first K steps — for a layer's last tile
+            // that is the next layer's first tile; every ReLU tile's epilogue runs before report_range, its values are operands.
             cy.pend = acc;
-            // the finished tile's largest (2^6-scaled) pre-activation: 8 v_max3 + one compare per tile, into a SCALAR accumulator
-            // (a vector accumulator carried through the pipelined loop made hipcc spill)
-            if (EPI == EPI_RELU) {
-                float mx = fmaxf(acc[0], acc[1]);
-#pragma unroll
-                for (int r = 2; r < 16; r += 2) mx = fmaxf(mx, fmaxf(acc[r], acc[r + 1]));
-                cy.sat |= __builtin_amdgcn_ballot_w64(mx >= VFN16_CLAMP);
-            }
         } else {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
