@@ -811,6 +811,52 @@ int vfn_icp_accumulate(const double* queries, int64_t n, const double* transform
                        void* workspace, int64_t workspace_bytes, void* stream);
 
 /* =============================================================================================
+ * Scoring rendered views (csrc/vfn_image.hip): the image half of evaluation/methods.py:549-610 (metrics) — utils/utils.py:235-245
+ * (get_psnr), :248-289 (get_ssim), :312-325 (get_l1_cm) and the save_rgb -> PNG -> load_rgb round trip (:73-108).  A float64
+ * SPECIFICATION of the reference's formulas (the reference evaluates them in float32).  Everything is float64, evaluated without
+ * contraction in the association written here; no result depends on the order in which workgroups arrive; no floating-point atomics.
+ * `info` as above: zero-filled by the caller and only ever OR-ed into, bit 1 = a non-finite value, bit 4 = a value outside the range of
+ * a byte.  Images are V views of H x W x C values, interleaved, row-major.  Limits: 1 <= V, 1 <= H, W < 2^15, C in {1, 3},
+ * V H W C < 2^31; anything else is refused before any launch.
+ *   vfn_image_quantize8  u[i] = trunc(double(x[i]) 255.0) for x[n] float32, 1 <= n < 2^31.  The product is exact (24 bits x 8 bits), so
+ *                     this is numpy's (x.astype(float64) * 255).astype(uint8) — what save_rgb writes for a float64 image — wherever
+ *                     that cast is defined.  Where it is not, the value is refused instead of wrapped: x not finite: info[0] |= 1;
+ *                     x < 0 or double(x) 255.0 >= 256: info[0] |= 4; u[i] = 0 in both cases.  (-0.0 is 0.)
+ *   vfn_image_scores  pred and target are uint8 (p = double(u) / 255.0, the division rounded once) or float32 (p = double(x)), chosen
+ *                     by pred_u8 / target_u8.  Writes sums[V, 3], both sums over all H W C elements of view v:
+ *                       sums[v][0] = sum (p - t)^2        (the difference rounded once, the square once)
+ *                       sums[v][1] = sum ssim(y, x, c)    (written 0 when want_ssim == 0)
+ *                       sums[v][2] = 0                    (reserved)
+ *                     ssim at (y, x, c), window k = 11, zero padding (a term outside the image is +0.0, the divisor always 121):
+ *                     for each a in {p, t, p p, t t, p t} (each product rounded once, per element)
+ *                       r_a[y'][x] = a[y'][x-5] + a[y'][x-4] + ... + a[y'][x+5]        added serially from the left, the first term as it is
+ *                       S_a        = r_a[y-5][x] + r_a[y-4][x] + ... + r_a[y+5][x]     added serially from the top, the first term as it is
+ *                       m_a        = S_a / 121.0
+ *                     mu1 = m_p, mu2 = m_t, s1 = m_pp - mu1 mu1, s2 = m_tt - mu2 mu2, s12 = m_pt - mu1 mu2,
+ *                       ssim = ((2 (mu1 mu2) + C1) (2 s12 + C2)) / (((mu1 mu1 + mu2 mu2) + C1) ((s1 + s2) + C2))
+ *                     (get_ssim's defaults: C1 = 1e-4, C2 = 9e-4).  With p == t every element is exactly 1.0.  No running window.
+ *                     A non-finite float32 element: info[0] |= 1.
+ *   vfn_image_abs_err a[V, H, W], b[V, H, W] float32: sums[v] = sum |double(a) s - double(b) s|, each product rounded once; s = 100 is
+ *                     get_l1_cm's sum.  A kernel of its own over the tiles of a C = 1 image; the sums are joined as below.
+ *   The sums are a FIXED tree.  A workgroup owns a tile of VFN_IMAGE_TILE x VFN_IMAGE_TILE = 16 x 16 pixels; tile (tile_y, tile_x) starts
+ *   at pixel (16 tile_y, 16 tile_x); lane l = 16 ly + lx owns pixel (16 tile_y + ly, 16 tile_x + lx) and adds its C elements serially in
+ *   ascending c, the first as it is; a lane outside the image holds +0.0.  The 256 lane values join as a balanced tree: lane l takes
+ *   lane l + d for d = 128, 64, ... 1.  One partial per tile goes to the workspace in (view, tile_y, tile_x) order.  A second launch, one
+ *   workgroup of 1024 lanes per view, joins the view's P = ceil(H / 16) ceil(W / 16) partials as vfn_reduce_stats does: lane l starts
+ *   from partial l (+0.0 if l >= P) and adds the partials l + 1024, l + 2048, ... serially, then a balanced tree (l takes l + d,
+ *   d = 512 ... 1).  The bits are a function of (V, H, W, C) and the data alone.
+ *   workspace: vfn_image_scores_workspace_bytes(V, H, W, C) bytes (vfn_image_abs_err: C = 1); answers on the host, -1 on error.
+ * ============================================================================================= */
+#define VFN_IMAGE_TILE 16
+int vfn_image_quantize8(const float* x, int64_t n, uint8_t* u, int64_t* info, void* stream);
+int64_t vfn_image_scores_workspace_bytes(int64_t V, int64_t H, int64_t W, int64_t C);
+int vfn_image_scores(const void* pred, int32_t pred_u8, const void* target, int32_t target_u8, int64_t V, int64_t H, int64_t W, int64_t C,
+                     int32_t want_ssim, double c1, double c2, double* sums, int64_t* info, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int vfn_image_abs_err(const float* a, const float* b, int64_t V, int64_t H, int64_t W, double scale, double* sums, int64_t* info,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
+/* =============================================================================================
  * Fusing depth maps into a mesh (csrc/vfn_tsdf.hip): the stage of evaluation/methods.py:613-665 (tsdf_mesh) between the rendered depth
  * maps and the mesh that metrics_3d scores, with the semantics of a uniform TSDF volume — projective integration with a running mean,
  * classic marching cubes on the zero level set.  Two deliberate differences: the volume is DENSE over a box the caller gives (not

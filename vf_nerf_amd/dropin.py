@@ -36,7 +36,8 @@ def _ensure_package(name: str) -> None:
         sys.modules[name] = pkg
 
 
-def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scalars=None, patch_mesh: bool = True) -> None:
+def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scalars=None, patch_mesh: bool = True,
+            patch_metrics: bool = False) -> None:
     """``patch_clip=False`` leaves ``torch.nn.utils.clip_grad_norm_`` PyTorch's own function (no process-wide replacement): a step session then
     parks its gradient in the optimizer's flat buffer with every ``param.grad`` None, the trainer's clip call finds nothing to scale, and
     ``optimizer.step()`` all-reduces (more than one rank), clips with the model's ``scheduler_config.clip_norm`` — the value the trainer
@@ -48,7 +49,10 @@ def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scal
     six ``.cpu()`` read-backs per 512-ray chunk): every call of it still lands on the HIP ``render()``; what it gives up is the grouping
     into chip-filling chunks and the single download per image (profiles/r05/bench_view_as_evaluator.json: both loops timed).
     ``patch_mesh`` replaces ``evaluation.utils.marching_cubes_vt.contrastive_marching_cubes`` with ``mesh.contrastive_marching_cubes``
-    (the device triangulation, same (vs, fs)); ``patch_mesh=False`` restores the reference's function."""
+    (the device triangulation, same (vs, fs)); ``patch_mesh=False`` restores the reference's function.
+    ``patch_metrics=True`` replaces ``evaluation.methods.metrics`` with ``evaluator.metrics`` (the image scores on the device, a float64
+    specification: the PSNR values differ from the reference's float32 ones by its rounding) and keeps the reference's function as
+    ``methods._reference_metrics``; the default leaves it alone, and ``False`` after ``True`` puts it back."""
     for dotted, module in _ALIASES.items():
         parts = dotted.split(".")
         for i in range(1, len(parts)):
@@ -77,6 +81,12 @@ def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scal
             methods.render_images = evaluator.render_images
         elif hasattr(methods, "_reference_render_images"):
             methods.render_images = methods._reference_render_images
+        if patch_metrics:
+            if not hasattr(methods, "_reference_metrics"):
+                methods._reference_metrics = methods.metrics
+            methods.metrics = evaluator.metrics
+        elif hasattr(methods, "_reference_metrics"):
+            methods.metrics = methods._reference_metrics
     except Exception:
         pass
     # evaluation/utils/marching_cubes_vt.contrastive_marching_cubes (a Python loop over every surface cell) -> the device triangulation;

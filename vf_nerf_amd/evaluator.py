@@ -6,12 +6,17 @@ chunk, with the device idle in between.  ``render_view`` does the same work with
 (``VectorFieldNerf.render_chunked``: same per-chunk arithmetic, so the same values) and ONE download per image;
 ``render_images`` is the reference function's loop around it — same dataset, same files written — and is what
 ``vf_nerf_amd.dropin.install()`` puts in place of ``evaluation.methods.render_images``, so that ``evaluation/evaluate.py`` runs
-unchanged."""
+unchanged.
+
+``score_view`` renders a view the same way and scores it against its target on the device (``vf_nerf_amd.metrics2d``) without
+downloading the image; ``metrics`` is the drop-in for ``evaluation.methods.metrics`` (methods.py:549-610: the PNGs written by
+``render_images`` scored against the dataset's images, ``metrics.json``), installed by ``dropin.install(patch_metrics=True)``."""
 from __future__ import annotations
 
 import importlib
+import json
 import os
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -79,3 +84,99 @@ def render_images(model, eval_path: str, dataset_config, epoch: int, split_size:
         depth_map[rows, cols, :] = depth_values
         utils.save_rgb(os.path.join(path, f"image-{i}.png"), rgb)
         utils.save_depth(os.path.join(path, f"depth-{i}"), depth_map)
+
+
+METRICS_CHUNK = 8       # views scored per launch by metrics(): bounds the images held at once (a 680 x 1200 target is 9.8 MB)
+
+
+@torch.no_grad()
+def score_view(model, all_pose: torch.Tensor, all_pixels: torch.Tensor, all_intrinsics: torch.Tensor, epoch: int, target_rgb,
+               target_depth=None, *, split_size: int = 512, white: bool = False, ssim: bool = True,
+               image_size: Optional[Tuple[int, int]] = None) -> dict:
+    """One view rendered as ``render_view`` renders it (same chunks, same streams, same sparse colours: the same values for the same
+    random stream position) and scored against ``target_rgb`` ([H,W,3], or [H W,3] with ``image_size`` = (H, W)) on the device:
+    rgb and depth are scattered into [H,W,3] / [H,W] images by ``all_pixels`` (a pixel no ray names stays 0, as in the reference's
+    loop, methods.py:517-540), the rgb image goes through the byte quantisation of the PNG round trip, and
+    ``metrics2d.image_scores`` returns {"psnr", "ssim" (``ssim=True``), "depth_l1_cm" (with ``target_depth``, H W values in metres)}.
+    Nothing but the scores is downloaded."""
+    from . import geomargs, metrics2d
+    target = geomargs.as_tensor(target_rgb, "target_rgb")
+    if image_size is None:
+        if target.dim() != 3:
+            raise ValueError(f"target_rgb must be [H,W,3] when image_size is not given, got {tuple(target.shape)}")
+        image_size = (int(target.shape[0]), int(target.shape[1]))
+    h, w = int(image_size[0]), int(image_size[1])
+    if h < 1 or w < 1 or target.numel() != h * w * 3:
+        raise ValueError(f"target_rgb {tuple(target.shape)} does not hold {h} x {w} x 3 values")
+    target = target.reshape(h, w, 3)
+    depth_target = None
+    if target_depth is not None:
+        depth_target = geomargs.as_tensor(target_depth, "target_depth")
+        if depth_target.numel() != h * w:
+            raise ValueError(f"target_depth {tuple(depth_target.shape)} does not hold {h} x {w} values")
+        depth_target = depth_target.reshape(h, w)
+    chunk = max(int(split_size), MIN_CHUNK)
+    keep = getattr(model, "sparse_colours", False)
+    model.sparse_colours = bool(SPARSE_COLOURS) or keep
+    try:
+        rgb, depth = model.render_chunked(all_pose, all_pixels, all_intrinsics, epoch, chunk=chunk, n_streams=2, white=white)
+    finally:
+        model.sparse_colours = keep
+    dev = rgb.device
+    uv = all_pixels.to(dev)
+    rows, cols = uv[:, 1].long(), uv[:, 0].long()
+    image = torch.zeros(h, w, 3, device=dev)
+    image[rows, cols] = rgb
+    pred_depth = None
+    if depth_target is not None:
+        pred_depth = torch.zeros(h, w, device=dev)
+        pred_depth[rows, cols] = depth[:, 0]
+    return metrics2d.image_scores(image, target, quantize=True, ssim=ssim, pred_depth=pred_depth, target_depth=depth_target, device=dev)
+
+
+@torch.no_grad()
+def metrics(model, eval_path: str, dataset_config, epoch: int, split_size: int = 200, device: torch.device = torch.device("cuda")) -> None:
+    """Drop-in for ``evaluation.methods.metrics`` (methods.py:549-610): the same file checks, the same ``render_images`` call when an
+    image or a depth map is missing, the same loop over the dataset and the same ``metrics.json`` ({"image-{i}": {"psnr"}, "mean_psnr"}),
+    with the PSNR of every view computed on the device (``metrics2d.score_views``).  The PNGs are read through the reference's own
+    ``utils.load_rgb`` (image I/O stays the reference's); it returns byte / 255 as float32, from which ``rint(p * 255)`` recovers the byte
+    exactly whether skimage divides by 255 or multiplies by its reciprocal.  The values are the float64 specification's: they differ
+    from the reference's float32 ``get_psnr`` by its rounding, and the mean is taken in float64."""
+    from . import metrics2d
+    dataset_dict = importlib.import_module("datasets.normal_datasets").dataset_dict
+    utils = importlib.import_module("utils.utils")
+    dataset = dataset_dict[dataset_config.dataset_name](dataset_config)
+    dataset.all_pixels = True
+    images_path = os.path.join(eval_path, "rendered_images")
+    num_images = len(dataset)
+    image_paths = [os.path.join(images_path, f"image-{i}.png") for i in range(num_images)]
+    depth_paths = [os.path.join(images_path, f"depth-{i}.npy") for i in range(num_images)]
+    if not all(os.path.exists(path) for path in image_paths) or not all(os.path.exists(path) for path in depth_paths):
+        print("Not all images and depth maps exist. Rendering images and depth maps.")
+        try:                                       # the function evaluate.py would reach: the reference's, or the one install() put there
+            render = importlib.import_module("evaluation.methods").render_images
+        except ImportError:
+            render = render_images
+        render(model, eval_path, dataset_config, epoch, split_size, device)
+    dataloader = torch.utils.data.DataLoader(dataset, batch_size=1, shuffle=False)
+    rows, preds, targets = [], [], []
+
+    def flush():
+        if preds:
+            scored = metrics2d.score_views(preds, targets, device=device)
+            rows.extend(scored[f"image-{k}"] for k in range(len(preds)))
+            preds.clear()
+            targets.clear()
+
+    for i, batch in enumerate(dataloader):
+        if i >= num_images:
+            break
+        targets.append(batch["rgb"].squeeze(0).reshape(dataset.image_size[0], dataset.image_size[1], 3).float())
+        loaded = utils.load_rgb(image_paths[i])                                    # [3,H,W] float32 = byte / 255
+        preds.append(torch.from_numpy(np.rint(loaded.transpose(1, 2, 0).astype(np.float64) * 255.0).astype(np.uint8)))
+        if len(preds) == METRICS_CHUNK:
+            flush()
+    flush()
+    metrics_dict = metrics2d.views_dictionary(rows)
+    with open(os.path.join(eval_path, "metrics.json"), "w") as f:
+        json.dump(metrics_dict, f, indent=4)

@@ -46,6 +46,7 @@ EXPORTS = (
     "vfn_tsdf_integrate", "vfn_tsdf_count", "vfn_tsdf_emit",
     "vfn_raster_depth", "vfn_smooth_laplacian_step",
     "vfn_transform_points", "vfn_nn_radius", "vfn_icp_accumulate_workspace_bytes", "vfn_icp_accumulate",
+    "vfn_image_quantize8", "vfn_image_scores_workspace_bytes", "vfn_image_scores", "vfn_image_abs_err",
 )
 
 
@@ -1534,6 +1535,80 @@ def icp_check(status: int) -> None:
 def icp_sum_levels(n: int) -> int:
     """Addition levels of every sum of vfn_icp_accumulate over n rows: the tree of vfn_reduce_stats."""
     return reduce_sum_levels(n)
+
+
+# ------------------------------------------------------------------------------------------------
+# image scores (csrc/vfn_image.hip; vf_nerf_amd/metrics2d.py is the public surface).  Contiguous tensors on one device.
+# ------------------------------------------------------------------------------------------------
+IMAGE_STATUS_RANGE = 4             # info bit of vfn_image_quantize8: a value outside the range of a byte
+IMAGE_TOP = 1024                   # csrc/vfn_image.hip: IMG_TOP (lanes of the second level)
+SSIM_C1, SSIM_C2 = 1e-4, 9e-4      # utils/utils.py:249 (get_ssim's defaults)
+
+
+def image_tile() -> int:
+    return header_constant("VFN_IMAGE_TILE")
+
+
+def image_workspace_bytes(v: int, h: int, w: int, c: int) -> int:
+    b = int(load().vfn_image_scores_workspace_bytes(C.c_int64(v), C.c_int64(h), C.c_int64(w), C.c_int64(c)))
+    if b < 0:
+        raise VfnError(f"vfn_image_scores_workspace_bytes failed: {load().vfn_last_error().decode()}")
+    return b
+
+
+def image_quantize8(x: torch.Tensor, info: torch.Tensor) -> torch.Tensor:
+    """x float32 (any shape) -> uint8 of that shape: trunc(double(x) 255); ``info`` (int64 [1], zero-filled) collects the refusals."""
+    u = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(load().vfn_image_quantize8(_ptr(x, "x"), C.c_int64(x.numel()), _ptr(u, "u", torch.uint8), _ptr(info, "info", torch.int64),
+                                          _stream()), "vfn_image_quantize8")
+    return u
+
+
+def _image_operand(t: torch.Tensor, name: str):
+    if t.dtype not in (torch.uint8, torch.float32):
+        raise VfnError(f"{name}: expected uint8 or float32, got {t.dtype}")
+    return _ptr(t, name, t.dtype), C.c_int32(int(t.dtype == torch.uint8))
+
+
+def image_scores(pred: torch.Tensor, target: torch.Tensor, want_ssim: bool, info: torch.Tensor, c1: float = SSIM_C1,
+                 c2: float = SSIM_C2) -> torch.Tensor:
+    """pred, target [V,H,W,C] (uint8 or float32 each) -> sums[V,3] float64 on the device (include/vfn.h: vfn_image_scores)."""
+    if pred.dim() != 4 or pred.shape != target.shape or pred.device != target.device:
+        raise VfnError(f"image_scores: two [V,H,W,C] tensors of one shape on one device, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    v, h, w, c = pred.shape
+    dev = pred.device
+    ws = torch.empty(max(image_workspace_bytes(v, h, w, c), 1), dtype=torch.uint8, device=dev)
+    sums = torch.empty(v, 3, dtype=torch.float64, device=dev)
+    (pp, pu), (tp, tu) = _image_operand(pred, "pred"), _image_operand(target, "target")
+    with torch.cuda.device(dev):
+        _check(load().vfn_image_scores(pp, pu, tp, tu, C.c_int64(v), C.c_int64(h), C.c_int64(w), C.c_int64(c), C.c_int32(int(bool(want_ssim))),
+                                       C.c_double(c1), C.c_double(c2), _ptr(sums, "sums", torch.float64), _ptr(info, "info", torch.int64),
+                                       _ptr(ws, "workspace", torch.uint8), C.c_int64(ws.numel()), _stream()), "vfn_image_scores")
+    return sums
+
+
+def image_abs_err(a: torch.Tensor, b: torch.Tensor, scale: float, info: torch.Tensor) -> torch.Tensor:
+    """a, b [V,H,W] float32 -> sums[V] float64 on the device: sum |a s - b s| (include/vfn.h: vfn_image_abs_err)."""
+    if a.dim() != 3 or a.shape != b.shape or a.device != b.device:
+        raise VfnError(f"image_abs_err: two [V,H,W] tensors of one shape on one device, got {tuple(a.shape)} and {tuple(b.shape)}")
+    v, h, w = a.shape
+    dev = a.device
+    ws = torch.empty(max(image_workspace_bytes(v, h, w, 1), 1), dtype=torch.uint8, device=dev)
+    sums = torch.empty(v, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_image_abs_err(_ptr(a, "a"), _ptr(b, "b"), C.c_int64(v), C.c_int64(h), C.c_int64(w), C.c_double(scale),
+                                        _ptr(sums, "sums", torch.float64), _ptr(info, "info", torch.int64), _ptr(ws, "workspace", torch.uint8),
+                                        C.c_int64(ws.numel()), _stream()), "vfn_image_abs_err")
+    return sums
+
+
+def image_sum_levels(h: int, w: int, c: int) -> int:
+    """Addition levels of a per-view sum of vfn_image_scores: the lane's channels (c - 1), the tile tree (8), the serial run of the second
+    level (ceil(P / 1024) - 1, P = tiles per view), its tree (10)."""
+    t = image_tile()
+    p = ((h + t - 1) // t) * ((w + t - 1) // t)
+    return (c - 1) + 8 + ((p + IMAGE_TOP - 1) // IMAGE_TOP - 1) + 10
 
 
 # ------------------------------------------------------------------------------------------------
