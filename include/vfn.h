@@ -955,7 +955,8 @@ int vfn_smooth_laplacian_step(const double* src, double* dst, int64_t n_vertices
  * how often the parameter occurs in the optimizer's list (the reference lists every vector-field parameter twice,
  * models/nerf/vector_field_nerf.py:57-63): a gradient counts mult times in the norm, is scaled mult times, and its parameter
  * receives mult consecutive Adam updates per step, exactly what the sequential per-entry loops do.
- * vfn_flat_clip_grad_norm: out2[0] = total 2-norm, out2[1] = min(max_norm / (norm + 1e-6), 1); gradients scaled in place.
+ * vfn_flat_clip_grad_norm: out2[0] = total 2-norm, out2[1] = min(max_norm / (norm + 1e-6), 1), NaN where the norm is NaN
+ *   (torch.clamp(max=1): every gradient inside the regions becomes NaN then; an infinite norm gives 0); gradients scaled in place.
  *   workspace: vfn_flat_clip_workspace_bytes() bytes of device memory, zero-filled once by the caller.
  * vfn_flat_adam_step: step_size[2 r + k] = lr / (1 - beta1^t), bc2_sqrt[2 r + k] = sqrt(1 - beta2^t) for update k (t = the step
  *   number of that update) of region r, evaluated by the caller in double precision as torch.optim.Adam does. */

@@ -32,7 +32,7 @@ __device__ __forceinline__ int mult_of(const Regions& r, long long i) {
 }
 
 // partial[b] = sum over the block's elements of mult * g^2; the last block to arrive adds the partials up in index order
-// (deterministic) and writes out[0] = total norm, out[1] = clip coefficient = min(max_norm / (total + 1e-6), 1).
+// (deterministic) and writes out[0] = total norm, out[1] = clip coefficient = min(max_norm / (total + 1e-6), 1), NaN for a NaN norm.
 __global__ __launch_bounds__(256) void vfn_grad_norm_kernel(const float* g, long long n, Regions r, float max_norm, double* partial,
                                                             unsigned* counter, float* out) {
     __shared__ double red[256];
@@ -67,7 +67,8 @@ __global__ __launch_bounds__(256) void vfn_grad_norm_kernel(const float* g, long
         if (threadIdx.x == 0) {
             const float total = (float)sqrt(red[0]);
             out[0] = total;
-            out[1] = fminf(max_norm / (total + 1e-6f), 1.0f);
+            const float coef = max_norm / (total + 1e-6f);
+            out[1] = coef < 1.0f ? coef : (coef != coef ? coef : 1.0f);      // clamp(max=1): a NaN norm stays NaN (fminf would give 1), as torch
             *counter = 0u;            // ready for the next call
         }
     }

@@ -40,7 +40,7 @@ __device__ __forceinline__ void item_sums(const LossArgs& a, long long i, float 
     if (i < p.n_rays) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) s[S_RGB] += fabsf(a.rgb[i * 3 + c] - a.rgb_gt[i * 3 + c]);
-        if (p.has_depth) s[S_DEPTH] += fminf(fabsf(a.depth[i] - a.depth_gt[i]), p.depth_clamp);
+        if (p.has_depth) { const float e = fabsf(a.depth[i] - a.depth_gt[i]); s[S_DEPTH] += e > p.depth_clamp ? p.depth_clamp : e; }   // clamp(max=): NaN stays NaN (torch)
         return;
     }
     i -= p.n_rays;
@@ -48,7 +48,7 @@ __device__ __forceinline__ void item_sums(const LossArgs& a, long long i, float 
         const float x = a.normals[i * 3], y = a.normals[i * 3 + 1], z = a.normals[i * 3 + 2];
         const float n = vnorm(x, y, z);
         s[S_UNIT] += (n - 1.f) * (n - 1.f);
-        if (p.smaller_on) { const float r = fmaxf(n - 1.f, 0.f); s[S_SMALL] += r * r; }
+        if (p.smaller_on) { const float r = n - 1.f < 0.f ? 0.f : n - 1.f; s[S_SMALL] += r * r; }           // relu: NaN stays NaN (torch)
         if (p.ray_center) {
             const float dx = a.points[i * 3] - p.centroid[0], dy = a.points[i * 3 + 1] - p.centroid[1], dz = a.points[i * 3 + 2] - p.centroid[2];
             const float d = vnorm(dx, dy, dz);
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void vfn_loss_bwd_kernel(const LossArgs a) {
             const float x = a.normals[j * 3], y = a.normals[j * 3 + 1], z = a.normals[j * 3 + 2];
             const float n = vnorm(x, y, z);
             float f = 0.f;                                                  // d|n| = n / |n| (0 at the origin, as torch.linalg.vector_norm)
-            if (n > 0.f) {
+            if (!(n <= 0.f)) {                                              // (a NaN norm: f = NaN, all three components NaN, as torch)
                 f = k_unit * (n - 1.f);
                 if (p.smaller_on) f += k_small * fmaxf(n - 1.f, 0.f);
                 f /= n;

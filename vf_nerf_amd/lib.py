@@ -1076,20 +1076,24 @@ def vf_render_fused16_scatter(vf_geom, vf_packed16, rn_geom, rn_packed16, points
            "vfn_vf_render_fused16_scatter")
 
 
-def select_samples(weights, points, ray_dirs, sigma=None, z_vals=None):
+def select_samples(weights, points, ray_dirs, sigma=None, z_vals=None, return_all: bool = False, index_fill: Optional[int] = None):
     """The sparse colour branch's sample selection on its own (vfn_select_samples) -> the selected indices ray * S + j as a Python list
-    (synchronises: tests and diagnostics).  ``sigma`` / ``z_vals`` given: the training selection."""
+    (synchronises: tests and diagnostics).  ``sigma`` / ``z_vals`` given: the training selection.  ``return_all``: (count, the whole
+    index buffer [N S] — which held ``index_fill`` everywhere before the launch, if given —, points_sel[:count], dirs_sel[:count]) as
+    device tensors instead, without the gather check below."""
     n, s = weights.shape
     dev = weights.device
     scratch = torch.empty(2 * n, dtype=torch.int32, device=dev)
     count = torch.zeros(4, dtype=torch.int32, device=dev)
-    index = torch.empty(n * s, dtype=torch.int32, device=dev)
+    index = torch.empty(n * s, dtype=torch.int32, device=dev) if index_fill is None else torch.full((n * s,), int(index_fill), dtype=torch.int32, device=dev)
     pts_sel, dirs_sel = torch.empty(n * s, 3, device=dev), torch.empty(n * s, 3, device=dev)
     _check(load().vfn_select_samples(_ptr(weights, "weights"), _ptr(sigma, "sigma"), _ptr(z_vals, "z_vals"), C.c_int32(n), C.c_int32(s),
                                      _ptr(points, "points"), _ptr(ray_dirs, "ray_dirs"), _ptr(scratch, "scratch", torch.int32),
                                      _ptr(count, "count", torch.int32), _ptr(index, "index", torch.int32), _ptr(pts_sel, "points_sel"),
                                      _ptr(dirs_sel, "dirs_sel"), _stream()), "vfn_select_samples")
     k = int(count[0])
+    if return_all:
+        return k, index, pts_sel[:max(min(k, n * s), 0)], dirs_sel[:max(min(k, n * s), 0)]
     got = index[:k].tolist()
     flat = points.reshape(-1, 3)
     assert torch.equal(pts_sel[:k], flat[index[:k].long()]) and torch.equal(dirs_sel[:k], ray_dirs[(index[:k] // s).long()])
