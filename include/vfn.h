@@ -861,7 +861,8 @@ int vfn_image_abs_err(const float* a, const float* b, int64_t V, int64_t H, int6
  * maps and the mesh that metrics_3d scores, with the semantics of a uniform TSDF volume — projective integration with a running mean,
  * classic marching cubes on the zero level set.  Two deliberate differences: the volume is DENSE over a box the caller gives (not
  * hashed 16^3 blocks opened near back-projected points, so a voxel in free space in front of a surface collects tsdf = 1 observations
- * that a hashed volume would never have allocated; the zero crossing lies inside the truncation band either way), and no colour.
+ * that a hashed volume would never have allocated; the zero crossing lies inside the truncation band either way), and colour is
+ * optional: a volume without one keeps its entry points and its bits, a volume with one adds colour[nx, ny, nz, 3] (below).
  * Volume: tsdf[nx, ny, nz] and weight[nx, ny, nz], float32, C order (k fastest), zero-filled by the caller before the first view;
  * voxel (i, j, k) has its centre at origin + (index + 0.5) voxel_length.  nx ny nz < 2^31, voxel_length > 0, sdf_trunc > 0.
  *   vfn_tsdf_integrate  depth[V, H, W] (float32 metres, 0 = no measurement), intrinsics[V, 4] = fx fy cx cy, extrinsics[V, 12] = the
@@ -892,7 +893,26 @@ int vfn_image_abs_err(const float* a, const float* b, int64_t V, int64_t H, int6
  *                       position[axis] = position[axis] + (f_L / (f_L + f_U)) (double)vl
  *                     in float64 without contraction, so the cells around an edge emit identical bits and the positional merge joins
  *                     them; vertices that coincide at a corner whose tsdf is exactly 0 merge too, degenerate faces are kept.
- * Limits: 3 T < 2^31.  No atomics.
+ * Colour (evaluation/methods.py:626: TSDFVolumeColorType.RGB8, convert_rgb_to_intensity=False): colour[nx, ny, nz, 3], float32, C order,
+ * in byte units (0 .. 255), zero-filled by the caller before the first view.
+ *   vfn_tsdf_integrate_rgb  vfn_tsdf_integrate with colour and rgb[V, H, W, 3] (uint8).  Per voxel and view the tests and the tsdf /
+ *                     weight update are exactly those above; where that update is applied, each channel c is updated with the weight
+ *                     BEFORE its increment, in float32, every operation rounded once in the association written, no contraction:
+ *                       colour_c = (colour_c weight + (float)rgb[v, u, c]) / (weight + 1.0f)
+ *                     with (v, u) the pixel the depth was read from.  Views in index order per voxel (the bits of V single-view
+ *                     calls), the volume read and written once per call; tsdf and weight come out bit-identical to
+ *                     vfn_tsdf_integrate on the same inputs.
+ *   vfn_tsdf_emit_colours  counts / offsets from vfn_tsdf_count; tri_cols[3 T, 3] (double) in the slot layout of vfn_tsdf_emit.  For a
+ *                     cut edge with endpoints L, U and f = (double)|tsdf| as in the position formula, in float64 without contraction:
+ *                       r = f_L / (f_L + f_U)
+ *                       col[c] = ((1.0 - r) (double)colour_L[c] + r (double)colour_U[c]) / 255.0
+ *                     (r = 0 gives colour_L / 255 exactly, r = 1 gives colour_U / 255 exactly).
+ *   vfn_tsdf_vertex_colours  ids[S] (the slot -> vertex numbering of vfn_mesh_number), tri_cols[S, 3] -> colours[n_vertices, 3] (double): a
+ *                     vertex takes the colour of the slot at which it first appears, the LOWEST slot carrying its id — the slot whose
+ *                     position bits vfn_mesh_dedup keeps.  (Two different edges can round to one position with colours that differ in
+ *                     the last bit; equal colour bits on all slots of a vertex are not relied on.)  first[n_vertices] (int32) is
+ *                     workspace: the lowest slot per vertex, found with an integer atomicMin per slot.
+ * Limits: 3 T < 2^31.  No floating-point atomics; one integer atomicMin per slot in vfn_tsdf_vertex_colours only.
  * ============================================================================================= */
 int vfn_tsdf_integrate(float* tsdf, float* weight, int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz,
                        float voxel_length, float sdf_trunc, const float* depth, int32_t height, int32_t width,
@@ -901,6 +921,13 @@ int vfn_tsdf_count(const float* tsdf, const float* weight, int32_t nx, int32_t n
                    int64_t* info, void* scan_ws, int64_t scan_ws_bytes, void* stream);
 int vfn_tsdf_emit(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz,
                   float voxel_length, const int32_t* counts, const int32_t* offsets, double* tri_verts, void* stream);
+int vfn_tsdf_integrate_rgb(float* tsdf, float* weight, float* colour, int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz,
+                           float voxel_length, float sdf_trunc, const float* depth, const uint8_t* rgb, int32_t height, int32_t width,
+                           const float* intrinsics, const float* extrinsics, int32_t n_views, void* stream);
+int vfn_tsdf_emit_colours(const float* tsdf, const float* weight, const float* colour, int32_t nx, int32_t ny, int32_t nz,
+                          const int32_t* counts, const int32_t* offsets, double* tri_cols, void* stream);
+int vfn_tsdf_vertex_colours(const int64_t* ids, int64_t n_slots, const double* tri_cols, int32_t* first, int64_t n_vertices,
+                            double* colours, void* stream);
 
 /* =============================================================================================
  * Rasterising a mesh's depth, and Laplacian smoothing (csrc/vfn_raster.hip): what evaluation/methods.py:33-72 (refuse: the mesh's depth

@@ -14,6 +14,17 @@ inside an axis-aligned box [-0.6, 0.6]^3 looking at its walls, analytic plane de
 HIP events around each call, one warm-up call, --reps timed calls, the median reported (all repeats are listed).
 
     python tools/bench_tsdf.py [--res 512] [--views 100] [--height 680] [--width 1200] [--reps 3] [--out profiles/r09/bench_tsdf.json]
+
+--colour measures, INSTEAD of the rows above and in one process, alternating over --reps (plain, rgb, plain extract, coloured extract,
+plain, rgb, ...), on the same scene with pattern images (tests/tsdf_colour_restatement.py):
+
+    plain              the batched colourless integration (the `batched` row above: the same call).
+    rgb                ONE vfn_tsdf_integrate_rgb call over all views (colour[res^3, 3] next to tsdf and weight).
+    extract / extract_coloured   extract_mesh and extract_coloured_mesh of the fused volume.
+    bytes              the algorithmic traffic of both integrations: 16 B against 40 B per voxel (each array read and written once),
+                       and the image gathers: 4 B (depth) against 4 + 3 B (depth + rgb) per voxel-view that reaches the image.
+
+    python tools/bench_tsdf.py --colour [--reps 5] [--parent profiles/r09/bench_tsdf.json] [--out profiles/r13/bench_tsdf_colour.json]
 """
 import argparse
 import json
@@ -98,6 +109,73 @@ def cpu_baseline(res, vl, trunc, depths, k4s, e12s, workers):
     return time.perf_counter() - t0, observed
 
 
+def event_time(fn, before=None):
+    """One call between HIP events -> (seconds, result)."""
+    if before:
+        before()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / 1e3, out
+
+
+def colour_rows(args, dev, vl, trunc, poses, depths, k, e):
+    import tsdf_colour_restatement as C
+    from vf_nerf_amd import lib, tsdf
+    res, nv, h, w = args.res, args.views, args.height, args.width
+    rgb = torch.from_numpy(C.pattern_images(nv, h, w)).to(dev)
+    dims = (res, res, res)
+    plain_vol = tsdf.TSDFVolume((-0.7, -0.7, -0.7), dims, voxel_length=vl, sdf_trunc=trunc, device=dev)
+    rgb_vol = tsdf.TSDFVolume((-0.7, -0.7, -0.7), dims, voxel_length=vl, sdf_trunc=trunc, device=dev, colour=True)
+    box = (plain_vol.origin, plain_vol.voxel_length, plain_vol.sdf_trunc)
+    calls = {"plain": (lambda: lib.tsdf_integrate(plain_vol.tsdf, plain_vol.weight, *box, depths, k, e), plain_vol.reset),
+             "rgb": (lambda: lib.tsdf_integrate_rgb(rgb_vol.tsdf, rgb_vol.weight, rgb_vol.colour, *box, depths, rgb, k, e), rgb_vol.reset),
+             "extract": (plain_vol.extract_mesh, None), "extract_coloured": (rgb_vol.extract_coloured_mesh, None)}
+    times = {name: [] for name in calls}
+    meshes = {}
+    for rep in range(args.reps + 1):                     # round 0 is the warm-up; every round runs the four calls in the same order
+        for name, (fn, before) in calls.items():
+            t, out = event_time(fn, before)
+            if rep:
+                times[name].append(t)
+            if out is not None:
+                meshes[name] = out
+    same = torch.equal(plain_vol.tsdf.view(torch.int32), rgb_vol.tsdf.view(torch.int32)) and torch.equal(plain_vol.weight, rgb_vol.weight)
+    same_mesh = torch.equal(meshes["extract"][0], meshes["extract_coloured"][0]) and torch.equal(meshes["extract"][1], meshes["extract_coloured"][1])
+    voxels = res ** 3
+    voxel_views = float(rgb_vol.weight.sum())            # updates applied; the gathers also serve the voxel-views a test then rejects
+    rows = {name: {"seconds": round(statistics.median(ts), 6), "all_seconds": [round(x, 6) for x in ts],
+                   "spread": round((max(ts) - min(ts)) / statistics.median(ts), 4)} for name, ts in times.items()}
+    result = {"device": torch.cuda.get_device_name(0), "res": res, "views": nv, "map": [h, w], "voxel_length": vl, "sdf_trunc": trunc,
+              "reps": args.reps,
+              "timing": "HIP events per call; one warm-up round, then --reps rounds of plain, rgb, extract, extract_coloured in that order "
+                        "in one process; the volume is zeroed before every integration (untimed); median, all repeats, (max - min) / median",
+              **rows,
+              "rgb_over_plain": round(rows["rgb"]["seconds"] / rows["plain"]["seconds"], 3),
+              "extract_coloured_over_extract": round(rows["extract_coloured"]["seconds"] / rows["extract"]["seconds"], 3),
+              "tsdf_weight_bits_equal": bool(same), "mesh_bits_equal": bool(same_mesh),
+              "vertices": int(meshes["extract_coloured"][0].shape[0]), "faces": int(meshes["extract_coloured"][1].shape[0]),
+              "bytes": {"plain_volume": 16 * voxels, "rgb_volume": 40 * voxels, "per_voxel": [16, 40],
+                        "updates_applied": voxel_views, "plain_gather_at_least": 4 * voxel_views, "rgb_gather_at_least": 7 * voxel_views,
+                        "note": "volume: every array read and written once (tsdf + weight; + 3 colour floats); gathers: 4 B of depth, and 3 B "
+                                "of rgb more, per update applied — a lower bound: the depth (and, issued with it, the rgb) is also read for "
+                                "voxel-views that the d > 0 or the truncation test then rejects",
+                        "plain_floor_s": round(16 * voxels / COPY_RATE, 6), "rgb_floor_s": round(40 * voxels / COPY_RATE, 6)}}
+    if args.parent:
+        with open(args.parent) as fh:
+            parent = json.load(fh)["batched"]
+        result["parent"] = {"file": args.parent, "batched_seconds": parent["seconds"], "batched_all_seconds": parent["all_seconds"],
+                            "plain_over_parent": round(rows["plain"]["seconds"] / parent["seconds"], 4)}
+    print(json.dumps(result), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(result, fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, default=512)
@@ -110,6 +188,8 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extract", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--colour", action="store_true", help="plain / rgb integration and plain / coloured extraction, alternating, in one process")
+    ap.add_argument("--parent", default=None, help="--colour: an earlier bench_tsdf.json whose `batched` time the plain one is compared with")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_tsdf: no GPU visible (nothing here can be measured on a CPU)")
@@ -124,6 +204,8 @@ def main():
     depths = room_depths(poses, k4, h, w, dev)
     k = torch.from_numpy(np.tile(k4, (nv, 1))).to(dev)
     e = tsdf.extrinsics_from_poses(poses, nv).to(dev)
+    if args.colour:
+        return colour_rows(args, dev, vl, trunc, poses, depths, k, e)
     vol = tsdf.TSDFVolume((-0.7, -0.7, -0.7), (res, res, res), voxel_length=vl, sdf_trunc=trunc, device=dev)
     args_vol = (vol.tsdf, vol.weight, vol.origin, vol.voxel_length, vol.sdf_trunc)
 

@@ -16,7 +16,13 @@
 //              signs of the eight corner values (a corner with weight 0 voids the cell), the triangle count, the ordered scan, then
 //              every triangle's three float64 vertices at their slots in the layout vfn_mesh_dedup / vfn_mesh_number consume.  A vertex is a function of its edge alone, so the (up to) four
 //              cells around an edge emit identical bits and the positional merge joins them.
-// No atomics.  fp32 (integration) and fp64 (vertices) without contraction: -ffp-contract=off (build.sh), correctly rounded / and sqrtf.
+//   colour     the COLOUR instantiation of the integration kernel carries a lane's 4 x 3 colour floats next to tsdf and weight (three
+//              16-B accesses in the vector form) and reads the pixel's three bytes with byte loads, issued with the depth load; the
+//              colourless instantiation is the code it was (the colour arguments are an empty record at the END of its arguments).
+//              emit_colours is a second source over the same skeleton whose vertex() is a colour; vertex_colours picks, per vertex,
+//              the colour of the lowest slot that carries its id (an integer atomicMin per slot, then a gather).
+// No floating-point atomics.  fp32 (integration) and fp64 (vertices, colours) without contraction: -ffp-contract=off (build.sh),
+// correctly rounded / and sqrtf.
 #include "vfn_common.h"
 #include "vfn_mc_extract.h"    // EDGE_A / EDGE_B / INC, count -> scan -> total -> emit over a source
 
@@ -40,6 +46,13 @@ struct Views {
     const float* intr;         // [V, 4]: fx fy cx cy
     const float* extr;         // [V, 12]: world -> camera rows
     int n, h, w;
+};
+
+// what the COLOUR instantiation adds to the kernel's arguments; empty without colour
+template <bool COLOUR> struct Colour {};
+template <> struct Colour<true> {
+    float* colour;             // [nx, ny, nz, 3], byte units
+    const unsigned char* rgb;  // [V, H, W, 3]
 };
 
 __device__ __forceinline__ float centre(float o, int i, float vl) { return o + ((float)i + 0.5f) * vl; }
@@ -86,8 +99,9 @@ __device__ bool brick_may_see(const float* __restrict__ e, const float* __restri
 }
 
 // one view into the RUN voxels of a lane (include/vfn.h: the association is the contract)
-__device__ __forceinline__ void integrate_view(const Views& vs, int view, float x, float y, const float z[RUN], int cnt, float trunc,
-                                               float ts[RUN], float wt[RUN]) {
+template <bool COLOUR>
+__device__ __forceinline__ void integrate_view(const Views& vs, const Colour<COLOUR>& cl, int view, float x, float y, const float z[RUN], int cnt,
+                                               float trunc, float ts[RUN], float wt[RUN], float (*col)[3]) {
     const float* __restrict__ e = vs.extr + (long long)view * 12;
     const float* __restrict__ k = vs.intr + (long long)view * 4;
     const float* __restrict__ dv = vs.depth + (long long)view * vs.h * vs.w;
@@ -102,20 +116,30 @@ __device__ __forceinline__ void integrate_view(const Views& vs, int view, float 
         const float xc = (px + e[2] * z[r]) + e[3], yc = (py + e[6] * z[r]) + e[7];
         const float u = floorf(((xc * fx) / zc + cx) + 0.5f), v = floorf(((yc * fy) / zc + cy) + 0.5f);
         if (!(u >= 0.f && u < wf && v >= 0.f && v < hf)) continue;
-        const float d = dv[(long long)(int)v * vs.w + (int)u];
+        const long long pix = (long long)(int)v * vs.w + (int)u;
+        const float d = dv[pix];
+        float p[3] = {0.f, 0.f, 0.f};
+        if constexpr (COLOUR) {                               // the pixel the depth is read from; issued with it, used only below
+            const unsigned char* __restrict__ px = cl.rgb + ((long long)view * vs.h * vs.w + pix) * 3;
+            p[0] = (float)px[0]; p[1] = (float)px[1]; p[2] = (float)px[2];
+        }
         if (!(d > 0.f)) continue;
         const float a = (u - cx) / fx, b = (v - cy) / fy;
         const float m = sqrtf((1.0f + a * a) + b * b);
         const float sdf = (d - zc) * m;
         if (!(sdf > -trunc)) continue;
         const float t = fminf(1.0f, sdf / trunc);
+        if constexpr (COLOUR) {                               // with the weight BEFORE its increment
+#pragma unroll
+            for (int c = 0; c < 3; ++c) col[r][c] = (col[r][c] * wt[r] + p[c]) / (wt[r] + 1.0f);
+        }
         ts[r] = (ts[r] * wt[r] + t) / (wt[r] + 1.0f);
         wt[r] = wt[r] + 1.0f;
     }
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(THREADS) void vfn_tsdf_integrate_kernel(Volume vol, Views vs, int nbj, int nbk) {
+template <bool VEC, bool COLOUR>
+__global__ __launch_bounds__(THREADS) void vfn_tsdf_integrate_kernel(Volume vol, Views vs, int nbj, int nbk, Colour<COLOUR> cl) {
     __shared__ unsigned long long seen[THREADS / 64];
     const long long b = blockIdx.x;
     const int bk = (int)(b % nbk), bj = (int)((b / nbk) % nbj), bi = (int)(b / ((long long)nbk * nbj));
@@ -126,6 +150,7 @@ __global__ __launch_bounds__(THREADS) void vfn_tsdf_integrate_kernel(Volume vol,
     const long long off = ((long long)i * vol.ny + j) * vol.nz + k0;
 
     float ts[RUN] = {0.f, 0.f, 0.f, 0.f}, wt[RUN] = {0.f, 0.f, 0.f, 0.f}, z[RUN];
+    float col[COLOUR ? RUN : 1][3] = {};                     // a lane's 12 contiguous colour floats
     if (live) {
         if (VEC) {
             const float4 a = *reinterpret_cast<const float4*>(vol.tsdf + off), c = *reinterpret_cast<const float4*>(vol.weight + off);
@@ -133,6 +158,18 @@ __global__ __launch_bounds__(THREADS) void vfn_tsdf_integrate_kernel(Volume vol,
             wt[0] = c.x; wt[1] = c.y; wt[2] = c.z; wt[3] = c.w;
         } else {
             for (int r = 0; r < cnt; ++r) { ts[r] = vol.tsdf[off + r]; wt[r] = vol.weight[off + r]; }
+        }
+        if constexpr (COLOUR) {
+            if (VEC) {
+                const float4* __restrict__ q = reinterpret_cast<const float4*>(cl.colour + off * 3);
+                const float4 a = q[0], b4 = q[1], c = q[2];
+                col[0][0] = a.x; col[0][1] = a.y; col[0][2] = a.z; col[1][0] = a.w;
+                col[1][1] = b4.x; col[1][2] = b4.y; col[2][0] = b4.z; col[2][1] = b4.w;
+                col[2][2] = c.x; col[3][0] = c.y; col[3][1] = c.z; col[3][2] = c.w;
+            } else {
+                for (int r = 0; r < cnt; ++r)
+                    for (int c = 0; c < 3; ++c) col[r][c] = cl.colour[(off + r) * 3 + c];
+            }
         }
     }
     const float x = centre(vol.ox, i, vol.vl), y = centre(vol.oy, j, vol.vl);
@@ -157,12 +194,12 @@ __global__ __launch_bounds__(THREADS) void vfn_tsdf_integrate_kernel(Volume vol,
             while (m_lo) {                                    // ascending view order
                 const int bit = __builtin_ctz(m_lo);
                 m_lo &= m_lo - 1;
-                integrate_view(vs, base + g * 64 + bit, x, y, z, cnt, vol.trunc, ts, wt);
+                integrate_view<COLOUR>(vs, cl, base + g * 64 + bit, x, y, z, cnt, vol.trunc, ts, wt, col);
             }
             while (m_hi) {
                 const int bit = __builtin_ctz(m_hi);
                 m_hi &= m_hi - 1;
-                integrate_view(vs, base + g * 64 + 32 + bit, x, y, z, cnt, vol.trunc, ts, wt);
+                integrate_view<COLOUR>(vs, cl, base + g * 64 + 32 + bit, x, y, z, cnt, vol.trunc, ts, wt, col);
             }
         }
         __syncthreads();
@@ -175,10 +212,32 @@ __global__ __launch_bounds__(THREADS) void vfn_tsdf_integrate_kernel(Volume vol,
         } else {
             for (int r = 0; r < cnt; ++r) { vol.tsdf[off + r] = ts[r]; vol.weight[off + r] = wt[r]; }
         }
+        if constexpr (COLOUR) {
+            if (VEC) {
+                float4* __restrict__ q = reinterpret_cast<float4*>(cl.colour + off * 3);
+                q[0] = make_float4(col[0][0], col[0][1], col[0][2], col[1][0]);
+                q[1] = make_float4(col[1][1], col[1][2], col[2][0], col[2][1]);
+                q[2] = make_float4(col[2][2], col[3][0], col[3][1], col[3][2]);
+            } else {
+                for (int r = 0; r < cnt; ++r)
+                    for (int c = 0; c < 3; ++c) cl.colour[(off + r) * 3 + c] = col[r][c];
+            }
+        }
     }
 }
 
 // ---- extraction -------------------------------------------------------------------------------------------------------
+// cut edge e of a cell: its axis, and its endpoints as corner numbers — L the one with the lower lattice index, U the other
+__device__ __forceinline__ void edge_ends(int e, int& ql, int& qu, int& axis) {
+    const int qa = EDGE_A[e], qb = EDGE_B[e];
+    axis = 0;
+    if (INC[qa][1] != INC[qb][1]) axis = 1;
+    if (INC[qa][2] != INC[qb][2]) axis = 2;
+    const bool a_low = INC[qa][axis] < INC[qb][axis];
+    ql = a_low ? qa : qb;
+    qu = a_low ? qb : qa;
+}
+
 // the TSDF source of vfn_mc_extract.h: it never sets a status
 struct Lattice {
     using Value = float;
@@ -213,12 +272,8 @@ struct Lattice {
 
     // the vertex of cut edge e of the cell: a function of the edge alone (its lower endpoint L, its axis, the two values)
     __device__ __forceinline__ void vertex(const int c[3], const float v[8], const Emit&, int e, double out[3]) const {
-        const int qa = EDGE_A[e], qb = EDGE_B[e];
-        int axis = 0;
-        if (INC[qa][1] != INC[qb][1]) axis = 1;
-        if (INC[qa][2] != INC[qb][2]) axis = 2;
-        const bool a_low = INC[qa][axis] < INC[qb][axis];
-        const int ql = a_low ? qa : qb, qu = a_low ? qb : qa;
+        int ql, qu, axis;
+        edge_ends(e, ql, qu, axis);
         const double vld = (double)vl;
         const double o[3] = {(double)ox, (double)oy, (double)oz};
 #pragma unroll
@@ -227,6 +282,49 @@ struct Lattice {
         out[axis] = out[axis] + (fl / (fl + fu)) * vld;
     }
 };
+
+// the same cells through the same skeleton, with a colour where the lattice source has a position (include/vfn.h: vfn_tsdf_emit_colours)
+struct LatticeColours {
+    using Value = float;
+    using Emit = Lattice::Emit;
+    Lattice at;
+    const float* colour;      // [nx, ny, nz, 3]
+
+    __host__ __device__ long long positions() const { return at.positions(); }
+    __device__ __forceinline__ bool eval(long long p, int c[3], float v[8], int& top, unsigned& status) const { return at.eval(p, c, v, top, status); }
+    __device__ __forceinline__ void emit_setup(const int[3], Emit&) const {}
+
+    __device__ __forceinline__ void vertex(const int c[3], const float v[8], const Emit&, int e, double out[3]) const {
+        int ql, qu, axis;
+        edge_ends(e, ql, qu, axis);
+        const long long il = ((long long)(c[0] + INC[ql][0]) * at.ny + (c[1] + INC[ql][1])) * at.nz + (c[2] + INC[ql][2]);
+        const long long iu = ((long long)(c[0] + INC[qu][0]) * at.ny + (c[1] + INC[qu][1])) * at.nz + (c[2] + INC[qu][2]);
+        const double fl = fabs((double)v[ql]), fu = fabs((double)v[qu]);
+        const double r = fl / (fl + fu);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+            out[ch] = ((1.0 - r) * (double)colour[il * 3 + ch] + r * (double)colour[iu * 3 + ch]) / 255.0;
+    }
+};
+
+// first[v] = the lowest slot whose id is v (first is filled with a value above every slot before)
+__global__ __launch_bounds__(256) void vfn_tsdf_first_slot_kernel(const long long* __restrict__ ids, long long n_slots, int* __restrict__ first,
+                                                                  long long n_vert) {
+    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_slots) return;
+    const long long v = ids[s];
+    if (v >= 0 && v < n_vert) atomicMin(first + v, (int)s);
+}
+
+__global__ __launch_bounds__(256) void vfn_tsdf_gather_colours_kernel(const double* __restrict__ tri_cols, long long n_slots,
+                                                                      const int* __restrict__ first, long long n_vert, double* __restrict__ colours) {
+    const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_vert) return;
+    const long long s = first[v];
+    const bool ok = s >= 0 && s < n_slots;                    // (a vertex no slot names: cannot come from vfn_mesh_number; zeros, not a fault)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) colours[v * 3 + c] = ok ? tri_cols[s * 3 + c] : 0.0;
+}
 
 int check_dims(int32_t nx, int32_t ny, int32_t nz, float vl, const char* what) {
     VFN_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1 && (long long)nx * ny < (1ll << 31) && (long long)nx * ny * nz < (1ll << 31),
@@ -244,30 +342,53 @@ int make_lattice(Lattice& a, const float* tsdf, const float* weight, int32_t nx,
     return VFN_OK;
 }
 
+// the checks and the launch of both integrating entry points; `colour` / `rgb` are read only by the COLOUR instantiation
+template <bool COLOUR>
+int integrate(const char* what, float* tsdf, float* weight, float* colour, int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz,
+              float voxel_length, float sdf_trunc, const float* depth, const unsigned char* rgb, int32_t height, int32_t width,
+              const float* intrinsics, const float* extrinsics, int32_t n_views, void* stream) {
+    const int rc = check_dims(nx, ny, nz, voxel_length, what);
+    if (rc != VFN_OK) return rc;
+    VFN_REQUIRE(tsdf && weight && (!COLOUR || colour), "%s: NULL volume", what);
+    VFN_REQUIRE(sdf_trunc > 0.f && sdf_trunc - sdf_trunc == 0.f, "%s: sdf_trunc must be positive and finite", what);
+    VFN_REQUIRE(n_views >= 0 && height >= 1 && width >= 1 && (long long)height * width < (1ll << 31),
+                "%s: bad views (%d of %d x %d)", what, n_views, height, width);
+    if (n_views == 0) return VFN_OK;
+    VFN_REQUIRE(depth && intrinsics && extrinsics && (!COLOUR || rgb), "%s: NULL view argument", what);
+    const long long nbi = (nx + BI - 1) / BI, nbj = (ny + BJ - 1) / BJ, nbk = (nz + BK - 1) / BK;
+    const long long bricks = nbi * nbj * nbk;
+    VFN_REQUIRE(bricks < (1ll << 31), "%s: %lld bricks exceed one launch", what, bricks);
+    Volume vol{tsdf, weight, nx, ny, nz, ox, oy, oz, voxel_length, sdf_trunc};
+    Views vs{depth, intrinsics, extrinsics, n_views, height, width};
+    Colour<COLOUR> cl;
+    // 16-B accesses need rows of a multiple of four voxels and 16-B aligned arrays (a lane's 12 colour floats then start on a multiple
+    // of 48 B); anything else takes the scalar form
+    bool vec = nz % RUN == 0 && ((uintptr_t)tsdf & 15) == 0 && ((uintptr_t)weight & 15) == 0;
+    if constexpr (COLOUR) {
+        cl.colour = colour;
+        cl.rgb = rgb;
+        vec = vec && ((uintptr_t)colour & 15) == 0;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (vec) hipLaunchKernelGGL((vfn_tsdf_integrate_kernel<true, COLOUR>), dim3((unsigned)bricks), dim3(THREADS), 0, s, vol, vs, (int)nbj, (int)nbk, cl);
+    else hipLaunchKernelGGL((vfn_tsdf_integrate_kernel<false, COLOUR>), dim3((unsigned)bricks), dim3(THREADS), 0, s, vol, vs, (int)nbj, (int)nbk, cl);
+    return vfn_check_launch(what);
+}
+
 }  // namespace
 
 extern "C" int vfn_tsdf_integrate(float* tsdf, float* weight, int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz,
                                   float voxel_length, float sdf_trunc, const float* depth, int32_t height, int32_t width,
                                   const float* intrinsics, const float* extrinsics, int32_t n_views, void* stream) {
-    const int rc = check_dims(nx, ny, nz, voxel_length, "vfn_tsdf_integrate");
-    if (rc != VFN_OK) return rc;
-    VFN_REQUIRE(tsdf && weight, "vfn_tsdf_integrate: NULL volume");
-    VFN_REQUIRE(sdf_trunc > 0.f && sdf_trunc - sdf_trunc == 0.f, "vfn_tsdf_integrate: sdf_trunc must be positive and finite");
-    VFN_REQUIRE(n_views >= 0 && height >= 1 && width >= 1 && (long long)height * width < (1ll << 31),
-                "vfn_tsdf_integrate: bad views (%d of %d x %d)", n_views, height, width);
-    if (n_views == 0) return VFN_OK;
-    VFN_REQUIRE(depth && intrinsics && extrinsics, "vfn_tsdf_integrate: NULL view argument");
-    const long long nbi = (nx + BI - 1) / BI, nbj = (ny + BJ - 1) / BJ, nbk = (nz + BK - 1) / BK;
-    const long long bricks = nbi * nbj * nbk;
-    VFN_REQUIRE(bricks < (1ll << 31), "vfn_tsdf_integrate: %lld bricks exceed one launch", bricks);
-    Volume vol{tsdf, weight, nx, ny, nz, ox, oy, oz, voxel_length, sdf_trunc};
-    Views vs{depth, intrinsics, extrinsics, n_views, height, width};
-    // 16-B accesses need rows of a multiple of four voxels and 16-B aligned arrays; anything else takes the scalar form
-    const bool vec = nz % RUN == 0 && ((uintptr_t)tsdf & 15) == 0 && ((uintptr_t)weight & 15) == 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (vec) hipLaunchKernelGGL(vfn_tsdf_integrate_kernel<true>, dim3((unsigned)bricks), dim3(THREADS), 0, s, vol, vs, (int)nbj, (int)nbk);
-    else hipLaunchKernelGGL(vfn_tsdf_integrate_kernel<false>, dim3((unsigned)bricks), dim3(THREADS), 0, s, vol, vs, (int)nbj, (int)nbk);
-    return vfn_check_launch("vfn_tsdf_integrate");
+    return integrate<false>("vfn_tsdf_integrate", tsdf, weight, nullptr, nx, ny, nz, ox, oy, oz, voxel_length, sdf_trunc, depth, nullptr, height,
+                            width, intrinsics, extrinsics, n_views, stream);
+}
+
+extern "C" int vfn_tsdf_integrate_rgb(float* tsdf, float* weight, float* colour, int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz,
+                                      float voxel_length, float sdf_trunc, const float* depth, const uint8_t* rgb, int32_t height, int32_t width,
+                                      const float* intrinsics, const float* extrinsics, int32_t n_views, void* stream) {
+    return integrate<true>("vfn_tsdf_integrate_rgb", tsdf, weight, colour, nx, ny, nz, ox, oy, oz, voxel_length, sdf_trunc, depth, rgb, height,
+                           width, intrinsics, extrinsics, n_views, stream);
 }
 
 extern "C" int vfn_tsdf_count(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, int32_t* counts, int32_t* offsets,
@@ -284,4 +405,33 @@ extern "C" int vfn_tsdf_emit(const float* tsdf, const float* weight, int32_t nx,
     const int rc = make_lattice(a, tsdf, weight, nx, ny, nz, ox, oy, oz, voxel_length, "vfn_tsdf_emit");
     if (rc != VFN_OK) return rc;
     return vfn_mc_emit(a, counts, offsets, tri_verts, (hipStream_t)stream, "vfn_tsdf_emit");
+}
+
+extern "C" int vfn_tsdf_emit_colours(const float* tsdf, const float* weight, const float* colour, int32_t nx, int32_t ny, int32_t nz,
+                                     const int32_t* counts, const int32_t* offsets, double* tri_cols, void* stream) {
+    LatticeColours a;
+    const int rc = make_lattice(a.at, tsdf, weight, nx, ny, nz, 0.f, 0.f, 0.f, 1.f, "vfn_tsdf_emit_colours");
+    if (rc != VFN_OK) return rc;
+    VFN_REQUIRE(colour, "vfn_tsdf_emit_colours: NULL colour volume");
+    a.colour = colour;
+    return vfn_mc_emit(a, counts, offsets, tri_cols, (hipStream_t)stream, "vfn_tsdf_emit_colours");
+}
+
+extern "C" int vfn_tsdf_vertex_colours(const int64_t* ids, int64_t n_slots, const double* tri_cols, int32_t* first, int64_t n_vertices,
+                                       double* colours, void* stream) {
+    VFN_REQUIRE(n_slots >= 0 && n_slots < (1ll << 31) && n_vertices >= 0 && n_vertices <= n_slots,
+                "vfn_tsdf_vertex_colours: %lld vertices of %lld slots are outside the limits", (long long)n_vertices, (long long)n_slots);
+    if (n_vertices == 0) return VFN_OK;
+    VFN_REQUIRE(ids && tri_cols && first && colours, "vfn_tsdf_vertex_colours: NULL argument");
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(first, 0x7f, (size_t)n_vertices * sizeof(int32_t), s);      // 0x7f7f7f7f: above every slot
+    if (e != hipSuccess) {
+        vfn_set_error("vfn_tsdf_vertex_colours: memset failed: %s", hipGetErrorString(e));
+        return VFN_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(vfn_tsdf_first_slot_kernel, dim3(blocks_for(n_slots)), dim3(256), 0, s, (const long long*)ids, (long long)n_slots,
+                       (int*)first, (long long)n_vertices);
+    hipLaunchKernelGGL(vfn_tsdf_gather_colours_kernel, dim3(blocks_for(n_vertices)), dim3(256), 0, s, tri_cols, (long long)n_slots,
+                       (const int*)first, (long long)n_vertices, colours);
+    return vfn_check_launch("vfn_tsdf_vertex_colours");
 }

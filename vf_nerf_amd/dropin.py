@@ -37,7 +37,7 @@ def _ensure_package(name: str) -> None:
 
 
 def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scalars=None, patch_mesh: bool = True,
-            patch_metrics: bool = False) -> None:
+            patch_metrics: bool = False, patch_tsdf_mesh: bool = False) -> None:
     """``patch_clip=False`` leaves ``torch.nn.utils.clip_grad_norm_`` PyTorch's own function (no process-wide replacement): a step session then
     parks its gradient in the optimizer's flat buffer with every ``param.grad`` None, the trainer's clip call finds nothing to scale, and
     ``optimizer.step()`` all-reduces (more than one rank), clips with the model's ``scheduler_config.clip_norm`` — the value the trainer
@@ -52,7 +52,10 @@ def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scal
     (the device triangulation, same (vs, fs)); ``patch_mesh=False`` restores the reference's function.
     ``patch_metrics=True`` replaces ``evaluation.methods.metrics`` with ``evaluator.metrics`` (the image scores on the device, a float64
     specification: the PSNR values differ from the reference's float32 ones by its rounding) and keeps the reference's function as
-    ``methods._reference_metrics``; the default leaves it alone, and ``False`` after ``True`` puts it back."""
+    ``methods._reference_metrics``; the default leaves it alone, and ``False`` after ``True`` puts it back.
+    ``patch_tsdf_mesh=True`` replaces ``evaluation.methods.tsdf_mesh`` with ``evaluator.tsdf_mesh`` (RGBD fusion on the device, a dense
+    volume: the coloured ``tsdf-mesh/tsdf.ply`` without vertex normals) and keeps the reference's function as
+    ``methods._reference_tsdf_mesh``; off by default, and ``False`` after ``True`` puts it back."""
     for dotted, module in _ALIASES.items():
         parts = dotted.split(".")
         for i in range(1, len(parts)):
@@ -87,6 +90,12 @@ def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scal
             methods.metrics = evaluator.metrics
         elif hasattr(methods, "_reference_metrics"):
             methods.metrics = methods._reference_metrics
+        if patch_tsdf_mesh:
+            if not hasattr(methods, "_reference_tsdf_mesh"):
+                methods._reference_tsdf_mesh = methods.tsdf_mesh
+            methods.tsdf_mesh = evaluator.tsdf_mesh
+        elif hasattr(methods, "_reference_tsdf_mesh"):
+            methods.tsdf_mesh = methods._reference_tsdf_mesh
     except Exception:
         pass
     # evaluation/utils/marching_cubes_vt.contrastive_marching_cubes (a Python loop over every surface cell) -> the device triangulation;

@@ -10,7 +10,10 @@ unchanged.
 
 ``score_view`` renders a view the same way and scores it against its target on the device (``vf_nerf_amd.metrics2d``) without
 downloading the image; ``metrics`` is the drop-in for ``evaluation.methods.metrics`` (methods.py:549-610: the PNGs written by
-``render_images`` scored against the dataset's images, ``metrics.json``), installed by ``dropin.install(patch_metrics=True)``."""
+``render_images`` scored against the dataset's images, ``metrics.json``), installed by ``dropin.install(patch_metrics=True)``.
+
+``tsdf_mesh`` is the drop-in for ``evaluation.methods.tsdf_mesh`` (methods.py:613-665: the rendered depth maps and PNGs fused into the
+coloured ``tsdf-mesh/tsdf.ply``), installed by ``dropin.install(patch_tsdf_mesh=True)``."""
 from __future__ import annotations
 
 import importlib
@@ -180,3 +183,35 @@ def metrics(model, eval_path: str, dataset_config, epoch: int, split_size: int =
     metrics_dict = metrics2d.views_dictionary(rows)
     with open(os.path.join(eval_path, "metrics.json"), "w") as f:
         json.dump(metrics_dict, f, indent=4)
+
+
+@torch.no_grad()
+def tsdf_mesh(eval_path: str, dataset_config) -> None:
+    """Drop-in for ``evaluation.methods.tsdf_mesh`` (methods.py:613-665): every ``rendered_images/depth-{i}.npy`` with its
+    ``image-{i}.png`` (read with PIL: the PNG's bytes) and the dataset's intrinsics / poses — per view for ``dtu`` / ``deepfashion``,
+    shared otherwise — fused WITH colour on the device (``tsdf.fuse_rgbd_maps``: voxel length 4/512, ``sdf_trunc`` 0.04, the depth as
+    ``tsdf.reference_depth`` states the reference's millimetre round trip, the box of the back-projected depths) and written to
+    ``tsdf-mesh/tsdf.ply`` (``ply.write_ply``: binary, float vertices, uchar colours).  Vertex normals are not written (the reference
+    calls ``compute_vertex_normals()`` first).  Installed by ``dropin.install(patch_tsdf_mesh=True)``."""
+    from PIL import Image
+    from . import ply, tsdf
+    dataset_dict = importlib.import_module("datasets.normal_datasets").dataset_dict
+    dataset = dataset_dict[dataset_config.dataset_name](dataset_config)
+    images_path = os.path.join(eval_path, "rendered_images")
+    n = len([name for name in os.listdir(images_path) if name.endswith(".npy") and name.startswith("depth")])
+    if n < 1:
+        raise FileNotFoundError(f"no depth-*.npy under {images_path}")
+    depths, images, intrinsics, poses = [], [], [], []
+    for i in range(n):
+        depth = np.load(os.path.join(images_path, f"depth-{i}.npy"))
+        depth = depth[..., 0] if depth.ndim == 3 else depth
+        with Image.open(os.path.join(images_path, f"image-{i}.png")) as png:
+            images.append(np.asarray(png.convert("RGB"), dtype=np.uint8))
+        depths.append(tsdf.reference_depth(np.ascontiguousarray(depth)))
+        k = dataset.intrinsics[i] if dataset_config.dataset_name in ["dtu", "deepfashion"] else dataset.intrinsics
+        intrinsics.append(torch.as_tensor(k).detach().cpu().to(torch.float64)[:3, :3])
+        poses.append(torch.as_tensor(dataset.poses[i]).detach().cpu().to(torch.float64))
+    vertices, faces, colours = tsdf.fuse_rgbd_maps(torch.stack(depths), np.stack(images), torch.stack(intrinsics), torch.stack(poses))
+    mesh_path = os.path.join(eval_path, "tsdf-mesh")
+    os.makedirs(mesh_path, exist_ok=True)
+    ply.write_ply(os.path.join(mesh_path, "tsdf.ply"), vertices, faces, colours)

@@ -43,7 +43,7 @@ EXPORTS = (
     "vfn_mesh_field_norms",
     "vfn_nn_sqdist", "vfn_tri_areas", "vfn_cumsum_workspace_bytes", "vfn_cumsum_f64", "vfn_sample_surface",
     "vfn_reduce_stats_workspace_bytes", "vfn_reduce_stats",
-    "vfn_tsdf_integrate", "vfn_tsdf_count", "vfn_tsdf_emit",
+    "vfn_tsdf_integrate", "vfn_tsdf_count", "vfn_tsdf_emit", "vfn_tsdf_integrate_rgb", "vfn_tsdf_emit_colours", "vfn_tsdf_vertex_colours",
     "vfn_raster_depth", "vfn_smooth_laplacian_step",
     "vfn_transform_points", "vfn_nn_radius", "vfn_icp_accumulate_workspace_bytes", "vfn_icp_accumulate",
     "vfn_image_quantize8", "vfn_image_scores_workspace_bytes", "vfn_image_scores", "vfn_image_abs_err",
@@ -1282,6 +1282,12 @@ def _extract(count, emit, cells: int, dev, what: str, check_status=None):
     stream of ``dev`` -> (vertices[V,3] float64, faces[F,3] int64, 0-based).  ``count`` and ``emit`` are the unit's entry points closed
     over the source's leading arguments; they receive the trailing ones.  Two values cross to the host, each to size the next outputs:
     the triangle count — with the input status, handed to ``check_status`` — and the vertex count."""
+    return _extract_slots(count, emit, cells, dev, what, check_status)[:2]
+
+
+def _extract_slots(count, emit, cells: int, dev, what: str, check_status=None, per_slot=None):
+    """``_extract`` -> (vertices, faces, extra).  ``per_slot(scanned, ids, n_vertices)`` runs on a non-empty mesh after the numbering,
+    with the counts / offsets pointers the entry points received and the slot -> vertex ids[3 F]; its result is ``extra`` (None otherwise)."""
     from .geomargs import empty_mesh          # (geomargs imports this module)
     with torch.cuda.device(dev):
         info = torch.zeros(4, dtype=torch.int64, device=dev)
@@ -1297,11 +1303,12 @@ def _extract(count, emit, cells: int, dev, what: str, check_status=None):
         if n_tri < 0 or n_slots >= (1 << 31):
             raise VfnError(f"{what}: {n_tri} triangles exceed the 2^31 / 3 limit")
         if n_tri == 0:
-            return empty_mesh(dev)
+            return empty_mesh(dev) + (None,)
         tri_verts = torch.empty(n_slots, 3, dtype=torch.float64, device=dev)
         emit(*scanned, _ptr(tri_verts, "tri_verts", torch.float64), _stream())
         vertices, ids = mesh_dedup(tri_verts, info=info)
-    return vertices, ids.view(n_tri, 3)
+        extra = per_slot(scanned, ids, vertices.shape[0]) if per_slot is not None else None
+    return vertices, ids.view(n_tri, 3), extra
 
 
 def mesh_triangulate(form: int, m: int, res: int, size: float, isovalue: float, comb: Optional[torch.Tensor] = None,
@@ -1634,6 +1641,14 @@ def tsdf_integrate(tsdf: torch.Tensor, weight: torch.Tensor, origin: Sequence[fl
     """All views of depth[V,H,W] (intrinsics[V,4] = fx fy cx cy, extrinsics[V,12] = world -> camera rows) into the volume, in place, in one
     pass over it; origin / voxel_length / sdf_trunc are taken as float32.  See include/vfn.h for the arithmetic."""
     vol = _tsdf_volume_args(tsdf, weight)
+    v, h, w = _tsdf_view_args(tsdf, depth, intrinsics, extrinsics)
+    with torch.cuda.device(tsdf.device):
+        _check(load().vfn_tsdf_integrate(*vol, *(C.c_float(float(o)) for o in origin), C.c_float(float(voxel_length)), C.c_float(float(sdf_trunc)),
+                                         _ptr(depth, "depth"), C.c_int32(h), C.c_int32(w), _ptr(intrinsics, "intrinsics"),
+                                         _ptr(extrinsics, "extrinsics"), C.c_int32(v), _stream()), "vfn_tsdf_integrate")
+
+
+def _tsdf_view_args(tsdf: torch.Tensor, depth: torch.Tensor, intrinsics: torch.Tensor, extrinsics: torch.Tensor, rgb=None):
     if depth.dim() != 3:
         raise VfnError(f"depth must be [V,H,W], got {tuple(depth.shape)}")
     v, h, w = depth.shape
@@ -1641,13 +1656,32 @@ def tsdf_integrate(tsdf: torch.Tensor, weight: torch.Tensor, origin: Sequence[fl
         raise VfnError(f"{v} views need intrinsics [{v},4] and extrinsics [{v},12], got {tuple(intrinsics.shape)} and {tuple(extrinsics.shape)}")
     if h < 1 or w < 1 or h * w >= (1 << 31) or v >= (1 << 31):
         raise VfnError(f"{v} depth maps of {h} x {w} are outside the limits of one call")
-    for t in (depth, intrinsics, extrinsics):
+    if rgb is not None and tuple(rgb.shape) != (v, h, w, 3):
+        raise VfnError(f"{v} depth maps of {h} x {w} need rgb [{v},{h},{w},3], got {tuple(rgb.shape)}")
+    for t in (depth, intrinsics, extrinsics) + (() if rgb is None else (rgb,)):
         if t.device != tsdf.device:
             raise VfnError("the views and the volume live on different devices")
+    return v, h, w
+
+
+def _tsdf_colour_arg(tsdf: torch.Tensor, colour: torch.Tensor):
+    if tuple(colour.shape) != tuple(tsdf.shape) + (3,) or colour.device != tsdf.device:
+        raise VfnError(f"colour must be [nx,ny,nz,3] on the volume's device, got {tuple(colour.shape)} on {colour.device}")
+    return _ptr(colour, "colour")
+
+
+def tsdf_integrate_rgb(tsdf: torch.Tensor, weight: torch.Tensor, colour: torch.Tensor, origin: Sequence[float], voxel_length: float,
+                       sdf_trunc: float, depth: torch.Tensor, rgb: torch.Tensor, intrinsics: torch.Tensor, extrinsics: torch.Tensor) -> None:
+    """``tsdf_integrate`` with the views' images: rgb[V,H,W,3] uint8 into colour[nx,ny,nz,3] float32 (byte units), the running mean of the
+    pixels whose depth updated the voxel.  tsdf / weight come out as ``tsdf_integrate`` leaves them.  See include/vfn.h."""
+    vol = _tsdf_volume_args(tsdf, weight)
+    col = _tsdf_colour_arg(tsdf, colour)
+    v, h, w = _tsdf_view_args(tsdf, depth, intrinsics, extrinsics, rgb)
     with torch.cuda.device(tsdf.device):
-        _check(load().vfn_tsdf_integrate(*vol, *(C.c_float(float(o)) for o in origin), C.c_float(float(voxel_length)), C.c_float(float(sdf_trunc)),
-                                         _ptr(depth, "depth"), C.c_int32(h), C.c_int32(w), _ptr(intrinsics, "intrinsics"),
-                                         _ptr(extrinsics, "extrinsics"), C.c_int32(v), _stream()), "vfn_tsdf_integrate")
+        _check(load().vfn_tsdf_integrate_rgb(vol[0], vol[1], col, *vol[2:], *(C.c_float(float(o)) for o in origin), C.c_float(float(voxel_length)),
+                                             C.c_float(float(sdf_trunc)), _ptr(depth, "depth"), _ptr(rgb, "rgb", torch.uint8), C.c_int32(h),
+                                             C.c_int32(w), _ptr(intrinsics, "intrinsics"), _ptr(extrinsics, "extrinsics"), C.c_int32(v),
+                                             _stream()), "vfn_tsdf_integrate_rgb")
 
 
 def tsdf_extract(tsdf: torch.Tensor, weight: torch.Tensor, origin: Sequence[float], voxel_length: float):
@@ -1658,6 +1692,33 @@ def tsdf_extract(tsdf: torch.Tensor, weight: torch.Tensor, origin: Sequence[floa
     return _extract(lambda *out: _check(load().vfn_tsdf_count(*vol, *out), "vfn_tsdf_count"),
                     lambda *out: _check(load().vfn_tsdf_emit(*vol, *box, *out), "vfn_tsdf_emit"),
                     (nx - 1) * (ny - 1) * (nz - 1), tsdf.device, "TSDF extraction")
+
+
+def tsdf_extract_coloured(tsdf: torch.Tensor, weight: torch.Tensor, colour: torch.Tensor, origin: Sequence[float], voxel_length: float):
+    """``tsdf_extract`` with vertex colours -> (vertices, faces, colours[n,3] float64 in [0,1]): the vertices and faces are those of
+    ``tsdf_extract``; a vertex takes the colour of the slot at which it first appears (include/vfn.h)."""
+    vol = _tsdf_volume_args(tsdf, weight)
+    col = _tsdf_colour_arg(tsdf, colour)
+    nx, ny, nz = tsdf.shape
+    dev = tsdf.device
+    box = tuple(C.c_float(float(o)) for o in origin) + (C.c_float(float(voxel_length)),)
+
+    def colours_of(scanned, ids, n):
+        n_slots = ids.shape[0]
+        tri_cols = torch.empty(n_slots, 3, dtype=torch.float64, device=dev)
+        _check(load().vfn_tsdf_emit_colours(vol[0], vol[1], col, *vol[2:], *scanned, _ptr(tri_cols, "tri_cols", torch.float64), _stream()),
+               "vfn_tsdf_emit_colours")
+        first = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        out = torch.empty(n, 3, dtype=torch.float64, device=dev)
+        _check(load().vfn_tsdf_vertex_colours(_ptr(ids, "ids", torch.int64), C.c_int64(n_slots), _ptr(tri_cols, "tri_cols", torch.float64),
+                                              _ptr(first, "first", torch.int32), C.c_int64(n), _ptr(out, "colours", torch.float64) if n else None,
+                                              _stream()), "vfn_tsdf_vertex_colours")
+        return out
+
+    vertices, faces, colours = _extract_slots(lambda *out: _check(load().vfn_tsdf_count(*vol, *out), "vfn_tsdf_count"),
+                                              lambda *out: _check(load().vfn_tsdf_emit(*vol, *box, *out), "vfn_tsdf_emit"),
+                                              (nx - 1) * (ny - 1) * (nz - 1), dev, "TSDF extraction", per_slot=colours_of)
+    return vertices, faces, colours if colours is not None else torch.empty(0, 3, dtype=torch.float64, device=dev)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -16,8 +16,9 @@ Everything stays on the device between the stages; a mesh is ``(vertices float64
 ``metrics_3d(..., icp_align=True)`` aligns every mesh's samples to the ground truth's before scoring (``vf_nerf_amd.icp``, a
 specification of ours, not verified against Open3D).
 
-Out of scope: colour (the reference fuses the dataset's RGB along with the depth; nothing it reports depends on it), PLY reading /
-writing.
+``refuse_rgbd`` is ``refuse`` with the views' images fused along with the depth, as the reference's ``refuse()`` does (nothing it reports
+depends on the colour; the mesh it returns is coloured) -> (vertices, faces, vertex colours); ``vf_nerf_amd.ply`` reads and writes PLY
+files.  Out of scope: vertex normals in the PLY, trimesh's vertex merging.
 """
 from __future__ import annotations
 
@@ -40,14 +41,35 @@ def refuse(mesh, intrinsics, poses, height: int, width: int, bounds=None, voxel_
     """Render the mesh's depth from every view, drop depths >= ``depth_trunc``, fuse the maps again -> (vertices, faces).  ``bounds`` as
     in ``tsdf.fuse_depth_maps`` (None: the back-projected depth points, padded by ``sdf_trunc``).  Two empty tensors when no camera
     sees anything."""
+    return _refuse(mesh, None, intrinsics, poses, height, width, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc,
+                   depth_trunc=depth_trunc, near=near, far=far, pixel_centre=pixel_centre, device=device)
+
+
+def refuse_rgbd(mesh, rgb, intrinsics, poses, height: int, width: int, **refuse_args):
+    """``refuse`` WITH the views' images, what the reference's ``refuse()`` fuses (methods.py:56-62: the dataset's rgb as bytes next to the
+    mesh's rendered depth) -> (vertices, faces, vertex_colours float64 [n,3] in [0,1]).  ``rgb`` is uint8 [V,height,width,3] (or
+    [height,width,3] for one view), or float32 in [0, 1] quantised as ``metrics2d.quantize_rgb8`` does — trunc(x 255), the reference's
+    ``(rgb * 255).astype(np.uint8)``.  ``refuse_args`` are ``refuse``'s; the vertices and faces are ``refuse``'s."""
+    if rgb is None:
+        raise ValueError("rgb is required (refuse re-fuses depth alone)")
+    return _refuse(mesh, rgb, intrinsics, poses, height, width, **refuse_args)
+
+
+def _refuse(mesh, rgb, intrinsics, poses, height, width, bounds=None, voxel_length=tsdf.VOXEL_LENGTH, sdf_trunc=tsdf.SDF_TRUNC,
+            depth_trunc=DEPTH_TRUNC, near=raster.NEAR, far=raster.FAR, pixel_centre=raster.PIXEL_CENTRE, device=None):
     if isinstance(depth_trunc, bool) or not isinstance(depth_trunc, (int, float, np.integer, np.floating)) or not float(depth_trunc) > 0:
         raise ValueError(f"depth_trunc must be a positive number, got {depth_trunc!r}")
     vl, _ = geomargs.positive32(voxel_length, "voxel_length"), geomargs.positive32(sdf_trunc, "sdf_trunc")
     if bounds is not None:
         tsdf.bounds_box(bounds, vl)                                        # every refusal that needs no device comes before the first launch
+    if rgb is not None:
+        n_views = 1 if geomargs.as_tensor(poses, "poses").dim() == 2 else int(geomargs.as_tensor(poses, "poses").shape[0])
+        tsdf._stack_rgb(rgb, (n_views, height, width))
     depth = raster.rasterize_depth_counted(mesh, intrinsics, poses, height, width, near=near, far=far, pixel_centre=pixel_centre, device=device)[0]
     depth = torch.where(depth >= float(depth_trunc), torch.zeros_like(depth), depth)
-    return tsdf.fuse_depth_maps(depth, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depth.device)
+    if rgb is None:
+        return tsdf.fuse_depth_maps(depth, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depth.device)
+    return tsdf.fuse_rgbd_maps(depth, rgb, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depth.device)
 
 
 def vertex_adjacency(faces: torch.Tensor, n_vertices: int) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -2,26 +2,33 @@
 ``render-images`` and ``3d-metrics`` — the mesh that ``metrics_3d`` scores for a trained VF-NeRF — without leaving the device.
 
 * ``TSDFVolume`` — a dense truncated-signed-distance volume: ``integrate`` fuses one depth map or a stack of them in ONE pass over the
-  volume, ``extract_mesh`` triangulates the zero level set with classic marching cubes.
+  volume, ``extract_mesh`` triangulates the zero level set with classic marching cubes.  ``TSDFVolume(..., colour=True)`` fuses every
+  view's RGB image together with its depth (the reference's ``TSDFVolumeColorType.RGB8``); ``extract_coloured_mesh`` adds a colour per
+  vertex.
 * ``reference_depth`` — a depth map as ``tsdf_mesh`` hands it to the fusion: millimetres as uint16, truncated at ``depth_trunc``.
 * ``fuse_depth_maps`` — depth maps + cameras -> mesh; the box defaults to the back-projected valid depth points, padded by ``sdf_trunc``.
+  ``fuse_rgbd_maps`` — the same with the views' images -> (vertices, faces, vertex colours).
 * ``fuse_rendered_views`` — a model's views rendered (``VectorFieldNerf.render_chunked``, as ``evaluator.render_view``), their depth
-  maps kept on the device and fused; only the mesh leaves it.
+  maps kept on the device and fused; only the mesh leaves it.  ``fuse_rendered_rgbd`` keeps the rendered rgb too (as the bytes of the
+  PNG ``render_images`` writes) and returns the coloured mesh; ``vf_nerf_amd.ply.write_ply`` writes it as the reference's ``tsdf.ply``.
 
 The semantics are modelled on a uniform TSDF volume's integration and extraction as ``tsdf_mesh`` drives one (voxel length 4/512,
 ``sdf_trunc`` 0.04, extrinsic = inv(pose)); include/vfn.h states the arithmetic operation for operation and tests/tsdf_restatement.py
-restates it in NumPy, which the device equals bit for bit.  Two deliberate differences from the reference's fusion:
+restates it in NumPy (tests/tsdf_colour_restatement.py: the colour), which the device equals bit for bit.  One deliberate difference
+from the reference's fusion:
 
 * the volume is DENSE over a box the caller gives, not hashed 16^3 blocks opened near back-projected points.  A voxel in free space in
   front of a surface therefore collects ``tsdf = 1`` observations here in cases where the hashed volume would never have allocated it;
-  the zero crossing lies inside the truncation band either way;
-* no colour is fused.
+  the zero crossing lies inside the truncation band either way.
 
 A mesh is ``(vertices float64 [n,3], faces int64 [m,3])``, 0-based, on the device — the form ``mesh.triangulate`` returns and
-``metrics3d.score_mesh`` accepts.  No CPU fallback: ``lib.VfnError`` when no device is visible.
+``metrics3d.score_mesh`` accepts; a coloured mesh adds ``colours float64 [n,3]`` in [0, 1].  A volume without colour keeps its kernels
+and its bits; the geometry of a coloured volume is bit-equal to the colourless one's.  No CPU fallback: ``lib.VfnError`` when no device
+is visible.
 
 ``refuse()`` and Laplacian smoothing (``tsdf-smoothed.ply``) are ``vf_nerf_amd.refuse``: a mesh's depth rasterised on the device
-(``vf_nerf_amd.raster``) and re-fused by this volume.  Out of scope: colour, PLY reading / writing.
+(``vf_nerf_amd.raster``) and re-fused by this volume.  PLY reading / writing is ``vf_nerf_amd.ply``.  Out of scope: vertex normals in
+the PLY (the reference calls ``compute_vertex_normals()`` before writing), the hashed volume.
 """
 from __future__ import annotations
 
@@ -110,6 +117,29 @@ def _stack_depths(depth, name: str = "depth") -> torch.Tensor:
     return d
 
 
+def _stack_rgb(rgb, views_shape, name: str = "rgb") -> torch.Tensor:
+    """The images that go with depth maps of ``views_shape`` = (V, H, W): uint8 or float32, [V,H,W,3] (or [H,W,3] for one view) ->
+    [V,H,W,3] as given (any device, not yet bytes).  Any other dtype or shape is refused."""
+    c = geomargs.as_tensor(rgb, name)
+    if c.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"{name} must be uint8 (bytes) or float32 (in [0, 1], quantised as the PNG is), got {c.dtype}")
+    if c.dim() == 3:
+        c = c.unsqueeze(0)
+    if c.dim() != 4 or c.shape[-1] != 3:
+        raise ValueError(f"{name} must be [H,W,3] or [V,H,W,3], got {tuple(geomargs.as_tensor(rgb, name).shape)}")
+    if tuple(c.shape[:3]) != tuple(views_shape):
+        raise ValueError(f"{name} of {tuple(c.shape[:3])} views x pixels does not go with depth maps of {tuple(views_shape)}")
+    return c
+
+
+def _rgb_bytes(c: torch.Tensor, dev) -> torch.Tensor:
+    """``_stack_rgb``'s result as contiguous uint8 on ``dev``; float32 goes through ``metrics2d.quantize_rgb8`` (the PNG's bytes)."""
+    if c.dtype == torch.float32:
+        from . import metrics2d
+        return metrics2d.quantize_rgb8(c, device=dev).contiguous()
+    return c.to(dev).contiguous()
+
+
 def reference_depth(depth_map, depth_scale: float = DEPTH_SCALE, depth_trunc: float = DEPTH_TRUNC) -> torch.Tensor:
     """A depth map in metres as ``tsdf_mesh`` feeds it to the fusion (evaluation/methods.py:651-657): q = trunc(float64(depth) depth_scale) as
     uint16, d = float32(q) / float32(depth_scale), d = 0 where d >= depth_trunc.  Non-finite, negative or >= 65.536 m (at the default
@@ -129,9 +159,10 @@ def reference_depth(depth_map, depth_scale: float = DEPTH_SCALE, depth_trunc: fl
 class TSDFVolume:
     """A dense TSDF volume of ``dims = (nx, ny, nz)`` voxels of ``voxel_length`` whose first voxel's corner is ``origin``: voxel (i, j, k)
     has its centre at origin + (index + 0.5) voxel_length.  ``tsdf`` / ``weight`` are float32 [nx,ny,nz] device tensors, zero until a
-    view has been integrated."""
+    view has been integrated.  ``colour=True`` adds ``colour`` float32 [nx,ny,nz,3] in byte units (else None): every ``integrate`` then
+    needs the views' images."""
 
-    def __init__(self, origin, dims, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC, device=None):
+    def __init__(self, origin, dims, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC, device=None, colour: bool = False):
         self.dims = _check_dims(dims)
         self.voxel_length = geomargs.positive32(voxel_length, "voxel_length")
         self.sdf_trunc = geomargs.positive32(sdf_trunc, "sdf_trunc")
@@ -142,26 +173,43 @@ class TSDFVolume:
         self.device = geomargs.device(device, "TSDF fusion")
         self.tsdf = torch.zeros(self.dims, dtype=torch.float32, device=self.device)
         self.weight = torch.zeros(self.dims, dtype=torch.float32, device=self.device)
+        self.colour = torch.zeros(self.dims + (3,), dtype=torch.float32, device=self.device) if colour else None
 
     def reset(self) -> None:
         self.tsdf.zero_()
         self.weight.zero_()
+        if self.colour is not None:
+            self.colour.zero_()
 
-    def integrate(self, depth, intrinsics, pose) -> None:
+    def integrate(self, depth, intrinsics, pose, rgb=None) -> None:
         """One depth map [H,W] or a stack [V,H,W] (float metres, 0 = no measurement; host or device tensors or NumPy) with intrinsics
         [3,3] / [4,4] shared or per view and camera-to-world poses [4,4] / [V,4,4].  The V views are fused in index order by ONE kernel
-        that reads and writes the volume once: the bits of V single-view calls."""
+        that reads and writes the volume once: the bits of V single-view calls.  ``rgb`` — required exactly when the volume has colour —
+        is the views' images, uint8 [V,H,W,3] / [H,W,3], or float32 in [0, 1] sent through ``metrics2d.quantize_rgb8``."""
         d = _stack_depths(depth)
         v = d.shape[0]
+        if (rgb is None) != (self.colour is None):
+            raise ValueError("rgb is required by a volume with colour" if rgb is None else "rgb was given to a volume without colour")
+        c = None if rgb is None else _stack_rgb(rgb, d.shape)
         k = split_intrinsics(intrinsics, v)
         e = extrinsics_from_poses(pose, v)
         _check_depth_values(d, "depth")
         d = d.to(self.device, torch.float32).contiguous()
-        lib.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel_length, self.sdf_trunc, d, k.to(self.device), e.to(self.device))
+        if c is None:
+            lib.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel_length, self.sdf_trunc, d, k.to(self.device), e.to(self.device))
+        else:
+            lib.tsdf_integrate_rgb(self.tsdf, self.weight, self.colour, self.origin, self.voxel_length, self.sdf_trunc, d,
+                                   _rgb_bytes(c, self.device), k.to(self.device), e.to(self.device))
 
     def extract_mesh(self):
         """-> (vertices float64 [n,3], faces int64 [m,3], 0-based) on the device; two empty tensors when nothing crosses zero."""
         return lib.tsdf_extract(self.tsdf, self.weight, self.origin, self.voxel_length)
+
+    def extract_coloured_mesh(self):
+        """``extract_mesh`` of a volume with colour -> (vertices, faces, colours float64 [n,3] in [0,1]): the same vertices and faces."""
+        if self.colour is None:
+            raise ValueError("extract_coloured_mesh needs a volume with colour (TSDFVolume(..., colour=True))")
+        return lib.tsdf_extract_coloured(self.tsdf, self.weight, self.colour, self.origin, self.voxel_length)
 
 
 def depth_bounds(depths: torch.Tensor, k: torch.Tensor, poses: torch.Tensor) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
@@ -208,9 +256,23 @@ def fuse_depth_maps(depths, intrinsics, poses, bounds=None, voxel_length: float 
     """Depth maps [V,H,W] (or one [H,W]) with their cameras -> (vertices, faces): one volume, one integration pass, one extraction.
     ``bounds`` = (min[3], max[3]) of the box; None: the min / max of the back-projected valid depth points, padded by ``sdf_trunc``.
     The box is covered by ceil(extent / voxel_length) voxels per axis (at least one)."""
+    return _fuse_maps(depths, None, intrinsics, poses, bounds, voxel_length, sdf_trunc, device)
+
+
+def fuse_rgbd_maps(depths, colours, intrinsics, poses, bounds=None, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC,
+                   device=None):
+    """``fuse_depth_maps`` with the views' images ``colours`` (uint8 [V,H,W,3] / [H,W,3], or float32 in [0, 1] quantised as the PNG is)
+    -> (vertices, faces, vertex_colours float64 [n,3] in [0,1]); the vertices and faces are ``fuse_depth_maps``' for the same depths."""
+    if colours is None:
+        raise ValueError("colours is required (fuse_depth_maps fuses depth alone)")
+    return _fuse_maps(depths, colours, intrinsics, poses, bounds, voxel_length, sdf_trunc, device)
+
+
+def _fuse_maps(depths, colours, intrinsics, poses, bounds, voxel_length, sdf_trunc, device):
     vl, tr = geomargs.positive32(voxel_length, "voxel_length"), geomargs.positive32(sdf_trunc, "sdf_trunc")
     d = _stack_depths(depths, "depths")
     v = d.shape[0]
+    c = None if colours is None else _stack_rgb(colours, d.shape, "colours")
     k = split_intrinsics(intrinsics, v)
     e = extrinsics_from_poses(poses, v)
     _check_depth_values(d, "depths")                           # (on whatever device the maps live)
@@ -221,11 +283,14 @@ def fuse_depth_maps(depths, intrinsics, poses, bounds=None, voxel_length: float 
         p = geomargs.as_tensor(poses, "poses").cpu()
         found = depth_bounds(d, k, p.unsqueeze(0) if p.dim() == 2 else p)
         if found is None:
-            return geomargs.empty_mesh(dev)
+            return geomargs.empty_mesh(dev) + (() if c is None else (torch.empty(0, 3, dtype=torch.float64, device=dev),))
         box = bounds_box((found[0].numpy() - tr, found[1].numpy() + tr), vl)
-    vol = TSDFVolume(box[0], box[1], voxel_length=vl, sdf_trunc=tr, device=dev)
-    lib.tsdf_integrate(vol.tsdf, vol.weight, vol.origin, vol.voxel_length, vol.sdf_trunc, d, k.to(dev), e.to(dev))
-    return vol.extract_mesh()
+    vol = TSDFVolume(box[0], box[1], voxel_length=vl, sdf_trunc=tr, device=dev, colour=c is not None)
+    if c is None:
+        lib.tsdf_integrate(vol.tsdf, vol.weight, vol.origin, vol.voxel_length, vol.sdf_trunc, d, k.to(dev), e.to(dev))
+        return vol.extract_mesh()
+    lib.tsdf_integrate_rgb(vol.tsdf, vol.weight, vol.colour, vol.origin, vol.voxel_length, vol.sdf_trunc, d, _rgb_bytes(c, dev), k.to(dev), e.to(dev))
+    return vol.extract_coloured_mesh()
 
 
 @torch.no_grad()
@@ -233,6 +298,21 @@ def render_depth_maps(model, poses, intrinsics, height: int, width: int, epoch: 
                       n_streams: int = 2, min_chunk: Optional[int] = None) -> torch.Tensor:
     """Every pixel of every view rendered as ``evaluator.render_view`` renders it (``VectorFieldNerf.render_chunked`` with sparse
     colours, chunks of max(split_size, min_chunk) rays) -> depth maps [V,height,width] float32 that stay on the device."""
+    return _render_maps(model, poses, intrinsics, height, width, epoch, split_size, white, n_streams, min_chunk, False)[0]
+
+
+@torch.no_grad()
+def render_rgbd_maps(model, poses, intrinsics, height: int, width: int, epoch: int, split_size: int = 512, white: bool = False,
+                     n_streams: int = 2, min_chunk: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``render_depth_maps`` keeping the rgb ``render_chunked`` returns next to the depth -> (depth maps [V,height,width] float32, images
+    [V,height,width,3] uint8 — ``metrics2d.quantize_rgb8``: the bytes of the PNG ``render_images`` writes), both on the device.  The
+    depth maps are ``render_depth_maps``' for the same random stream."""
+    from . import metrics2d
+    depth, rgb = _render_maps(model, poses, intrinsics, height, width, epoch, split_size, white, n_streams, min_chunk, True)
+    return depth, metrics2d.quantize_rgb8(rgb, device=depth.device)
+
+
+def _render_maps(model, poses, intrinsics, height, width, epoch, split_size, white, n_streams, min_chunk, keep_rgb):
     from . import evaluator
     p = geomargs.as_tensor(poses, "poses").to(torch.float32)
     p = p.unsqueeze(0) if p.dim() == 2 else p
@@ -255,15 +335,18 @@ def render_depth_maps(model, poses, intrinsics, height: int, width: int, epoch: 
     uv = torch.stack([uu.reshape(-1), vv.reshape(-1)], dim=1).to(dev)
     chunk = max(int(split_size), int(evaluator.MIN_CHUNK if min_chunk is None else min_chunk))
     out = torch.empty(v, height, width, dtype=torch.float32, device=dev)
+    images = torch.empty(v, height, width, 3, dtype=torch.float32, device=dev) if keep_rgb else None
     keep = getattr(model, "sparse_colours", False)
     model.sparse_colours = bool(evaluator.SPARSE_COLOURS) or keep
     try:
         for i in range(v):
-            _, depth = model.render_chunked(p[i].to(dev), uv, k[i].to(dev), epoch, chunk=chunk, n_streams=n_streams, white=white)
+            rgb, depth = model.render_chunked(p[i].to(dev), uv, k[i].to(dev), epoch, chunk=chunk, n_streams=n_streams, white=white)
             out[i] = depth.reshape(height, width)
+            if keep_rgb:
+                images[i] = rgb.reshape(height, width, 3)
     finally:
         model.sparse_colours = keep
-    return out
+    return out, images
 
 
 @torch.no_grad()
@@ -283,3 +366,19 @@ def fuse_rendered_views(model, poses, intrinsics, height: int, width: int, epoch
     if as_reference:
         depths = reference_depth(depths, depth_scale=depth_scale, depth_trunc=depth_trunc)
     return fuse_depth_maps(depths, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depths.device)
+
+
+@torch.no_grad()
+def fuse_rendered_rgbd(model, poses, intrinsics, height: int, width: int, epoch: int, bounds=None, voxel_length: float = VOXEL_LENGTH,
+                       sdf_trunc: float = SDF_TRUNC, as_reference: bool = True, depth_scale: float = DEPTH_SCALE,
+                       depth_trunc: float = DEPTH_TRUNC, split_size: int = 512, white: bool = False, n_streams: int = 2,
+                       min_chunk: Optional[int] = None):
+    """``fuse_rendered_views`` with colour: the same arguments and the same depth handling, the rendered rgb kept as the PNG's bytes
+    (``render_rgbd_maps``) and fused with the depth -> (vertices, faces, vertex_colours).  The vertices and faces are
+    ``fuse_rendered_views``' for the same random stream; ``ply.write_ply`` writes the result as the reference's ``tsdf.ply``."""
+    depths, images = render_rgbd_maps(model, poses, intrinsics, height, width, epoch, split_size=split_size, white=white, n_streams=n_streams,
+                                      min_chunk=min_chunk)
+    depths = torch.where(depths < 0, torch.zeros_like(depths), depths)
+    if as_reference:
+        depths = reference_depth(depths, depth_scale=depth_scale, depth_trunc=depth_trunc)
+    return fuse_rgbd_maps(depths, images, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depths.device)
