@@ -745,12 +745,30 @@ int vfn_mesh_field_norms(const float* field, int64_t n, float* norms, float* uni
  *                     zero-area face is never chosen; a = u[i,1], b = u[i,2], and if a + b > 1 then a = 1 - a, b = 1 - b;
  *                     points[i, c] = (v0[c] + a e1[c]) + b e2[c] with e1 = v1 - v0, e2 = v2 - v0.  Writes points[count, 3] and
  *                     face_index[count] (int64).  A chosen face with an index outside [0, V): info[0] |= 2, point 0.
- *   vfn_reduce_stats  reads x[n]; writes stats[4] = sum, min, max, number of x[i] < threshold (as a double: exact).  A fixed two-level
- *                     tree without floating-point atomics: block b joins x[4096 b, 4096 (b + 1)) — 16 values per lane as a balanced
- *                     tree (4 levels), 256 lanes as a balanced tree (8 levels) — into one partial; one block of 1024 lanes joins the
- *                     P = ceil(n / 4096) partials, a lane its partials l, l + 1024, ... serially, then a balanced tree (10 levels).
+ *   vfn_reduce_stats  reads x[n]; writes stats[4] = sum, min, max, number of x[i] < threshold (as a double: exact), each along THE FIXED
+ *                     TREE below with the lane order "far"; values past n join as the identity.
  *                     workspace: vfn_reduce_stats_workspace_bytes(n) bytes (the partials); -1 on error.
+ *
+ * THE FIXED TREE (csrc/vfn_tree.h) joins the sums of vfn_reduce_stats, vfn_icp_accumulate, vfn_image_scores and vfn_image_abs_err: two
+ * launches, no floating-point atomics, the bits a function of the sizes and the data alone.  A join of two values puts the value of the
+ * lower slot, lane or partial on the left.
+ *   Tile.  Block b owns the VFN_TREE_LANES x VFN_TREE_PER = 256 x 16 = 4096 values [4096 b, 4096 (b + 1)); lane l owns the value
+ *   4096 b + l + 256 k in its slot k, k < 16.  A value past n is the identity: +0.0 for a sum, +inf for a minimum, -inf for a maximum,
+ *   0 for a count.  (The image sums have no slots: a tile is 16 x 16 pixels and a lane owns one value, see there.)
+ *   Lane tree.  A lane joins its 16 slots as a balanced tree of 4 levels, in one of two orders, named by the slots that meet first:
+ *     "near"  slot k with slot k + 1: ((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7)), ... — vfn_icp_accumulate;
+ *     "far"   slot k with slot k + 8: ((v0 + v8) + (v4 + v12)) + ((v2 + v10) + (v6 + v14)), ... — the "near" tree over the slots in
+ *             4-bit bit-reversed order 0, 8, 4, 12, 2, 10, 6, 14, 1, 9, ... — vfn_reduce_stats.
+ *   Block tree.  The 256 lane values join as a balanced tree of 8 levels: lane l takes lane l + d for d = 128, 64, ... 1.  Lane 0's value
+ *   is the block's partial; the partials lie in the workspace in block order.
+ *   Second level.  One block of VFN_TREE_TOP = 1024 lanes joins the P partials: lane l starts from partial l (the identity if l >= P),
+ *   joins the partials l + 1024, l + 2048, ... serially in that order, then the block tree over 1024 lanes (d = 512 ... 1, 10 levels).
+ *   Depth.  A sum is (lane levels) + 8 + (ceil(P / 1024) - 1) + 10 additions deep; lane levels = 4 with P = ceil(n / 4096) for
+ *   vfn_reduce_stats and vfn_icp_accumulate, C - 1 with P = the tiles of a view for the image sums.
  * ============================================================================================= */
+#define VFN_TREE_LANES 256            /* lanes of a first-level block of the fixed tree */
+#define VFN_TREE_PER 16               /* values a lane owns */
+#define VFN_TREE_TOP 1024             /* lanes of the second level */
 int vfn_nn_sqdist(const double* queries, int64_t n, const double* targets, int64_t m, double* best, int64_t* info, void* stream);
 int vfn_tri_areas(const double* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces, double* areas, int64_t* info,
                   void* stream);
@@ -792,12 +810,10 @@ int vfn_reduce_stats(const double* x, int64_t n, double threshold, double* stats
  *                     (each difference rounded once):
  *                       sums[0] = the number of rows (exact), sums[1] = sum sqdist[i], sums[2 + a] = sum p_a, sums[5 + a] = sum s_a,
  *                       sums[8 + 3 a + b] = sum p_a s_b (the product rounded once).
- *                     The fixed two-level tree of vfn_reduce_stats, no floating-point atomics: block b joins the rows
- *                     [4096 b, 4096 (b + 1)) — a lane's 16 rows as a balanced tree (4 levels), 256 lanes as a balanced tree (8 levels);
- *                     one block of 1024 lanes joins the P = ceil(n / 4096) partials, a lane its partials l, l + 1024, ... serially,
- *                     then a balanced tree (10 levels): every sum is 4 + 8 + (ceil(P / 1024) - 1) + 10 additions deep, a function of
- *                     n alone.  Rows without a neighbour and rows past n join as the identity (+ 0.0).  An index >= m: info[0] |= 2,
- *                     the row is skipped.  workspace: vfn_icp_accumulate_workspace_bytes(n) bytes (the partials); -1 on error.
+ *                     Every sum goes along THE FIXED TREE (above, after vfn_reduce_stats) over the n rows with the lane order "near"
+ *                     — not the order of vfn_reduce_stats: the same shape and depth, other pairs.  Rows without a neighbour and rows
+ *                     past n join as the identity (+0.0).  An index >= m: info[0] |= 2, the row is skipped.
+ *                     workspace: vfn_icp_accumulate_workspace_bytes(n) bytes (the partials); -1 on error.
  * ============================================================================================= */
 #define VFN_ICP_GRID_CAP 128          /* cells per axis at most */
 #define VFN_ICP_GRID_MARGIN_LOG2 20   /* the cell edge is at least radius (1 + 2^-20) */
@@ -838,13 +854,11 @@ int vfn_icp_accumulate(const double* queries, int64_t n, const double* transform
  *                     A non-finite float32 element: info[0] |= 1.
  *   vfn_image_abs_err a[V, H, W], b[V, H, W] float32: sums[v] = sum |double(a) s - double(b) s|, each product rounded once; s = 100 is
  *                     get_l1_cm's sum.  A kernel of its own over the tiles of a C = 1 image; the sums are joined as below.
- *   The sums are a FIXED tree.  A workgroup owns a tile of VFN_IMAGE_TILE x VFN_IMAGE_TILE = 16 x 16 pixels; tile (tile_y, tile_x) starts
- *   at pixel (16 tile_y, 16 tile_x); lane l = 16 ly + lx owns pixel (16 tile_y + ly, 16 tile_x + lx) and adds its C elements serially in
- *   ascending c, the first as it is; a lane outside the image holds +0.0.  The 256 lane values join as a balanced tree: lane l takes
- *   lane l + d for d = 128, 64, ... 1.  One partial per tile goes to the workspace in (view, tile_y, tile_x) order.  A second launch, one
- *   workgroup of 1024 lanes per view, joins the view's P = ceil(H / 16) ceil(W / 16) partials as vfn_reduce_stats does: lane l starts
- *   from partial l (+0.0 if l >= P) and adds the partials l + 1024, l + 2048, ... serially, then a balanced tree (l takes l + d,
- *   d = 512 ... 1).  The bits are a function of (V, H, W, C) and the data alone.
+ *   The sums go along THE FIXED TREE (above, after vfn_reduce_stats) without a lane tree.  A workgroup owns a tile of VFN_IMAGE_TILE x
+ *   VFN_IMAGE_TILE = 16 x 16 pixels; tile (tile_y, tile_x) starts at pixel (16 tile_y, 16 tile_x); lane l = 16 ly + lx owns pixel
+ *   (16 tile_y + ly, 16 tile_x + lx) and adds its C elements serially in ascending c, the first as it is; a lane outside the image holds
+ *   +0.0.  The block tree joins the 256 lane values into one partial per tile, in (view, tile_y, tile_x) order; the second level runs
+ *   once per view over that view's P = ceil(H / 16) ceil(W / 16) partials.  The bits are a function of (V, H, W, C) and the data alone.
  *   workspace: vfn_image_scores_workspace_bytes(V, H, W, C) bytes (vfn_image_abs_err: C = 1); answers on the host, -1 on error.
  * ============================================================================================= */
 #define VFN_IMAGE_TILE 16

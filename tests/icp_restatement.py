@@ -10,6 +10,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+import tree_restatement as T
+
 SUMS = 17
 
 
@@ -104,28 +106,37 @@ def bounded(free_index, free_sqdist, radius: float):
     return np.where(ok, free_index, -1), np.where(ok, free_sqdist, np.inf)
 
 
-def terms(queries, t, targets, index, sqdist, anchor) -> np.ndarray:
-    """The rows with a neighbour -> [k,17]: 1, d2, p = q' - a (3), s = target - a (3), p_a s_b (9), every difference and product
-    rounded once."""
+def placed_terms(queries, t, targets, index, sqdist, anchor) -> np.ndarray:
+    """Every row in its place -> [n,17]: 1, d2, p = q' - a (3), s = target - a (3), p_a s_b (9), every difference and product rounded
+    once; a row without a neighbour is seventeen +0.0, as the device joins it."""
     index = np.asarray(index)
     keep = index >= 0
     a = np.asarray(anchor, dtype=np.float64)
-    p = transform(queries, t)[keep] - a
-    s = np.asarray(targets, dtype=np.float64)[index[keep]] - a
-    out = np.empty((int(keep.sum()), SUMS))
+    p = transform(queries, t) - a
+    s = np.asarray(targets, dtype=np.float64)[np.where(keep, index, 0)] - a
+    out = np.empty((len(index), SUMS))
     out[:, 0] = 1.0
-    out[:, 1] = np.asarray(sqdist, dtype=np.float64)[keep]
+    out[:, 1] = np.asarray(sqdist, dtype=np.float64)
     out[:, 2:5], out[:, 5:8] = p, s
     for i in range(3):
         for j in range(3):
             out[:, 8 + 3 * i + j] = p[:, i] * s[:, j]
+    out[~keep] = 0.0
     return out
 
 
+def terms(queries, t, targets, index, sqdist, anchor) -> np.ndarray:
+    """The rows of ``placed_terms`` with a neighbour -> [k,17]."""
+    return placed_terms(queries, t, targets, index, sqdist, anchor)[np.asarray(index) >= 0]
+
+
 def sums_of(term_rows, how: str = "fsum") -> np.ndarray:
-    """Column sums of ``terms``: math.fsum (the exact sum rounded once) or numpy's own pairwise sum."""
+    """Column sums: math.fsum (the exact sum rounded once), numpy's own pairwise sum, or "tree": the device's fixed tree
+    (tests/tree_restatement.py, lane order "near"), which needs the rows of ``placed_terms``, not of ``terms``."""
     if how == "fsum":
         return np.array([math.fsum(term_rows[:, c].tolist()) for c in range(SUMS)])
+    if how == "tree":
+        return T.two_level(term_rows, "near")
     return term_rows.sum(axis=0)
 
 

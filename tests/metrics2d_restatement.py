@@ -6,7 +6,9 @@ import math
 
 import numpy as np
 
-TILE, TOP = 16, 1024          # include/vfn.h: VFN_IMAGE_TILE; csrc/vfn_image.hip: IMG_TOP
+import tree_restatement as T
+
+TILE, TOP = 16, T.TOP         # include/vfn.h: VFN_IMAGE_TILE, VFN_TREE_TOP
 R, K = 5, 11                  # window radius, window edge
 C1, C2 = 1e-4, 9e-4           # utils/utils.py:249
 
@@ -64,7 +66,7 @@ def squared_error_map(p, t):
 def view_sum(e):
     """e[H,W,C] per-element values of ONE view -> their sum along the fixed tree: a lane's channels serially, the 256 lanes of a
     16 x 16 tile as a balanced tree (l takes l + d, d = 128 .. 1; lanes outside the image hold +0.0), the tiles in (tile_y, tile_x) order
-    joined by 1024 lanes (lane l: partials l, l + 1024, ... serially, +0.0 without a partial), then a balanced tree."""
+    joined by the second level of tests/tree_restatement.py."""
     h, w, c = e.shape
     lane = e[:, :, 0].copy()
     for k in range(1, c):
@@ -73,23 +75,7 @@ def view_sum(e):
     pad = np.zeros((ty * TILE, tx * TILE))
     pad[:h, :w] = lane
     a = pad.reshape(ty, TILE, tx, TILE).transpose(0, 2, 1, 3).reshape(ty * tx, TILE * TILE)     # [tile, l = 16 ly + lx]
-    d = TILE * TILE // 2
-    while d >= 1:
-        a = a[:, :d] + a[:, d:2 * d]
-        d //= 2
-    part = a[:, 0]
-    n = part.shape[0]
-    rounds = -(-n // TOP)
-    s = np.zeros(TOP)
-    s[:min(n, TOP)] = part[:TOP]
-    for k in range(1, rounds):
-        chunk = part[k * TOP:(k + 1) * TOP]
-        s[:chunk.shape[0]] = s[:chunk.shape[0]] + chunk
-    d = TOP // 2
-    while d >= 1:
-        s = s[:d] + s[d:2 * d]
-        d //= 2
-    return float(s[0])
+    return float(T.top_join(T.block_tree(a)))
 
 
 def elements(pred, target, want_ssim=True, c1=C1, c2=C2):

@@ -9,6 +9,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+import tree_restatement as T
+
 
 def _nn_rows(q, tx, ty, tz, tile):
     best = np.full(q.shape[0], np.inf)
@@ -63,6 +65,11 @@ def sample_surface(vertices, faces, cum, uniforms):
     v0 = v[f[face, 0]]
     e1, e2 = v[f[face, 1]] - v0, v[f[face, 2]] - v0
     return (v0 + a[:, None] * e1) + b[:, None] * e2, face.astype(np.int64)
+
+
+def stats_sum(x):
+    """stats[0] of vfn_reduce_stats: the sum of x[n] along the device's fixed tree (tests/tree_restatement.py, lane order "far")."""
+    return float(T.two_level(np.asarray(x, dtype=np.float64)[:, None], "far")[0])
 
 
 def median(x):

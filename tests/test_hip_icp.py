@@ -1,7 +1,8 @@
 """Point-set alignment on the MI355X (csrc/vfn_icp.hip through vf_nerf_amd/icp.py) against the CPU restatement of its contract
 (tests/icp_restatement.py).  Neighbour indices, squared distances, transformed points and counts are compared bit for bit; the sixteen
-floating-point sums against math.fsum within the pairwise-summation bound of the tree the kernel builds; the loop is followed
-iteration by iteration from the device's own transformations."""
+floating-point sums against math.fsum within the pairwise-summation bound of the tree the kernel builds, and all seventeen bit for bit
+against the restatement of that tree (tests/tree_restatement.py); the loop is followed iteration by iteration from the device's own
+transformations."""
 import math
 import os
 import sys
@@ -240,15 +241,18 @@ def test_non_finite_coordinates_are_refused(bad):
 # 5: the sums
 # ---------------------------------------------------------------------------------------------------------------------------------
 def check_sums(q, move, t, index, sqdist, anchor):
-    """index / sqdist are device tensors.  The count is exact; every other sum is within L u sum|term| of math.fsum, L = the addition
-    levels include/vfn.h states; two runs give equal bits."""
+    """index / sqdist are device tensors.  All 17 sums equal the restatement of the fixed tree (lane order "near") bit for bit; the count
+    is exact; every other sum is within L u sum|term| of math.fsum, L = the addition levels include/vfn.h states; two runs give equal
+    bits."""
     n = len(q)
     qd, td = torch.from_numpy(q).to(DEV), torch.from_numpy(t).to(DEV)
     twelve = icp._twelve(move)
     got = lib.icp_accumulate(qd, twelve, td, index, sqdist, tuple(anchor)).cpu().numpy()
     again = lib.icp_accumulate(qd, twelve, td, index, sqdist, tuple(anchor)).cpu().numpy()
     assert got.shape == (17,) and np.array_equal(bits(got), bits(again))
-    rows = R.terms(q, move, t, index.cpu().numpy(), sqdist.cpu().numpy(), anchor)
+    placed = R.placed_terms(q, move, t, index.cpu().numpy(), sqdist.cpu().numpy(), anchor)
+    assert np.array_equal(bits(got), bits(R.sums_of(placed, "tree")))
+    rows = placed[index.cpu().numpy() >= 0]
     exact = R.sums_of(rows)
     assert got[0] == exact[0] == len(rows)
     L = lib.icp_sum_levels(n)
@@ -262,7 +266,7 @@ def check_sums(q, move, t, index, sqdist, anchor):
     return got
 
 
-@pytest.mark.parametrize("n,m", [(1, 1), (4097, 1805), (100003, 2049)])
+@pytest.mark.parametrize("n,m", [(1, 1), (257, 130), (4097, 1805), (100003, 2049)])
 def test_accumulate_on_searched_pairs(n, m):
     q, t = uniform_case(n, m)
     q = q + 100.0

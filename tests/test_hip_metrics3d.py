@@ -1,6 +1,7 @@
 """Mesh scoring on the MI355X (csrc/vfn_metrics.hip through vf_nerf_amd/metrics3d.py) against the CPU restatement
 (tests/metrics3d_restatement.py) and scipy's cKDTree.  Distances, areas, samples, medians, minima, maxima and counts are compared bit
-for bit; the two sums (cumulative areas, means) against math.fsum within the pairwise-summation bound of the tree the kernel builds."""
+for bit; the two sums (cumulative areas, means) against math.fsum within the pairwise-summation bound of the tree the kernel builds,
+and the statistics sum bit for bit against the restatement of that tree (tests/tree_restatement.py)."""
 import math
 import os
 import sys
@@ -274,7 +275,7 @@ def sum_levels(n):
     return levels
 
 
-@pytest.mark.parametrize("n", [1, 2, 255, 4096, 4097, 1000003, 2500000, 4096 * 1024 + 5])
+@pytest.mark.parametrize("n", [1, 2, 255, 257, 4096, 4097, 1000003, 2500000, 4096 * 1024 + 5])
 def test_statistics(n):
     g = np.random.default_rng(n)
     x = g.uniform(0, 1, n) ** 3 * 0.3
@@ -287,6 +288,7 @@ def test_statistics(n):
     s2 = lib.reduce_stats(xd, threshold)
     assert torch.equal(s.view(torch.int64), s2.view(torch.int64))
     total, mn, mx, cnt = s.cpu().tolist()
+    assert bits(total) == bits(R.stats_sum(x))              # the fixed tree of include/vfn.h, lane order "far", bit for bit
     assert mn == x.min() and mx == x.max() and cnt == int((x < threshold).sum())
     assert lib.reduce_stats(xd, 0.0).cpu()[3] == 0 and lib.reduce_stats(xd, math.inf).cpu()[3] == n
     lo, hi = metrics3d._median_pair(xd).cpu().tolist()
@@ -296,6 +298,14 @@ def test_statistics(n):
     mean = total / n
     print(f"n={n}: mean error {abs(mean - exact) / exact / U:.2f} x 2^-53, bound {L}")
     assert abs(mean - exact) <= L * U * exact
+
+
+def test_statistics_of_one_negative_zero():
+    """The 4095 values past n join as +0.0: the sum of a lone -0.0 is +0.0; minimum and maximum keep the value itself."""
+    x = np.array([-0.0])
+    total, mn, mx, cnt = lib.reduce_stats(torch.from_numpy(x).to(DEV), 0.05).cpu().tolist()
+    assert bits(total) == bits(R.stats_sum(x)) == bits(0.0)
+    assert mn == 0.0 and mx == 0.0 and cnt == 1
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

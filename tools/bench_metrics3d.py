@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Device time of mesh scoring (vf_nerf_amd.metrics3d): the all-pairs nearest-neighbour search at n = m = 2^17, 10^6 and 2.5 x 10^6
-(metrics_3d's and get_chamfer_distance's default point counts) and the surface sampling of 10^6 points, on a mesh that
+(metrics_3d's and get_chamfer_distance's default point counts), the surface sampling of 10^6 points and the statistics
+(lib.reduce_stats: sum, min, max, count) of 2.5 x 10^6 seeded values shaped like squared distances, on a mesh that
 mesh.extract_mesh makes from the trained-weight scene of bench.py (the random-weight scene when the fixture is absent).  The two point
 sets of a search are surface samples of that mesh and of a copy scaled by 1.01: what the scorer itself searches.
 
@@ -47,10 +48,18 @@ def timed(fn, reps):
     return statistics.median(times), times, out
 
 
+def statistics_input(n, dev):
+    """n seeded values in [0, 0.3), most of them small: 0.3 u^3 for uniform u."""
+    g = torch.Generator(device=dev)
+    g.manual_seed(n)
+    return torch.rand(n, dtype=torch.float64, device=dev, generator=g) ** 3 * 0.3
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[1 << 17, 1000000, 2500000])
     ap.add_argument("--sample-count", type=int, default=1000000)
+    ap.add_argument("--statistics-count", type=int, default=2500000)
     ap.add_argument("--res", type=int, default=128)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--workers", type=int, default=16)
@@ -60,7 +69,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_metrics3d: no GPU visible (nothing here can be measured on a CPU)")
     import bench
-    from vf_nerf_amd import mesh, metrics3d
+    from vf_nerf_amd import lib, mesh, metrics3d
     dev = torch.device("cuda:0")
     trained = bench.build_trained_scene(dev, 64, 32, 32, 0)
     scene, model = ("trained", trained[0]) if trained is not None else ("random", bench.build_scene(dev, 64, 32, 32, 0)[0])
@@ -70,7 +79,13 @@ def main():
               "reps": args.reps, "timing": "HIP events, one warm-up call, median of reps",
               "peak_lane_instructions_per_s": PEAK_LANE_INSTRUCTIONS,
               "peak_note": "published 78.6 TFLOP/s vector fp64 / 2 (not measured here); 9 fp64 lane-instructions per pair",
-              "nearest_distances": [], "sample_surface": None}
+              "nearest_distances": [], "sample_surface": None, "statistics": None}
+    x = statistics_input(args.statistics_count, dev)
+    t, all_t, _ = timed(lambda: lib.reduce_stats(x, 0.05), args.reps)
+    result["statistics"] = {"count": args.statistics_count, "seconds": round(t, 6), "all_seconds": [round(v, 6) for v in all_t],
+                            "values_per_s": round(args.statistics_count / t, 1)}
+    print(json.dumps(result["statistics"]), flush=True)
+    del x
     g = torch.Generator(device=dev)
     g.manual_seed(0)
     t, all_t, _ = timed(lambda: metrics3d.sample_surface(m.vertices_scaled, m.faces, args.sample_count, generator=g), args.reps)

@@ -33,7 +33,7 @@ ONLY=${VFN_ONLY:-}
 for u in $UNITS; do
   [ -f "$u.hip" ] || { echo "build.sh: missing source $u.hip" >&2; exit 1; }
   if [ -n "$ONLY" ] && ! echo " $ONLY " | grep -q " $u "; then
-    if [ -s "$OBJDIR/$u.o" ] && [ "$OBJDIR/$u.o" -nt "$u.hip" ] && [ "$OBJDIR/$u.o" -nt vfn_common.h ] && [ "$OBJDIR/$u.o" -nt vfn_mc_tables.h ] && [ "$OBJDIR/$u.o" -nt vfn_mc_extract.h ] && [ "$OBJDIR/$u.o" -nt ../../include/vfn.h ]; then
+    if [ -s "$OBJDIR/$u.o" ] && [ "$OBJDIR/$u.o" -nt "$u.hip" ] && [ "$OBJDIR/$u.o" -nt vfn_common.h ] && [ "$OBJDIR/$u.o" -nt vfn_mc_tables.h ] && [ "$OBJDIR/$u.o" -nt vfn_mc_extract.h ] && [ "$OBJDIR/$u.o" -nt vfn_tree.h ] && [ "$OBJDIR/$u.o" -nt ../../include/vfn.h ]; then
       OBJS="$OBJS $OBJDIR/$u.o"; touch "$OBJDIR/$u.remarks"; continue
     fi
     echo "build.sh: VFN_ONLY given but $u.o is missing or older than its sources" >&2; exit 1

@@ -5,8 +5,8 @@
 //                     sorted by the cell of a uniform grid whose edge exceeds the radius, so a query reads the 3 x 3 x 3 cells around
 //                     its own as 9 contiguous ranges (the 3 cells along z are neighbours in the sorted order).  Lanes diverge: the
 //                     targets come through vector loads.  No LDS.
-//   icp_accumulate    the 17 sums a rigid solve needs over the rows with a neighbour, as a fixed two-level tree (the shape of
-//                     vfn_reduce_stats): no floating-point atomics, bits a function of n and the data alone.
+//   icp_accumulate    the 17 sums a rigid solve needs over the rows with a neighbour, along the fixed tree of vfn_tree.h, lane order
+//                     "near": no floating-point atomics, bits a function of n and the data alone.
 // All arithmetic fp64 with -ffp-contract=off (build.sh): the expressions of include/vfn.h, operation for operation.
 //
 // WHY THE GRID CANNOT CHANGE A BIT.  The result is defined without the grid: the minimum of (d2, original index) in lexicographic order
@@ -26,14 +26,13 @@
 // A bare h = r fails step (3): (1 + 4 u) / 1 + 519 u > 1, and two points exactly r apart can land two cells apart.
 // Within a cell the sorted order is the original one (the sort is stable), but nothing relies on it: the comparison carries the index.
 #include "vfn_common.h"
+#include "vfn_tree.h"
 #include <math.h>
 
 namespace {
 
 constexpr int ICP_BLOCK = 256;
 constexpr int ACC_N = 17;                                                          // count, sum d2, 3 + 3 first moments, 9 products
-constexpr int ACC_BLOCK = 256, ACC_PER = 16, ACC_TILE = ACC_BLOCK * ACC_PER;       // 4096 rows per first-level partial
-constexpr int ACC_TOP = 1024;                                                      // lanes of the second level
 constexpr int GRID_CAP = VFN_ICP_GRID_CAP;                                         // cells per axis at most (include/vfn.h)
 constexpr double GRID_MARGIN = 1.0 + 1.0 / (double)(1ll << VFN_ICP_GRID_MARGIN_LOG2);     // cell edge over radius at least: 1 + 2^-20
 
@@ -121,14 +120,7 @@ __global__ __launch_bounds__(ICP_BLOCK) void vfn_nn_radius_kernel(const double* 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // the 17 sums
 // ---------------------------------------------------------------------------------------------------------------------------------
-struct Acc { double v[ACC_N]; };
-
-__device__ __forceinline__ Acc acc_join(const Acc& a, const Acc& b) {
-    Acc r;
-#pragma unroll
-    for (int c = 0; c < ACC_N; ++c) r.v[c] = a.v[c] + b.v[c];
-    return r;
-}
+using Acc = TreeSum<ACC_N>;
 
 __device__ __forceinline__ Acc acc_row(long long i, long long n, const double* __restrict__ q, const Xform& T, const double* __restrict__ t, long long m,
                                        const long long* __restrict__ index, const double* __restrict__ sqdist, double ax, double ay, double az,
@@ -156,75 +148,39 @@ __device__ __forceinline__ Acc acc_row(long long i, long long n, const double* _
     return r;
 }
 
-// The balanced tree over a lane's ACC_PER = 16 rows (4 levels) as a binary counter: row k joins the finished subtree of its size
-// on its left for every trailing 1 bit of k, so ((r0 + r1) + (r2 + r3)) + ... with at most four finished subtrees alive.  The loop is
-// not unrolled: sixteen rows' loads in flight at once would need more registers than a lane has.
-template <typename Leaf>
-__device__ __forceinline__ Acc acc_lane_tree(const Leaf& leaf) {
-    static_assert(ACC_PER == 16, "the counter below has four levels");
-    Acc s0, s1, s2, s3, a;
-#pragma unroll 1
-    for (int k = 0; k < ACC_PER; ++k) {
-        a = leaf(k);
-        if (!(k & 1)) { s0 = a; continue; }
-        a = acc_join(s0, a);
-        if (!(k & 2)) { s1 = a; continue; }
-        a = acc_join(s1, a);
-        if (!(k & 4)) { s2 = a; continue; }
-        a = acc_join(s2, a);
-        if (!(k & 8)) { s3 = a; continue; }
-        a = acc_join(s3, a);
-    }
-    return a;
+// first level: block b covers rows [b TREE_TILE, (b + 1) TREE_TILE); lane l takes the rows l + 256 k in the "near" order, then the block
+// tree.  The lane tree is not unrolled: sixteen rows' loads in flight at once would need more registers than a lane has.
+__global__ __launch_bounds__(TREE_LANES) void vfn_icp_accumulate_kernel(const double* __restrict__ q, long long n, Xform T, const double* __restrict__ t,
+                                                                        long long m, const long long* __restrict__ index,
+                                                                        const double* __restrict__ sqdist, double ax, double ay, double az,
+                                                                        double* __restrict__ partials, unsigned long long* __restrict__ info) {
+    __shared__ Acc sh[TREE_LANES];
+    const int l = threadIdx.x;
+    const long long base = (long long)blockIdx.x * TREE_TILE + l;
+    const Acc mine = tree_lane<1, Acc>([&](int k) { return acc_row(base + (long long)k * TREE_LANES, n, q, T, t, m, index, sqdist, ax, ay, az, info); },
+                                       TreeAdd());
+    tree_block<TREE_LANES>(mine, sh, TreeAdd());
+    if (l < ACC_N) partials[(long long)blockIdx.x * ACC_N + l] = sh[0].v[l];
 }
 
-// first level: block b covers rows [b ACC_TILE, (b + 1) ACC_TILE); lane l takes the rows l + 256 k, k < 16 (neighbouring k first: 4 levels), then the block
-// tree (lane l takes lane l + d, d = 128 ... 1: 8 levels).  LDS: 17 doubles x 256 lanes.
-__global__ __launch_bounds__(ACC_BLOCK) void vfn_icp_accumulate_kernel(const double* __restrict__ q, long long n, Xform T, const double* __restrict__ t,
-                                                                       long long m, const long long* __restrict__ index,
-                                                                       const double* __restrict__ sqdist, double ax, double ay, double az,
-                                                                       double* __restrict__ partials, unsigned long long* __restrict__ info) {
-    __shared__ double sh[ACC_N][ACC_BLOCK];
-    const int l = threadIdx.x;
-    const long long base = (long long)blockIdx.x * ACC_TILE + l;
-    const Acc mine = acc_lane_tree([&](int k) { return acc_row(base + (long long)k * ACC_BLOCK, n, q, T, t, m, index, sqdist, ax, ay, az, info); });
+// second level over the p partials; the block tree one component after the other through the same 1024 doubles of LDS (1024 Acc would
+// be 136 KiB).
+__global__ __launch_bounds__(TREE_TOP) void vfn_icp_accumulate_top_kernel(const double* __restrict__ partials, long long p, double* __restrict__ sums) {
+    __shared__ double sh[TREE_TOP];
+    Acc zero;
 #pragma unroll
-    for (int c = 0; c < ACC_N; ++c) sh[c][l] = mine.v[c];
-    __syncthreads();
-    for (int d = ACC_BLOCK / 2; d >= 1; d >>= 1) {
-        if (l < d) {
+    for (int c = 0; c < ACC_N; ++c) zero.v[c] = 0.0;
+    const Acc s = tree_top_lane(p, zero, [&](long long i) {
+        Acc r;
 #pragma unroll
-            for (int c = 0; c < ACC_N; ++c) sh[c][l] = sh[c][l] + sh[c][l + d];
-        }
-        __syncthreads();
-    }
-    if (l < ACC_N) partials[(long long)blockIdx.x * ACC_N + l] = sh[l][0];
-}
-
-// second level, one block of ACC_TOP lanes: lane l joins the partials l, l + 1024, ... serially, then a balanced tree (10 levels), one
-// component after the other through the same 1024 doubles of LDS.
-__global__ __launch_bounds__(ACC_TOP) void vfn_icp_accumulate_top_kernel(const double* __restrict__ partials, long long p, double* __restrict__ sums) {
-    __shared__ double sh[ACC_TOP];
-    const int l = threadIdx.x;
-    Acc s;
-#pragma unroll
-    for (int c = 0; c < ACC_N; ++c) s.v[c] = 0.0;
-    bool first = true;
-    for (long long i = l; i < p; i += ACC_TOP) {
-#pragma unroll
-        for (int c = 0; c < ACC_N; ++c) s.v[c] = first ? partials[i * ACC_N + c] : s.v[c] + partials[i * ACC_N + c];
-        first = false;
-    }
+        for (int c = 0; c < ACC_N; ++c) r.v[c] = partials[i * ACC_N + c];
+        return r;
+    }, TreeAdd());
 #pragma unroll
     for (int c = 0; c < ACC_N; ++c) {
-        sh[l] = s.v[c];
-        __syncthreads();
-        for (int d = ACC_TOP / 2; d >= 1; d >>= 1) {
-            if (l < d) sh[l] = sh[l] + sh[l + d];
-            __syncthreads();
-        }
-        if (l == 0) sums[c] = sh[0];
-        __syncthreads();
+        const double r = tree_block<TREE_TOP>(s.v[c], sh, TreeAdd());
+        if (threadIdx.x == 0) sums[c] = r;
+        __syncthreads();                               // the next component overwrites sh
     }
 }
 
@@ -286,7 +242,7 @@ extern "C" int64_t vfn_icp_accumulate_workspace_bytes(int64_t n) {
         vfn_set_error("vfn_icp_accumulate_workspace_bytes: n %lld outside [1, 2^31)", (long long)n);
         return -1;
     }
-    return (int64_t)(((n + ACC_TILE - 1) / ACC_TILE) * ACC_N * sizeof(double));
+    return (int64_t)(tree_tiles(n) * ACC_N * sizeof(double));
 }
 
 extern "C" int vfn_icp_accumulate(const double* queries, int64_t n, const double* transform, const double* targets, int64_t m,
@@ -300,9 +256,9 @@ extern "C" int vfn_icp_accumulate(const double* queries, int64_t n, const double
     VFN_REQUIRE(load_xform(transform, &T), "vfn_icp_accumulate: a non-finite transform");
     VFN_REQUIRE(isfinite(anchor[0]) && isfinite(anchor[1]) && isfinite(anchor[2]), "vfn_icp_accumulate: a non-finite anchor");
     hipStream_t s = (hipStream_t)stream;
-    const long long p = (n + ACC_TILE - 1) / ACC_TILE;
-    hipLaunchKernelGGL(vfn_icp_accumulate_kernel, dim3((unsigned)p), dim3(ACC_BLOCK), 0, s, queries, (long long)n, T, targets, (long long)m,
+    const long long p = tree_tiles(n);
+    hipLaunchKernelGGL(vfn_icp_accumulate_kernel, dim3((unsigned)p), dim3(TREE_LANES), 0, s, queries, (long long)n, T, targets, (long long)m,
                        (const long long*)index, sqdist, anchor[0], anchor[1], anchor[2], (double*)workspace, (unsigned long long*)info);
-    hipLaunchKernelGGL(vfn_icp_accumulate_top_kernel, dim3(1), dim3(ACC_TOP), 0, s, (const double*)workspace, p, sums);
+    hipLaunchKernelGGL(vfn_icp_accumulate_top_kernel, dim3(1), dim3(TREE_TOP), 0, s, (const double*)workspace, p, sums);
     return vfn_check_launch("vfn_icp_accumulate");
 }

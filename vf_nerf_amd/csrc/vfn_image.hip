@@ -6,39 +6,31 @@
 //               windowed quantities for the tile's 26 rows, a vertical pass the 11-row sums of the lane's own pixel: 2 x 11 additions
 //               per quantity instead of 121, in the association of include/vfn.h (direct sums, no running window).
 //   abs_err     the same tiles over one-channel float images: |a s - b s|.
-//   sums        a fixed two-level tree (no floating-point atomics): the 256 lanes of a tile as a balanced tree into one partial per
-//               tile, then one 1024-lane workgroup per view over that view's partials, as vfn_reduce_stats joins its partials.
+//   sums        the fixed tree of vfn_tree.h without a lane tree: the block tree over the 256 lanes of a tile into one partial per
+//               tile, then the second level once per view over that view's partials.
 // All arithmetic fp64 with -ffp-contract=off (build.sh): the expressions of include/vfn.h, operation for operation.
 #include "vfn_common.h"
+#include "vfn_tree.h"
 #include <math.h>
 
 namespace {
 
 constexpr int IMG_TILE = VFN_IMAGE_TILE;            // pixels per tile edge: 16 x 16 = one lane per pixel
 constexpr int IMG_BLOCK = IMG_TILE * IMG_TILE;      // 256 lanes
+static_assert(IMG_BLOCK == TREE_LANES, "a tile is one first-level block of the fixed tree");
 constexpr int IMG_R = 5, IMG_K = 2 * IMG_R + 1;     // window radius, window edge (11)
 constexpr int IMG_HALO = IMG_TILE + 2 * IMG_R;      // 26 staged rows / columns
-constexpr int IMG_TOP = 1024;                       // lanes of the second level
+using Pair = TreeSum<2>;                            // a view's two sums travel together
 
 __device__ __forceinline__ double img_value(const float* p, long long i) { return (double)p[i]; }
 __device__ __forceinline__ double img_value(const unsigned char* p, long long i) { return (double)p[i] / 255.0; }
 __device__ __forceinline__ bool img_bad(const float* p, long long i) { return !isfinite(p[i]); }
 __device__ __forceinline__ bool img_bad(const unsigned char*, long long) { return false; }
 
-// the balanced tree over the 256 lane values of a tile, the same pairs for every launch: lane l takes lane l + d for d = 128 ... 1
-__device__ __forceinline__ void img_tile_tree(double a, double b, double (*red)[IMG_BLOCK], double* __restrict__ partial) {
-    const int l = threadIdx.x;
-    red[0][l] = a;
-    red[1][l] = b;
-    __syncthreads();
-    for (int d = IMG_BLOCK / 2; d >= 1; d >>= 1) {
-        if (l < d) {
-            red[0][l] = red[0][l] + red[0][l + d];
-            red[1][l] = red[1][l] + red[1][l + d];
-        }
-        __syncthreads();
-    }
-    if (l == 0) { partial[0] = red[0][0]; partial[1] = red[1][0]; }
+// the block tree over the 256 lane values of a tile -> the tile's partial
+__device__ __forceinline__ void img_tile_tree(double a, double b, Pair* red, double* __restrict__ partial) {
+    const Pair r = tree_block<IMG_BLOCK>(Pair{{a, b}}, red, TreeAdd());
+    if (threadIdx.x == 0) { partial[0] = r.v[0]; partial[1] = r.v[1]; }
 }
 
 // block (view v, tile_y, tile_x) = blockIdx.x in that order; lane l = 16 ly + lx owns pixel (16 tile_y + ly, 16 tile_x + lx)
@@ -48,7 +40,7 @@ __global__ __launch_bounds__(IMG_BLOCK) void vfn_image_scores_kernel(const PT* _
                                                                      double* __restrict__ partials, unsigned long long* __restrict__ info) {
     __shared__ double sp[SSIM ? IMG_HALO : 1][IMG_HALO + 1], st[SSIM ? IMG_HALO : 1][IMG_HALO + 1];
     __shared__ double rs[SSIM ? 5 : 1][SSIM ? IMG_HALO : 1][IMG_TILE + 1];
-    __shared__ double red[2][IMG_BLOCK];
+    __shared__ Pair red[IMG_BLOCK];
     const int l = threadIdx.x, ly = l / IMG_TILE, lx = l % IMG_TILE;
     const long long b = blockIdx.x;
     const int tx = (int)(b % tiles_x), ty = (int)((b / tiles_x) % tiles_y);
@@ -131,7 +123,7 @@ __global__ __launch_bounds__(IMG_BLOCK) void vfn_image_scores_kernel(const PT* _
 __global__ __launch_bounds__(IMG_BLOCK) void vfn_image_abs_err_kernel(const float* __restrict__ a, const float* __restrict__ bb, int H, int W,
                                                                       int tiles_y, int tiles_x, double scale, double* __restrict__ partials,
                                                                       unsigned long long* __restrict__ info) {
-    __shared__ double red[2][IMG_BLOCK];
+    __shared__ Pair red[IMG_BLOCK];
     const int l = threadIdx.x, ly = l / IMG_TILE, lx = l % IMG_TILE;
     const long long b = blockIdx.x;
     const int tx = (int)(b % tiles_x), ty = (int)((b / tiles_x) % tiles_y);
@@ -147,33 +139,18 @@ __global__ __launch_bounds__(IMG_BLOCK) void vfn_image_abs_err_kernel(const floa
     img_tile_tree(val, 0.0, red, partials + 2 * b);
 }
 
-// second level, one block of 1024 lanes per view: lane l joins the view's partials l, l + 1024, ... serially (a lane without a partial
-// holds +0.0), then a balanced tree (10 levels).  out[v n_out + k] = slot k for k < slots; the slots above are written 0.
-__global__ __launch_bounds__(IMG_TOP) void vfn_image_top_kernel(const double* __restrict__ partials, long long per_view, double* __restrict__ out,
-                                                                 int n_out, int slots) {
-    __shared__ double sh[2][IMG_TOP];
-    const int l = threadIdx.x;
+// second level, one block per view over the view's per_view partials.  out[v n_out + k] = slot k for k < slots; the slots above are
+// written 0.
+__global__ __launch_bounds__(TREE_TOP) void vfn_image_top_kernel(const double* __restrict__ partials, long long per_view, double* __restrict__ out,
+                                                                  int n_out, int slots) {
+    __shared__ Pair sh[TREE_TOP];
     const double* __restrict__ part = partials + 2 * per_view * (long long)blockIdx.x;
-    double s0 = 0.0, s1 = 0.0;
-    if (l < per_view) { s0 = part[2 * l]; s1 = part[2 * l + 1]; }
-    for (long long i = (long long)l + IMG_TOP; i < per_view; i += IMG_TOP) {
-        s0 = s0 + part[2 * i];
-        s1 = s1 + part[2 * i + 1];
-    }
-    sh[0][l] = s0;
-    sh[1][l] = s1;
-    __syncthreads();
-    for (int d = IMG_TOP / 2; d >= 1; d >>= 1) {
-        if (l < d) {
-            sh[0][l] = sh[0][l] + sh[0][l + d];
-            sh[1][l] = sh[1][l] + sh[1][l + d];
-        }
-        __syncthreads();
-    }
-    if (l == 0) {
+    const Pair s = tree_top_lane(per_view, Pair{{0.0, 0.0}}, [&](long long i) { return Pair{{part[2 * i], part[2 * i + 1]}}; }, TreeAdd());
+    const Pair r = tree_block<TREE_TOP>(s, sh, TreeAdd());
+    if (threadIdx.x == 0) {
         double* o = out + (long long)blockIdx.x * n_out;
-        o[0] = sh[0][0];
-        if (n_out > 1) o[1] = slots > 1 ? sh[1][0] : 0.0;
+        o[0] = r.v[0];
+        if (n_out > 1) o[1] = slots > 1 ? r.v[1] : 0.0;
         for (int k = 2; k < n_out; ++k) o[k] = 0.0;
     }
 }
@@ -241,7 +218,7 @@ extern "C" int vfn_image_scores(const void* pred, int32_t pred_u8, const void* t
     else if (pred_u8) launch_scores<unsigned char, float>(pred, target, V, H, W, C, want_ssim, c1, c2, partials, info, s);
     else if (target_u8) launch_scores<float, unsigned char>(pred, target, V, H, W, C, want_ssim, c1, c2, partials, info, s);
     else launch_scores<float, float>(pred, target, V, H, W, C, want_ssim, c1, c2, partials, info, s);
-    hipLaunchKernelGGL(vfn_image_top_kernel, dim3((unsigned)V), dim3(IMG_TOP), 0, s, (const double*)partials, tiles_of(H) * tiles_of(W), sums, 3,
+    hipLaunchKernelGGL(vfn_image_top_kernel, dim3((unsigned)V), dim3(TREE_TOP), 0, s, (const double*)partials, tiles_of(H) * tiles_of(W), sums, 3,
                        want_ssim ? 2 : 1);
     return vfn_check_launch("vfn_image_scores");
 }
@@ -257,7 +234,7 @@ extern "C" int vfn_image_abs_err(const float* a, const float* b, int64_t V, int6
     const long long ty = tiles_of(H), tx = tiles_of(W);
     hipLaunchKernelGGL(vfn_image_abs_err_kernel, dim3((unsigned)(V * ty * tx)), dim3(IMG_BLOCK), 0, s, a, b, (int)H, (int)W, (int)ty, (int)tx, scale,
                        (double*)workspace, (unsigned long long*)info);
-    hipLaunchKernelGGL(vfn_image_top_kernel, dim3((unsigned)V), dim3(IMG_TOP), 0, s, (const double*)workspace, ty * tx, sums, 1, 1);
+    hipLaunchKernelGGL(vfn_image_top_kernel, dim3((unsigned)V), dim3(TREE_TOP), 0, s, (const double*)workspace, ty * tx, sums, 1, 1);
     return vfn_check_launch("vfn_image_abs_err");
 }
 

@@ -9,9 +9,10 @@
 //   nn_sqdist       the hot path: all pairs, exact.  One lane holds NN_QPL queries in registers; the targets of a slice are read at
 //                   wave-uniform addresses (scalar loads, no LDS), 9 fp64 vector instructions per pair, no index; the slices of one
 //                   query merge with a 64-bit integer atomicMin on the bits of the non-negative double (order-independent).
-//   reduce_stats    sum / min / max / count(x < threshold) as a fixed two-level tree (no floating-point atomics).
+//   reduce_stats    sum / min / max / count(x < threshold) along the fixed tree of vfn_tree.h, lane order "far".
 // All arithmetic fp64 with -ffp-contract=off (build.sh): the expressions of include/vfn.h, operation for operation.
 #include "vfn_common.h"
+#include "vfn_tree.h"
 #include <math.h>
 
 namespace {
@@ -24,8 +25,6 @@ constexpr int NN_MIN_SLICE = 256;             // fewest targets per slice
 constexpr long long NN_WANT_BLOCKS = 16384;   // workgroups aimed at: many rounds of 256 CUs, so the last round's idle share stays small
 
 constexpr int SCAN_BLOCK = 256, SCAN_PER = 4, SCAN_TILE = SCAN_BLOCK * SCAN_PER;   // 1024 values per scan block
-constexpr int RED_BLOCK = 256, RED_PER = 16, RED_TILE = RED_BLOCK * RED_PER;       // 4096 values per first-level partial
-constexpr int RED_TOP = 1024;                                                      // lanes of the second level
 
 constexpr unsigned long long INF_BITS = 0x7FF0000000000000ull;
 
@@ -180,33 +179,20 @@ __device__ __forceinline__ Stats stats_join(const Stats& a, const Stats& b) {
     return Stats{a.sum + b.sum, fmin(a.mn, b.mn), fmax(a.mx, b.mx), a.cnt + b.cnt};
 }
 
-// a balanced tree over the LANES values of a block, the same pairs for every launch: lane l takes lane l + d for d = LANES/2 ... 1
-template <int LANES>
-__device__ __forceinline__ Stats stats_block_tree(Stats s, Stats* sh) {
-    const int l = threadIdx.x;
-    sh[l] = s;
-    __syncthreads();
-    for (int d = LANES / 2; d >= 1; d >>= 1) {
-        if (l < d) sh[l] = stats_join(sh[l], sh[l + d]);
-        __syncthreads();
-    }
-    return sh[0];
-}
-
 __device__ __forceinline__ Stats stats_empty() {
     return Stats{0.0, __longlong_as_double((long long)INF_BITS), -__longlong_as_double((long long)INF_BITS), 0};
 }
 
-// first level: block b covers x[b RED_TILE, (b + 1) RED_TILE); lane l holds the RED_PER values l + 256 k and joins them as a balanced
-// tree (4 levels), then the block tree (8 levels): 12 addition levels.  Values past n join as the identity (sum + 0.0: exact).
-__global__ __launch_bounds__(RED_BLOCK) void vfn_reduce_stats_kernel(const double* __restrict__ x, long long n, double threshold,
-                                                                     Stats* __restrict__ partials) {
-    __shared__ Stats sh[RED_BLOCK];
-    const long long base = (long long)blockIdx.x * RED_TILE + threadIdx.x;
-    Stats s[RED_PER];
+// first level: block b covers x[b TREE_TILE, (b + 1) TREE_TILE); lane l holds the values l + 256 k in its slots k and joins them in the
+// "far" order, then the block tree.  Fully unrolled, the 16 loads issued before the first join: the lane tree is register moves.
+__global__ __launch_bounds__(TREE_LANES) void vfn_reduce_stats_kernel(const double* __restrict__ x, long long n, double threshold,
+                                                                      Stats* __restrict__ partials) {
+    __shared__ Stats sh[TREE_LANES];
+    const long long base = (long long)blockIdx.x * TREE_TILE + threadIdx.x;
+    Stats s[TREE_PER];
 #pragma unroll
-    for (int k = 0; k < RED_PER; ++k) {
-        const long long i = base + (long long)k * RED_BLOCK;
+    for (int k = 0; k < TREE_PER; ++k) {
+        const long long i = base + (long long)k * TREE_LANES;
         if (i < n) {
             const double val = x[i];
             s[k] = Stats{val, val, val, val < threshold ? 1ll : 0ll};
@@ -214,25 +200,16 @@ __global__ __launch_bounds__(RED_BLOCK) void vfn_reduce_stats_kernel(const doubl
             s[k] = stats_empty();
         }
     }
-#pragma unroll
-    for (int d = RED_PER / 2; d >= 1; d >>= 1)
-#pragma unroll
-        for (int k = 0; k < d; ++k) s[k] = stats_join(s[k], s[k + d]);
-    const Stats r = stats_block_tree<RED_BLOCK>(s[0], sh);
+    const Stats mine = tree_lane<TREE_PER, Stats>([&](int k) { return s[tree_far_slot(k)]; }, stats_join);
+    const Stats r = tree_block<TREE_LANES>(mine, sh, stats_join);
     if (threadIdx.x == 0) partials[blockIdx.x] = r;
 }
 
-// second level, one block of RED_TOP lanes: lane l joins the partials l, l + 1024, ... serially (ceil(P / 1024) - 1 additions), then the
-// block tree (10 levels).  stats[4] = sum, min, max, count (as a double: exact below 2^53).
-__global__ __launch_bounds__(RED_TOP) void vfn_reduce_stats_top_kernel(const Stats* __restrict__ partials, long long p, double* __restrict__ stats) {
-    __shared__ Stats sh[RED_TOP];
-    Stats s = stats_empty();
-    bool first = true;
-    for (long long i = threadIdx.x; i < p; i += RED_TOP) {
-        s = first ? partials[i] : stats_join(s, partials[i]);
-        first = false;
-    }
-    const Stats r = stats_block_tree<RED_TOP>(s, sh);
+// second level over the p partials.  stats[4] = sum, min, max, count (as a double: exact below 2^53).
+__global__ __launch_bounds__(TREE_TOP) void vfn_reduce_stats_top_kernel(const Stats* __restrict__ partials, long long p, double* __restrict__ stats) {
+    __shared__ Stats sh[TREE_TOP];
+    const Stats s = tree_top_lane(p, stats_empty(), [&](long long i) { return partials[i]; }, stats_join);
+    const Stats r = tree_block<TREE_TOP>(s, sh, stats_join);
     if (threadIdx.x == 0) {
         stats[0] = r.sum; stats[1] = r.mn; stats[2] = r.mx; stats[3] = (double)r.cnt;
     }
@@ -331,7 +308,7 @@ extern "C" int64_t vfn_reduce_stats_workspace_bytes(int64_t n) {
         vfn_set_error("vfn_reduce_stats_workspace_bytes: n %lld outside [1, 2^31)", (long long)n);
         return -1;
     }
-    return (int64_t)(((n + RED_TILE - 1) / RED_TILE) * sizeof(Stats));
+    return (int64_t)(tree_tiles(n) * sizeof(Stats));
 }
 
 extern "C" int vfn_reduce_stats(const double* x, int64_t n, double threshold, double* stats, void* workspace, int64_t workspace_bytes,
@@ -341,8 +318,8 @@ extern "C" int vfn_reduce_stats(const double* x, int64_t n, double threshold, do
     VFN_REQUIRE(x && stats && workspace && workspace_bytes >= need, "vfn_reduce_stats: NULL argument or a workspace of %lld bytes < %lld",
                 (long long)workspace_bytes, (long long)need);
     hipStream_t s = (hipStream_t)stream;
-    const long long p = (n + RED_TILE - 1) / RED_TILE;
-    hipLaunchKernelGGL(vfn_reduce_stats_kernel, dim3((unsigned)p), dim3(RED_BLOCK), 0, s, x, (long long)n, threshold, (Stats*)workspace);
-    hipLaunchKernelGGL(vfn_reduce_stats_top_kernel, dim3(1), dim3(RED_TOP), 0, s, (const Stats*)workspace, p, stats);
+    const long long p = tree_tiles(n);
+    hipLaunchKernelGGL(vfn_reduce_stats_kernel, dim3((unsigned)p), dim3(TREE_LANES), 0, s, x, (long long)n, threshold, (Stats*)workspace);
+    hipLaunchKernelGGL(vfn_reduce_stats_top_kernel, dim3(1), dim3(TREE_TOP), 0, s, (const Stats*)workspace, p, stats);
     return vfn_check_launch("vfn_reduce_stats");
 }

@@ -158,6 +158,13 @@ def header_abi_version() -> int:
     return int(re.search(r"#define\s+VFN_ABI_VERSION\s+(\d+)", _header_raw()).group(1))
 
 
+@functools.lru_cache(maxsize=None)
+def header_constant(name: str) -> int:
+    """An integer ``#define`` of include/vfn.h (the header is the single source the kernels are compiled from)."""
+    import re
+    return int(re.search(r"#define\s+" + name + r"\s+(\d+)", _header_raw()).group(1))
+
+
 def __getattr__(name: str):
     # read on first use, not at import: the CPU-only parts of the package (loss, optimizer, host logic) import this module too
     if name == "ABI_VERSION":            # include/vfn.h is the single source: the library must report the same number
@@ -165,6 +172,10 @@ def __getattr__(name: str):
     if name == "HEADER_PATH":
         _header_raw()
         return _header_cache["path"]
+    if name == "REDUCE_TILE":            # values per first-level partial of the fixed tree
+        return header_constant("VFN_TREE_LANES") * header_constant("VFN_TREE_PER")
+    if name in ("REDUCE_TOP", "IMAGE_TOP"):          # lanes of its second level
+        return header_constant("VFN_TREE_TOP")
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -1368,7 +1379,7 @@ def mesh_dedup(tri_verts: torch.Tensor, info: Optional[torch.Tensor] = None):
 # ------------------------------------------------------------------------------------------------
 # mesh scoring (csrc/vfn_metrics.hip; vf_nerf_amd/metrics3d.py is the public surface).  Everything float64, contiguous, on one device.
 # ------------------------------------------------------------------------------------------------
-CUMSUM_TILE, REDUCE_TILE, REDUCE_TOP = 1024, 4096, 1024      # csrc/vfn_metrics.hip: SCAN_TILE, RED_TILE, RED_TOP
+CUMSUM_TILE = 1024                 # csrc/vfn_metrics.hip: SCAN_TILE
 
 
 def nn_sqdist(queries: torch.Tensor, targets: torch.Tensor, info: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1449,24 +1460,27 @@ def reduce_stats(x: torch.Tensor, threshold: float) -> torch.Tensor:
     return stats
 
 
+def tree_sum_levels(lane_levels: int, partials: int) -> int:
+    """Addition levels of a sum along the fixed tree of include/vfn.h: what a lane adds before the block tree, the block tree over
+    VFN_TREE_LANES lanes, the serial run of the second level (ceil(partials / VFN_TREE_TOP) - 1), its block tree."""
+    lanes, top = header_constant("VFN_TREE_LANES"), header_constant("VFN_TREE_TOP")
+    return lane_levels + (lanes.bit_length() - 1) + ((partials + top - 1) // top - 1) + (top.bit_length() - 1)
+
+
+def _tree_tiles(n: int) -> int:
+    tile = header_constant("VFN_TREE_LANES") * header_constant("VFN_TREE_PER")
+    return (n + tile - 1) // tile
+
+
 def reduce_sum_levels(n: int) -> int:
-    """Addition levels of vfn_reduce_stats's sum over n values: 4 (a lane's 16 values) + 8 (256 lanes) + the serial run of the second
-    level (ceil(P / 1024) - 1, P = ceil(n / 4096) partials) + 10 (1024 lanes)."""
-    p = (n + REDUCE_TILE - 1) // REDUCE_TILE
-    return 4 + 8 + ((p + REDUCE_TOP - 1) // REDUCE_TOP - 1) + 10
+    """Addition levels of vfn_reduce_stats's sum over n values: a lane's 16 values (4), P = ceil(n / 4096) partials."""
+    return tree_sum_levels(4, _tree_tiles(n))
 
 
 # ------------------------------------------------------------------------------------------------
 # point-set alignment (csrc/vfn_icp.hip; vf_nerf_amd/icp.py is the public surface).  Everything float64, contiguous, on one device.
 # ------------------------------------------------------------------------------------------------
 ICP_SUMS = 17                      # count, sum d2, sum p[3], sum s[3], sum p s^T [9] (include/vfn.h: vfn_icp_accumulate)
-
-
-@functools.lru_cache(maxsize=None)
-def header_constant(name: str) -> int:
-    """An integer ``#define`` of include/vfn.h (the header is the single source the kernels are compiled from)."""
-    import re
-    return int(re.search(r"#define\s+" + name + r"\s+(\d+)", _header_raw()).group(1))
 
 
 def icp_grid_limits():
@@ -1544,15 +1558,14 @@ def icp_check(status: int) -> None:
 
 
 def icp_sum_levels(n: int) -> int:
-    """Addition levels of every sum of vfn_icp_accumulate over n rows: the tree of vfn_reduce_stats."""
-    return reduce_sum_levels(n)
+    """Addition levels of every sum of vfn_icp_accumulate over n rows: a lane's 16 rows (4), P = ceil(n / 4096) partials."""
+    return tree_sum_levels(4, _tree_tiles(n))
 
 
 # ------------------------------------------------------------------------------------------------
 # image scores (csrc/vfn_image.hip; vf_nerf_amd/metrics2d.py is the public surface).  Contiguous tensors on one device.
 # ------------------------------------------------------------------------------------------------
 IMAGE_STATUS_RANGE = 4             # info bit of vfn_image_quantize8: a value outside the range of a byte
-IMAGE_TOP = 1024                   # csrc/vfn_image.hip: IMG_TOP (lanes of the second level)
 SSIM_C1, SSIM_C2 = 1e-4, 9e-4      # utils/utils.py:249 (get_ssim's defaults)
 
 
@@ -1615,11 +1628,9 @@ def image_abs_err(a: torch.Tensor, b: torch.Tensor, scale: float, info: torch.Te
 
 
 def image_sum_levels(h: int, w: int, c: int) -> int:
-    """Addition levels of a per-view sum of vfn_image_scores: the lane's channels (c - 1), the tile tree (8), the serial run of the second
-    level (ceil(P / 1024) - 1, P = tiles per view), its tree (10)."""
+    """Addition levels of a per-view sum of vfn_image_scores: the lane's channels (c - 1), P = tiles per view."""
     t = image_tile()
-    p = ((h + t - 1) // t) * ((w + t - 1) // t)
-    return (c - 1) + 8 + ((p + IMAGE_TOP - 1) // IMAGE_TOP - 1) + 10
+    return tree_sum_levels(c - 1, ((h + t - 1) // t) * ((w + t - 1) // t))
 
 
 # ------------------------------------------------------------------------------------------------
