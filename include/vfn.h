@@ -814,6 +814,28 @@ int vfn_reduce_stats(const double* x, int64_t n, double threshold, double* stats
  *                     — not the order of vfn_reduce_stats: the same shape and depth, other pairs.  Rows without a neighbour and rows
  *                     past n join as the identity (+0.0).  An index >= m: info[0] |= 2, the row is skipped.
  *                     workspace: vfn_icp_accumulate_workspace_bytes(n) bytes (the partials); -1 on error.
+ *   vfn_nn_nearest    (csrc/vfn_nn.hip) the UNBOUNDED search, with the index: for every query i, over ALL targets j, the minimum of
+ *                     (d2(j), j) in lexicographic order, d2(j) = (dx dx + dy dy) + dz dz with dx = q.x - t_j.x, ... (no transform
+ *                     argument): sqdist[i] = that d2 — vfn_nn_sqdist's best[i] bit for bit — and index[i] = the LOWEST original index
+ *                     that attains it.  The definition does not mention a grid and the grid changes no bit; it only bounds the work.
+ *                     The grid is vfn_nn_radius's, with the same meaning of sorted_targets, perm, cell_start, box[7] (HOST memory),
+ *                     nx, ny, nz, cell(), order[n] and check_finite; no radius: the cell edge h = box[6] is any normal number with
+ *                     (e - o) / h <= 129 on every axis and ((VFN_ICP_GRID_CAP + 2) h)^2 finite.
+ *                     One lane per query.  Per axis a = fl(fl(min(max(x, o), e) - o) / h), c = cell(x), f = a - c (exact);
+ *                     s = the minimum over the three axes of min(f, max(fl(1 - f), 0)).  Ring r = the cells at Chebyshev distance
+ *                     exactly r from (c_x, c_y, c_z), clipped to the grid.  The rings are visited in the order r = 0, 1, ...; after
+ *                     ring r the query STOPS when rings 0..r cover the whole grid, or when
+ *                       fl(r + s) >= 2^-20  and  lb >= 2^-1022  and  best < lb,   w = fl(fl(r + s) h),  lb = fl(fl(w w) (1 - 2^-20)),
+ *                     best = the least d2 so far (+inf before the first target); its outputs are then written (index -1 and +inf
+ *                     only when no target has d2 < +inf).  A query that has not stopped after ring max_rings (>= 0) is a LEFTOVER:
+ *                     its outputs are not written, its number i goes to leftover[k], k = an integer atomicAdd of 1 on
+ *                     leftover_count[0] (device memory, zero-filled by the caller; leftover has room for n entries).  The order of
+ *                     the list is arbitrary and no output depends on it; its LENGTH is a function of the queries, the grid and
+ *                     max_rings alone.  The argument that a stopped query has missed no target that could win or tie is in
+ *                     csrc/vfn_nn.hip.
+ *   vfn_nn_nearest_list  the same minimum for the count queries listed in leftover[count] (1 <= count <= n), by all m targets[m, 3] in
+ *                     their ORIGINAL order, one wave per query: writes index[i] and sqdist[i] of the listed queries only.  With every
+ *                     query listed this is the all-pairs search with an index.
  * ============================================================================================= */
 #define VFN_ICP_GRID_CAP 128          /* cells per axis at most */
 #define VFN_ICP_GRID_MARGIN_LOG2 20   /* the cell edge is at least radius (1 + 2^-20) */
@@ -825,6 +847,12 @@ int64_t vfn_icp_accumulate_workspace_bytes(int64_t n);
 int vfn_icp_accumulate(const double* queries, int64_t n, const double* transform, const double* targets, int64_t m,
                        const int64_t* index, const double* sqdist, const double* anchor, double* sums, int64_t* info,
                        void* workspace, int64_t workspace_bytes, void* stream);
+int vfn_nn_nearest(const double* queries, int64_t n, const double* sorted_targets, const int64_t* perm, int64_t m,
+                   const int32_t* cell_start, const double* box, int32_t nx, int32_t ny, int32_t nz, int32_t max_rings,
+                   const int64_t* order, int32_t check_finite, int64_t* index, double* sqdist, int64_t* leftover,
+                   int64_t* leftover_count, int64_t* info, void* stream);
+int vfn_nn_nearest_list(const double* queries, int64_t n, const double* targets, int64_t m, const int64_t* leftover, int64_t count,
+                        int64_t* index, double* sqdist, void* stream);
 
 /* =============================================================================================
  * Scoring rendered views (csrc/vfn_image.hip): the image half of evaluation/methods.py:549-610 (metrics) — utils/utils.py:235-245

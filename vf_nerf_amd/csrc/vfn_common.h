@@ -31,6 +31,18 @@ __device__ __forceinline__ double vfn_pair_sqdist(double qx, double qy, double q
     return (dx * dx + dy * dy) + dz * dz;
 }
 
+// The cell of a coordinate along one axis of the grid of include/vfn.h (vfn_nn_radius, vfn_nn_nearest): ONE definition for the two
+// searches — both arguments about the grid (csrc/vfn_icp.hip, csrc/vfn_nn.hip) are about this expression.  vfn_cell_coord is the real
+// cell coordinate fl(fl(clamp(x, o, e) - o) / h); the clamp to [0, dim - 1] happens in double, before the conversion.
+__device__ __forceinline__ double vfn_cell_coord(double x, double o, double e, double h) {
+    x = fmin(fmax(x, o), e);
+    return (x - o) / h;
+}
+__device__ __forceinline__ int vfn_cell_of(double x, double o, double e, double h, int dim) {
+    const double c = floor(vfn_cell_coord(x, o, e, h));
+    return (int)fmin(fmax(c, 0.0), (double)(dim - 1));
+}
+
 // launches shared between translation units, not part of the ABI (csrc/vfn_rays.hip, used by csrc/vfn_render.hip)
 int vfn_internal_raygen(const vfn_raygen_params* p, const float* uv, const float* pose, const float* intrinsics, const float* k_sign,
                         const float* t_vals, const float* far_per_ray, const float* u_coarse, int gen_u, long long u_base, uint64_t seed,

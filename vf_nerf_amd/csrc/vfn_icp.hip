@@ -53,13 +53,6 @@ __device__ __forceinline__ void apply(const Xform& T, double x, double y, double
     }
 }
 
-// the cell of a coordinate along one axis (see the argument above); the clamp happens in double, before the conversion
-__device__ __forceinline__ int cell_of(double x, double o, double e, double h, int dim) {
-    x = fmin(fmax(x, o), e);
-    const double c = floor((x - o) / h);
-    return (int)fmin(fmax(c, 0.0), (double)(dim - 1));
-}
-
 __global__ __launch_bounds__(256) void vfn_icp_finite_kernel(const double* __restrict__ q, long long n, const double* __restrict__ t, long long m,
                                                              unsigned long long* __restrict__ info) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -91,9 +84,9 @@ __global__ __launch_bounds__(ICP_BLOCK) void vfn_nn_radius_kernel(const double* 
     if (i < 0 || i >= n) return;
     double px, py, pz;
     apply(T, q[3 * i], q[3 * i + 1], q[3 * i + 2], px, py, pz);
-    const int cx = cell_of(px, g.o[0], g.e[0], g.h, g.dim[0]);
-    const int cy = cell_of(py, g.o[1], g.e[1], g.h, g.dim[1]);
-    const int cz = cell_of(pz, g.o[2], g.e[2], g.h, g.dim[2]);
+    const int cx = vfn_cell_of(px, g.o[0], g.e[0], g.h, g.dim[0]);              // (vfn_common.h: shared with csrc/vfn_nn.hip)
+    const int cy = vfn_cell_of(py, g.o[1], g.e[1], g.h, g.dim[1]);
+    const int cz = vfn_cell_of(pz, g.o[2], g.e[2], g.h, g.dim[2]);
     const int x0 = cx > 0 ? cx - 1 : 0, x1 = cx + 1 < g.dim[0] ? cx + 1 : g.dim[0] - 1;
     const int y0 = cy > 0 ? cy - 1 : 0, y1 = cy + 1 < g.dim[1] ? cy + 1 : g.dim[1] - 1;
     const int z0 = cz > 0 ? cz - 1 : 0, z1 = cz + 1 < g.dim[2] ? cz + 1 : g.dim[2] - 1;

@@ -50,7 +50,7 @@ class Grid:
     cell_start: torch.Tensor           # [cells + 1] int32
     box: Tuple[float, ...]             # min[3], max[3], cell edge
     dims: Tuple[int, int, int]
-    radius: float
+    radius: float                      # 0.0: the grid of the unbounded search (metrics3d.nearest_grid), which vfn_nn_radius refuses
 
     @property
     def anchor(self) -> Tuple[float, float, float]:
@@ -59,6 +59,10 @@ class Grid:
 
     def args(self):
         return self.sorted_targets, self.perm, self.cell_start, self.box, self.dims
+
+    def nearest_args(self):
+        """What ``lib.nn_nearest`` takes: the same, after the targets in their original order (its all-pairs launch reads those)."""
+        return (self.targets,) + self.args()
 
 
 @dataclasses.dataclass
@@ -129,9 +133,10 @@ def _cells(points: torch.Tensor, box, dims, dev) -> torch.Tensor:
     return (c[:, 0] * dims[1] + c[:, 1]) * dims[2] + c[:, 2]
 
 
-def build_grid(targets: torch.Tensor, radius: float) -> Grid:
+def build_grid(targets: torch.Tensor, radius: float, edge=None) -> Grid:
     """Device targets [m,3] float64 -> their ``Grid`` for searches within ``radius``.  Plumbing in torch: the bounding box (six values
-    cross to the host), the cell edge, a stable sort by cell key, the table of first positions.
+    cross to the host), the cell edge, a stable sort by cell key, the table of first positions.  ``edge`` (a function of the box's three
+    extents) chooses the cell edge instead: the grid of the unbounded search (``metrics3d.nearest_grid``), which has no radius.
 
     Cell edge h = radius (1 + 2^-20), enlarged to extent / 128 (1 + 2^-20) on the longest axis when that is larger: at most
     GRID_CAP = 128 cells an axis, so the table never exceeds 128^3 + 1 entries when the radius is tiny against the extent (the cells
@@ -144,8 +149,11 @@ def build_grid(targets: torch.Tensor, radius: float) -> Grid:
     if not all(math.isfinite(e) for e in extent):
         raise lib.VfnError("point-set alignment: the targets' bounding box overflows float64")
     cap, margin = lib.icp_grid_limits()
-    h = radius * margin
-    h = max([h] + [e / cap * margin for e in extent])
+    if edge is None:
+        h = radius * margin
+        h = max([h] + [e / cap * margin for e in extent])
+    else:
+        h = edge(extent)
     dims = tuple(min(cap, int(math.floor(e / h)) + 1) for e in extent)
     box = tuple(box) + (h,)
     key = _cells(targets, box, dims, dev)

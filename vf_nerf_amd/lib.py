@@ -46,6 +46,7 @@ EXPORTS = (
     "vfn_tsdf_integrate", "vfn_tsdf_count", "vfn_tsdf_emit", "vfn_tsdf_integrate_rgb", "vfn_tsdf_emit_colours", "vfn_tsdf_vertex_colours",
     "vfn_raster_depth", "vfn_smooth_laplacian_step",
     "vfn_transform_points", "vfn_nn_radius", "vfn_icp_accumulate_workspace_bytes", "vfn_icp_accumulate",
+    "vfn_nn_nearest", "vfn_nn_nearest_list",
     "vfn_image_quantize8", "vfn_image_scores_workspace_bytes", "vfn_image_scores", "vfn_image_abs_err",
 )
 
@@ -1526,6 +1527,46 @@ def nn_radius(queries: torch.Tensor, transform, grid, radius: float, order: Opti
     if own:
         nn_check(int(info.cpu()))
     return index, sqdist
+
+
+def nn_nearest(queries: torch.Tensor, grid, max_rings: int, order: Optional[torch.Tensor] = None, info: Optional[torch.Tensor] = None,
+               check_finite: bool = True):
+    """-> (index[n] int64, sqdist[n], leftover_count) of every query's nearest target over ALL targets, ties to the lowest original index
+    (include/vfn.h: vfn_nn_nearest).  ``grid`` = (targets[m,3] in their original order, sorted_targets[m,3], perm[m] int64,
+    cell_start[cells+1] int32, box: 7 floats, dims: 3 ints).  The ring search leaves the queries that have not stopped after ring
+    ``max_rings`` on a list; ONE host read — the list's length and the status word — and, unless the list is empty, a second launch
+    serves them by all pairs (vfn_nn_nearest_list).  ``leftover_count`` (a Python int) only tells how the work was split: no bit of
+    the result depends on ``max_rings``, ``order`` or the grid.  That read brings the status word with it, so a non-finite coordinate
+    raises here whether or not the caller gave its own zero-filled ``info`` (int64 [1])."""
+    targets, sorted_targets, perm, cell_start, box, dims = grid
+    n, m = queries.shape[0], sorted_targets.shape[0]
+    if isinstance(max_rings, bool) or not isinstance(max_rings, int) or max_rings < 0:
+        raise VfnError(f"nn_nearest: max_rings must be a non-negative integer, got {max_rings!r}")
+    if (targets.shape[0] != m or perm.shape[0] != m or cell_start.shape[0] != dims[0] * dims[1] * dims[2] + 1
+            or (order is not None and order.shape[0] != n)):
+        raise VfnError("nn_nearest: targets / perm / cell_start / order do not have the lengths the grid and the queries give")
+    dev = queries.device
+    index = torch.empty(n, dtype=torch.int64, device=dev)
+    sqdist = torch.empty(n, dtype=torch.float64, device=dev)
+    leftover = torch.empty(n, dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    if info is None:
+        info = torch.zeros(1, dtype=torch.int64, device=dev)
+    q = _ptr(queries, "queries", torch.float64)
+    _check(load().vfn_nn_nearest(q, C.c_int64(n), _ptr(sorted_targets, "sorted_targets", torch.float64), _ptr(perm, "perm", torch.int64),
+                                 C.c_int64(m), _ptr(cell_start, "cell_start", torch.int32), (C.c_double * 7)(*box), C.c_int32(dims[0]),
+                                 C.c_int32(dims[1]), C.c_int32(dims[2]), C.c_int32(min(max_rings, 2 ** 31 - 1)), _ptr(order, "order", torch.int64),
+                                 C.c_int32(int(check_finite)), _ptr(index, "index", torch.int64), _ptr(sqdist, "sqdist", torch.float64),
+                                 _ptr(leftover, "leftover", torch.int64), _ptr(count, "leftover_count", torch.int64),
+                                 _ptr(info, "info", torch.int64), _stream()), "vfn_nn_nearest")
+    left, status = (int(x) for x in torch.cat((count, info)).cpu())          # the one read between the two launches
+    nn_check(status)
+    left = min(left, n)
+    if left:
+        _check(load().vfn_nn_nearest_list(q, C.c_int64(n), _ptr(targets, "targets", torch.float64), C.c_int64(m),
+                                          _ptr(leftover, "leftover", torch.int64), C.c_int64(left), _ptr(index, "index", torch.int64),
+                                          _ptr(sqdist, "sqdist", torch.float64), _stream()), "vfn_nn_nearest_list")
+    return index, sqdist, left
 
 
 def icp_accumulate(queries: torch.Tensor, transform, targets: torch.Tensor, index: torch.Tensor, sqdist: torch.Tensor, anchor,

@@ -4,6 +4,13 @@ threshold — without copying either mesh to the host.
 
 * ``nearest_distances`` — every query's distance to its nearest target: all pairs in float64, bit-equal to
   ``scipy.spatial.cKDTree(targets).query(queries)[0]`` (tests/test_metrics3d_host.py, tests/test_hip_metrics3d.py).  No index.
+* ``nearest`` — the same distance WITH the index of the target that attains it (ties to the lowest index), by a uniform grid over the
+  targets searched ring by ring (csrc/vfn_nn.hip, include/vfn.h: ``vfn_nn_nearest``): exact, unbounded, and bit-equal to the all-pairs
+  search whatever the grid — an exact lower bound on every unvisited target's distance ends a query's search; a query it has not
+  ended after ``max_rings`` rings is served by all pairs.  ``nearest_grid`` builds the grid of a target set once for several searches.
+* ``search="grid"`` on ``nearest_distances``, ``chamfer_from_points``, ``chamfer_distance``, ``precision_recall_fscore`` and
+  ``score_mesh`` runs their searches through that kernel instead of all pairs (the default, ``"all_pairs"``): one grid per point set
+  and direction, and the same numbers to the bit — only the time differs (DESIGN 6i has the measurements).
 * ``sample_surface`` — area-weighted surface samples (face by cumulative area, folded-square barycentric coordinates).
 * ``chamfer_from_points`` / ``chamfer_distance`` — the reference's four numbers with the reference's combination.
 * ``precision_recall_fscore`` — shares of points within a threshold of the other set.
@@ -32,8 +39,12 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import geomargs, lib
+from . import geomargs, icp, lib
 from .geomargs import LIMIT
+
+SEARCHES = ("all_pairs", "grid")
+MAX_RINGS = 8                      # rings a query of the grid search visits before it is left to all pairs (speed only)
+GRID_TARGETS_PER_CELL = 8          # the default grid has about sqrt(m / 8) cells along the longest axis (speed only)
 
 # this unit's forms of the shared checks (module attributes, so a test can stand in for the device)
 _device = functools.partial(geomargs.device, what="mesh scoring")
@@ -62,16 +73,100 @@ def _check_threshold(threshold) -> float:
     return float(threshold)
 
 
+def _check_search(search) -> str:
+    if search not in SEARCHES:
+        raise ValueError(f"search must be one of {SEARCHES}, got {search!r}")
+    return search
+
+
+def _search_kw(search) -> dict:
+    """The checked ``search`` as the keyword of ``_both_directions``: none for the default, whose call stays what it was."""
+    return {} if _check_search(search) == "all_pairs" else {"search": search}
+
+
+def _check_max_rings(max_rings) -> int:
+    if isinstance(max_rings, bool) or not isinstance(max_rings, (int, np.integer)) or int(max_rings) < 0:
+        raise ValueError(f"max_rings must be a non-negative integer, got {max_rings!r}")
+    return int(max_rings)
+
+
+def _check_cells(cells) -> Optional[int]:
+    cap = lib.icp_grid_limits()[0]
+    if cells is None:
+        return None
+    if isinstance(cells, bool) or not isinstance(cells, (int, np.integer)) or not 1 <= int(cells) <= cap:
+        raise ValueError(f"cells must be None or an integer in [1, {cap}], got {cells!r}")
+    return int(cells)
+
+
 def _dev_points(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
     return t.to(dev, torch.float64).contiguous()
 
 
-def nearest_distances(queries, targets, device=None) -> torch.Tensor:
-    """queries[n,3], targets[m,3] -> float64 [n] on the device: the distance of every query to its nearest target (sqrt of the kernel's
-    exact minimum of squared distances).  A NaN / inf coordinate raises ``lib.VfnError``."""
-    q, t = _check_points(queries, "queries"), _check_points(targets, "targets")
+def grid_edge(extent, m: int, cells: Optional[int] = None) -> float:
+    """The cell edge of the unbounded search's grid over m targets whose bounding box has the three ``extent``s (host arithmetic):
+    ``cells`` cells along the longest axis — by default min(128, max(1, ceil(sqrt(m / 8)))), about eight targets a cell when they lie
+    on a surface — so h = longest / cells (1 + 2^-20); h = 1.0 for a box without extent.  Only speed depends on it."""
+    cap, margin = lib.icp_grid_limits()
+    if cells is None:
+        cells = min(cap, max(1, math.ceil(math.sqrt(m / GRID_TARGETS_PER_CELL))))
+    longest = max(extent)
+    return longest / cells * margin if longest > 0 else 1.0
+
+
+def _grid(targets: torch.Tensor, cells: Optional[int]) -> "icp.Grid":
+    """Device targets -> their grid for the unbounded search (``icp.build_grid``'s plumbing with ``grid_edge``'s cell edge; no radius)."""
+    return icp.build_grid(targets, 0.0, edge=lambda extent: grid_edge(extent, targets.shape[0], cells))
+
+
+def nearest_grid(targets, cells: Optional[int] = None, device=None) -> "icp.Grid":
+    """targets[m,3] -> the ``icp.Grid`` that ``nearest`` builds for them: the targets sorted by the cell of a uniform grid with
+    ``cells`` cells along the longest axis of their bounding box (None: ``grid_edge``'s default; at most 128).  Give it to ``nearest``
+    in place of the targets to search the same set several times."""
+    t = _check_points(targets, "targets")
+    cells = _check_cells(cells)
     dev = _device(device)
-    return torch.sqrt(lib.nn_sqdist(_dev_points(q, dev), _dev_points(t, dev)))
+    with torch.cuda.device(dev):
+        return _grid(_dev_points(t, dev), cells)
+
+
+def _nearest_sq(q: torch.Tensor, t: torch.Tensor, search: str, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Device queries and targets -> the squared nearest distances by the chosen search: the same bits either way."""
+    if search == "all_pairs":
+        return lib.nn_sqdist(q, t, info=info)
+    with torch.cuda.device(q.device):
+        grid = _grid(t, None)
+        return lib.nn_nearest(q, grid.nearest_args(), MAX_RINGS, order=icp.query_order(q, None, grid), info=info)[1]
+
+
+def nearest(queries, targets, device=None, max_rings: int = MAX_RINGS, cells: Optional[int] = None):
+    """queries[n,3], targets[m,3] (or a ``nearest_grid`` of them) -> (index int64 [n], distance float64 [n]) on the device: for every
+    query the index of its nearest target over ALL targets and the distance to it — ``nearest_distances`` to the bit; among targets at
+    the same squared distance the lowest index.  ``max_rings`` (>= 0) and ``cells`` change the time, never a bit: a query whose search
+    the ring bound has not ended after ring ``max_rings`` goes to an all-pairs pass.  A NaN / inf coordinate raises ``lib.VfnError``."""
+    q = _check_points(queries, "queries")
+    max_rings, cells = _check_max_rings(max_rings), _check_cells(cells)
+    grid = targets if isinstance(targets, icp.Grid) else None
+    if grid is not None and cells is not None:
+        raise ValueError("cells is the grid's own: give it to nearest_grid")
+    t = None if grid is not None else _check_points(targets, "targets")
+    dev = grid.targets.device if grid is not None else _device(device)
+    with torch.cuda.device(dev):
+        q = _dev_points(q, dev)
+        if grid is None:
+            grid = _grid(_dev_points(t, dev), cells)
+        index, sqdist, _ = lib.nn_nearest(q, grid.nearest_args(), max_rings, order=icp.query_order(q, None, grid))
+    return index, torch.sqrt(sqdist)
+
+
+def nearest_distances(queries, targets, device=None, search: str = "all_pairs") -> torch.Tensor:
+    """queries[n,3], targets[m,3] -> float64 [n] on the device: the distance of every query to its nearest target (sqrt of the kernel's
+    exact minimum of squared distances).  ``search``: "all_pairs" or "grid" (``nearest``'s kernel; the same bits).  A NaN / inf
+    coordinate raises ``lib.VfnError``."""
+    q, t = _check_points(queries, "queries"), _check_points(targets, "targets")
+    search = _check_search(search)
+    dev = _device(device)
+    return torch.sqrt(_nearest_sq(_dev_points(q, dev), _dev_points(t, dev), search))
 
 
 def face_areas(vertices, faces, device=None) -> torch.Tensor:
@@ -152,51 +247,54 @@ def _prf(pred_row, ref_row) -> dict:
     return {"precision": p, "recall": r, "fscore": 2 * p * r / (p + r) if p + r > 0 else 0.0, "pred_within": n_p, "ref_within": n_r}
 
 
-def _both_directions(pred_points, ref_points, threshold: float, device=None):
-    """-> host float64 [2,7]: row 0 = the ref points against the pred set, row 1 = the pred points against the ref set.  One read."""
+def _both_directions(pred_points, ref_points, threshold: float, device=None, search: str = "all_pairs"):
+    """-> host float64 [2,7]: row 0 = the ref points against the pred set, row 1 = the pred points against the ref set.  One read
+    of the results (the grid search adds its own: a box per grid, a count per search)."""
     p, r = _check_points(pred_points, "pred_points"), _check_points(ref_points, "ref_points")
     dev = _device(device)
     p, r = _dev_points(p, dev), _dev_points(r, dev)
     info = torch.zeros(1, dtype=torch.int64, device=dev)
-    one = _direction(torch.sqrt(lib.nn_sqdist(r, p, info=info)), threshold)
-    two = _direction(torch.sqrt(lib.nn_sqdist(p, r, info=info)), threshold)
+    one = _direction(torch.sqrt(_nearest_sq(r, p, search, info=info)), threshold)
+    two = _direction(torch.sqrt(_nearest_sq(p, r, search, info=info)), threshold)
     host = torch.cat((one, two, info.to(torch.float64))).cpu().numpy()
     lib.nn_check(int(host[14]))
     return host[:14].reshape(2, 7)
 
 
-def chamfer_from_points(pred_points, ref_points, device=None) -> Tuple[float, float, float, float]:
+def chamfer_from_points(pred_points, ref_points, device=None, search: str = "all_pairs") -> Tuple[float, float, float, float]:
     """utils.py:350-367 on two point sets -> (mean, median, min, max) as Python floats: per direction the mean / median / min / max of
     the squared nearest distances, then the sum of the means, the sum of the medians, the min of the mins, the max of the maxes.  The
-    median is np.median's (the mean of the two middle values for an even count)."""
-    rows = _both_directions(pred_points, ref_points, 0.0, device)
+    median is np.median's (the mean of the two middle values for an even count).  ``search`` as in ``nearest_distances``."""
+    rows = _both_directions(pred_points, ref_points, 0.0, device, **_search_kw(search))
     return _chamfer(rows[0], rows[1])
 
 
-def chamfer_distance(pred_mesh, ref_mesh, num_points: int = 2500000, generator: Optional[torch.Generator] = None, device=None):
+def chamfer_distance(pred_mesh, ref_mesh, num_points: int = 2500000, generator: Optional[torch.Generator] = None, device=None,
+                     search: str = "all_pairs"):
     """``utils.get_chamfer_distance``: ``num_points`` samples of each surface (pred first, then ref, from the same generator), then
-    ``chamfer_from_points``."""
+    ``chamfer_from_points`` (``search`` goes there)."""
+    search = _check_search(search)
     pv, pf = _check_mesh(pred_mesh, "pred_mesh")
     rv, rf = _check_mesh(ref_mesh, "ref_mesh")
     num_points = geomargs.positive_int(num_points, "num_points")
     pred_points, _ = sample_surface(pv, pf, num_points, generator=generator, device=device)
     ref_points, _ = sample_surface(rv, rf, num_points, generator=generator, device=device)
-    return chamfer_from_points(pred_points, ref_points, device=device)
+    return chamfer_from_points(pred_points, ref_points, device=device, search=search)
 
 
-def precision_recall_fscore(pred_points, ref_points, threshold: float, device=None) -> dict:
+def precision_recall_fscore(pred_points, ref_points, threshold: float, device=None, search: str = "all_pairs") -> dict:
     """precision = the share of pred points whose nearest ref point is closer than ``threshold`` (distance < threshold), recall = the
     share of ref points whose nearest pred point is closer than ``threshold``, fscore = 2 P R / (P + R), 0 when P + R = 0.  The counts
     are returned too (``pred_within``, ``ref_within``).  This is the plain definition on the two point sets as given; it is NOT claimed
     equal to the external ``evaluate_3d_reconstruction`` package the reference calls, which also voxel-down-samples both clouds and
-    optionally aligns them with ICP first."""
+    optionally aligns them with ICP first.  ``search`` as in ``nearest_distances``."""
     threshold = _check_threshold(threshold)
-    rows = _both_directions(pred_points, ref_points, threshold, device)
+    rows = _both_directions(pred_points, ref_points, threshold, device, **_search_kw(search))
     return _prf(rows[1], rows[0])
 
 
 def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: float = 0.05, generator: Optional[torch.Generator] = None,
-               uniforms=None, device=None, icp_align: bool = False, icp_threshold: Optional[float] = None) -> dict:
+               uniforms=None, device=None, icp_align: bool = False, icp_threshold: Optional[float] = None, search: str = "all_pairs") -> dict:
     """One entry of the reference's ``3d-metrics.json`` (methods.py:794-801): {"chamfer distance": {mean, median, min, max}, "precision",
     "recall", "fscore"} (plus the two counts), from ONE sampling of each mesh and ONE nearest-neighbour search per direction shared
     by both metrics.  ``uniforms`` ([num_points,3]) is used for BOTH meshes when given.
@@ -204,7 +302,10 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
     ``icp_align=True``: the pred samples are aligned to the ref samples with ``icp.align`` (correspondences within ``icp_threshold``;
     None = ``distance_thresh`` — that default is ours, not the external package's), moved by the result and scored as above; the
     entry gains "icp": {"transformation" (nested lists), "fitness", "inlier_rmse", "iterations"}.  With ``icp_align=False`` nothing
-    changes: the same keys, values and draws from the generator as without the keyword."""
+    changes: the same keys, values and draws from the generator as without the keyword.
+
+    ``search="grid"``: the two scoring searches go through the grid kernel (``nearest``); the dictionary is the same to the bit."""
+    search = _check_search(search)
     pv, pf = _check_mesh(pred_mesh, "pred_mesh")
     rv, rf = _check_mesh(ref_mesh, "ref_mesh")
     num_points = geomargs.positive_int(num_points, "num_points")
@@ -212,7 +313,6 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
     if not isinstance(icp_align, (bool, np.bool_)):
         raise ValueError(f"icp_align must be a bool, got {icp_align!r}")
     if icp_align:
-        from . import icp
         icp_radius = icp._check_radius(threshold if icp_threshold is None else icp_threshold, "icp_threshold")
     pred_points, _ = sample_surface(pv, pf, num_points, generator=generator, uniforms=uniforms, device=device)
     ref_points, _ = sample_surface(rv, rf, num_points, generator=generator, uniforms=uniforms, device=device)
@@ -220,7 +320,7 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
     if icp_align:
         aligned = icp.align(pred_points, ref_points, icp_radius, device=pred_points.device)
         pred_points = icp.transform_points(pred_points, aligned.transformation, device=pred_points.device)
-    rows = _both_directions(pred_points, ref_points, threshold, device)
+    rows = _both_directions(pred_points, ref_points, threshold, device, **_search_kw(search))
     mean, median, mn, mx = _chamfer(rows[0], rows[1])
     out = {"chamfer distance": {"mean": mean, "median": median, "min": mn, "max": mx}}
     out.update(_prf(rows[1], rows[0]))
