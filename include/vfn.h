@@ -1018,6 +1018,38 @@ int vfn_smooth_laplacian_step(const double* src, double* dst, int64_t n_vertices
                               int64_t n_neighbours, double lam, int64_t* info, void* stream);
 
 /* =============================================================================================
+ * Normals of a triangle mesh and the dots of normal consistency (csrc/vfn_normals.hip): what the reference leaves to Open3D's
+ * compute_vertex_normals() before it writes tsdf.ply (evaluation/methods.py:664-665), and the third score beside chamfer distance and
+ * F-score.  A SPECIFICATION: area-weighted vertex normals are Open3D's compute_vertex_normals() as remembered, not verified against
+ * Open3D, and Open3D's sums have no fixed order.  Everything is float64, evaluated without contraction in the association written
+ * here, with no floating-point atomics: no bit depends on the schedule.  Indices are int64.  info[0] (int64, zero-filled by the caller,
+ * only OR-ed into): bit 1 = a non-finite coordinate or normal was read, bit 2 = an index outside its range — nothing is read through
+ * such an index and that row's output is the fallback —, bit 4 = a length that overflowed (finite inputs, a non-finite cross product or
+ * a non-finite r below).  Limits: 0 <= n, m < 2^31 (a count of 0 launches nothing).  Every argument check answers before any launch.
+ *   unit(c, fallback):  s = c.x c.x;  s = s + c.y c.y;  s = s + c.z c.z;  r = sqrt(s) (correctly rounded);
+ *                     r > 0 and finite: (c.x / r, c.y / r, c.z / r), three divisions; otherwise `fallback`, and info bit 4 if r is
+ *                     not finite.
+ *   vfn_face_normals  reads vertices[n, 3], faces[m, 3]; one lane per face: a = v1 - v0, b = v2 - v0,
+ *                       c = (a.y b.z - a.z b.y,  a.z b.x - a.x b.z,  a.x b.y - a.y b.x)      two products and one subtraction each
+ *                     normalise = 0: out[m, 3] = c (its length is twice the area; bit 4 if it is not finite although the coordinates
+ *                     are); normalise = 1: out = unit(c, (0, 0, 0)).  A face with an index outside [0, n): bit 2, out = (0, 0, 0).
+ *   vfn_vertex_normals  reads face_normals[m, 3] (the UNNORMALISED ones) and a CSR of every vertex's faces: row_start[n + 1],
+ *                     incident[row_start[n]], a vertex's faces ascending, each once.  One lane per vertex:
+ *                       s = fn[f_0];  s = s + fn[f_1];  ...                     per component, in the row's order
+ *                       out[n, 3] = unit(s, (0, 0, 1))
+ *                     — area weighting.  A vertex without faces gets (0, 0, 1).  A row outside [0, row_start[n]] (read on the device)
+ *                     or a face outside [0, m): bit 2, (0, 0, 1).  A long row is slow (one lane walks it) and stays correct.
+ *   vfn_normal_dots   reads qn[n, 3], tn[m, 3], index[n]; with j = index[i]:
+ *                       d = qn.x tn[j].x;  d = d + qn.y tn[j].y;  d = d + qn.z tn[j].z;  out[i] = fabs(d)
+ *                     j outside [0, m): bit 2, out[i] = 0.
+ * ============================================================================================= */
+int vfn_face_normals(const double* vertices, int64_t n, const int64_t* faces, int64_t m, int32_t normalise, double* out, int64_t* info,
+                     void* stream);
+int vfn_vertex_normals(const double* face_normals, int64_t m, const int64_t* row_start, const int64_t* incident, int64_t n, double* out,
+                       int64_t* info, void* stream);
+int vfn_normal_dots(const double* qn, int64_t n, const double* tn, int64_t m, const int64_t* index, double* out, int64_t* info, void* stream);
+
+/* =============================================================================================
  * Optimizer side of a training step over ONE flat fp32 buffer (train/vector_field_nerf_train.py:254-260:
  * torch.nn.utils.clip_grad_norm_(model.parameters(), clip); optimizer.step()).  The unique parameters — and their gradients
  * and Adam moments — are laid out contiguously, sorted into up to four REGIONS [start, end) of equal multiplicity `mult` =

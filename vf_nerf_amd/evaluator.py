@@ -13,7 +13,8 @@ downloading the image; ``metrics`` is the drop-in for ``evaluation.methods.metri
 ``render_images`` scored against the dataset's images, ``metrics.json``), installed by ``dropin.install(patch_metrics=True)``.
 
 ``tsdf_mesh`` is the drop-in for ``evaluation.methods.tsdf_mesh`` (methods.py:613-665: the rendered depth maps and PNGs fused into the
-coloured ``tsdf-mesh/tsdf.ply``), installed by ``dropin.install(patch_tsdf_mesh=True)``."""
+coloured ``tsdf-mesh/tsdf.ply``), installed by ``dropin.install(patch_tsdf_mesh=True)``; with ``TSDF_VERTEX_NORMALS`` set it writes the
+vertex normals too, as the reference does (``compute_vertex_normals()``; ours are ``meshops.vertex_normals``)."""
 from __future__ import annotations
 
 import importlib
@@ -30,6 +31,9 @@ MIN_CHUNK = 8192        # rays per launch group of a whole view (see render_view
 # colours: the rendering net is evaluated only for the samples whose weight is non-zero — a few percent — which leaves rgb and depth
 # bit-identical (model.sparse_colours, include/vfn.h vfn_render_params.sparse_colours).  False: the dense plan.
 SPARSE_COLOURS = True
+# tsdf_mesh writes nx ny nz (meshops.vertex_normals of the fused mesh) into tsdf.ply; False: the file without normals.
+# dropin.install(tsdf_vertex_normals=...) sets it.
+TSDF_VERTEX_NORMALS = False
 
 
 @torch.no_grad()
@@ -191,10 +195,11 @@ def tsdf_mesh(eval_path: str, dataset_config) -> None:
     ``image-{i}.png`` (read with PIL: the PNG's bytes) and the dataset's intrinsics / poses — per view for ``dtu`` / ``deepfashion``,
     shared otherwise — fused WITH colour on the device (``tsdf.fuse_rgbd_maps``: voxel length 4/512, ``sdf_trunc`` 0.04, the depth as
     ``tsdf.reference_depth`` states the reference's millimetre round trip, the box of the back-projected depths) and written to
-    ``tsdf-mesh/tsdf.ply`` (``ply.write_ply``: binary, float vertices, uchar colours).  Vertex normals are not written (the reference
-    calls ``compute_vertex_normals()`` first).  Installed by ``dropin.install(patch_tsdf_mesh=True)``."""
+    ``tsdf-mesh/tsdf.ply`` (``ply.write_ply``: binary, float vertices, uchar colours).  The reference calls ``compute_vertex_normals()``
+    first: with the module switch ``TSDF_VERTEX_NORMALS`` set the file also holds ``meshops.vertex_normals`` of the fused mesh (the
+    extraction already merges its vertices: no weld); by default it does not.  Installed by ``dropin.install(patch_tsdf_mesh=True)``."""
     from PIL import Image
-    from . import ply, tsdf
+    from . import meshops, ply, tsdf
     dataset_dict = importlib.import_module("datasets.normal_datasets").dataset_dict
     dataset = dataset_dict[dataset_config.dataset_name](dataset_config)
     images_path = os.path.join(eval_path, "rendered_images")
@@ -214,4 +219,7 @@ def tsdf_mesh(eval_path: str, dataset_config) -> None:
     vertices, faces, colours = tsdf.fuse_rgbd_maps(torch.stack(depths), np.stack(images), torch.stack(intrinsics), torch.stack(poses))
     mesh_path = os.path.join(eval_path, "tsdf-mesh")
     os.makedirs(mesh_path, exist_ok=True)
-    ply.write_ply(os.path.join(mesh_path, "tsdf.ply"), vertices, faces, colours)
+    if TSDF_VERTEX_NORMALS:
+        ply.write_ply(os.path.join(mesh_path, "tsdf.ply"), vertices, faces, colours, normals=meshops.vertex_normals((vertices, faces)))
+    else:
+        ply.write_ply(os.path.join(mesh_path, "tsdf.ply"), vertices, faces, colours)

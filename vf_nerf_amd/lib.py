@@ -48,6 +48,7 @@ EXPORTS = (
     "vfn_transform_points", "vfn_nn_radius", "vfn_icp_accumulate_workspace_bytes", "vfn_icp_accumulate",
     "vfn_nn_nearest", "vfn_nn_nearest_list",
     "vfn_image_quantize8", "vfn_image_scores_workspace_bytes", "vfn_image_scores", "vfn_image_abs_err",
+    "vfn_face_normals", "vfn_vertex_normals", "vfn_normal_dots",
 )
 
 
@@ -1838,6 +1839,79 @@ def smooth_laplacian(vertices: torch.Tensor, row_start: torch.Tensor, neighbours
         if int(info.cpu()) != 0:
             raise VfnError("Laplacian smoothing: the adjacency names a vertex or a row outside its range")
     return a
+
+
+# ------------------------------------------------------------------------------------------------
+# mesh normals (csrc/vfn_normals.hip; vf_nerf_amd/meshops.py is the public surface).  Everything float64 / int64, contiguous, on one device.
+# ------------------------------------------------------------------------------------------------
+GEOM_STATUS_OVERFLOW = 4           # info bit of the normals unit: a length that overflowed
+
+
+def normals_check(status: int, what: str) -> None:
+    if status & GEOM_STATUS_INDEX:
+        raise VfnError(f"{what}: an index lies outside its range")
+    if status & GEOM_STATUS_NONFINITE:
+        raise VfnError(f"{what}: a non-finite coordinate or normal")
+    if status & GEOM_STATUS_OVERFLOW:
+        raise VfnError(f"{what}: a normal's length overflowed")
+
+
+def _own_info(info: Optional[torch.Tensor], dev):
+    return (info, False) if info is not None else (torch.zeros(1, dtype=torch.int64, device=dev), True)
+
+
+def face_normals(vertices: torch.Tensor, faces: torch.Tensor, normalise: bool, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vertices[n,3] float64, faces[m,3] int64 -> [m,3]: the cross product of two edges, a unit vector with ``normalise`` (include/vfn.h:
+    vfn_face_normals).  A bad input raises — or, with the caller's zero-filled ``info`` (int64 [1]), sets its bits (``normals_check``)."""
+    n, m = vertices.shape[0], faces.shape[0]
+    dev = faces.device
+    out = torch.empty(m, 3, dtype=torch.float64, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_face_normals(_ptr(vertices, "vertices", torch.float64) if n else None, C.c_int64(n),
+                                       _ptr(faces, "faces", torch.int64) if m else None, C.c_int64(m), C.c_int32(int(bool(normalise))),
+                                       _ptr(out, "out", torch.float64) if m else None, _ptr(info, "info", torch.int64), _stream()),
+               "vfn_face_normals")
+    if own and m:
+        normals_check(int(info.cpu()), "face normals")
+    return out
+
+
+def vertex_normals(face_normals_raw: torch.Tensor, row_start: torch.Tensor, incident: torch.Tensor, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The unnormalised face normals [m,3] and the incidence CSR (row_start[n+1], incident, int64) -> unit vertex normals [n,3]
+    (include/vfn.h: vfn_vertex_normals).  ``info`` as in ``face_normals``."""
+    m, n = face_normals_raw.shape[0], row_start.shape[0] - 1
+    if n < 0:
+        raise VfnError("vertex_normals: row_start must have n + 1 >= 1 entries")
+    dev = row_start.device
+    out = torch.empty(n, 3, dtype=torch.float64, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_vertex_normals(_ptr(face_normals_raw, "face_normals", torch.float64) if m else None, C.c_int64(m),
+                                         _ptr(row_start, "row_start", torch.int64), _ptr(incident, "incident", torch.int64) if incident.shape[0] else None,
+                                         C.c_int64(n), _ptr(out, "out", torch.float64) if n else None, _ptr(info, "info", torch.int64), _stream()),
+               "vfn_vertex_normals")
+    if own and n:
+        normals_check(int(info.cpu()), "vertex normals")
+    return out
+
+
+def normal_dots(qn: torch.Tensor, tn: torch.Tensor, index: torch.Tensor, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qn[n,3], tn[m,3], index[n] int64 -> |qn[i] . tn[index[i]]| [n] (include/vfn.h: vfn_normal_dots).  ``info`` as in ``face_normals``."""
+    n, m = qn.shape[0], tn.shape[0]
+    if index.shape[0] != n:
+        raise VfnError(f"normal_dots: index must have the queries' {n} rows")
+    dev = qn.device
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_normal_dots(_ptr(qn, "qn", torch.float64) if n else None, C.c_int64(n), _ptr(tn, "tn", torch.float64) if m else None,
+                                      C.c_int64(m), _ptr(index, "index", torch.int64) if n else None,
+                                      _ptr(out, "out", torch.float64) if n else None, _ptr(info, "info", torch.int64), _stream()),
+               "vfn_normal_dots")
+    if own and n:
+        normals_check(int(info.cpu()), "normal dots")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

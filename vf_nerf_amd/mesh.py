@@ -12,9 +12,9 @@
 Exactness: every vertex is the reference's float64 expression evaluated in the same order without contraction, so positions,
 key order and faces equal the reference's bit for bit (tests/test_mesh_*.py).  Two documented departures: a non-finite norm /
 udf value in a triangulated cell is refused (the reference's dict cannot merge NaN vertices in any meaningful way — ``nan != nan``,
-so every NaN vertex would become a vertex of its own), and ``field_to_mesh`` refuses any non-finite norm in the grid.  Trimesh's
-default vertex merging (``process=True`` in methods.py:305) is not reproduced: ``vertices`` / ``faces`` are the PLY file's
-content, before trimesh.
+so every NaN vertex would become a vertex of its own), and ``field_to_mesh`` refuses any non-finite norm in the grid.  By default
+``vertices`` / ``faces`` are the PLY file's content, before trimesh; ``extract_mesh(..., weld=True)`` merges the vertices the way
+trimesh's default (``process=True`` in methods.py:305) is remembered to — ``meshops.weld``, a specification not verified against trimesh.
 """
 from __future__ import annotations
 
@@ -22,7 +22,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from . import geomargs, grid, lib
+from . import geomargs, grid, lib, meshops
 
 N_COMBS = 28
 
@@ -149,11 +149,15 @@ class Mesh(NamedTuple):
 
 @torch.no_grad()
 def extract_mesh(decoder, resolution: int, scale: float = 1.0, translation=0, centroid=0, smooth_after: bool = False,
-                 smooth_all: bool = False, max_batch: int = 100000, device=None) -> Mesh:
+                 smooth_all: bool = False, max_batch: int = 100000, device=None, weld: bool = False) -> Mesh:
     """evaluation/methods.py:140-322 (``marching_cubes_mesh``) without files: lattice -> queries -> ``field_to_mesh``.  The lattice is
     regenerated on the device from its axis tables (no res^3 host grid), the queries stay device-resident.  ``vertices_scaled`` is
     what the PLY's f4 vertices become after ``apply_scale`` / ``apply_translation(translation)`` / ``apply_translation(centroid)``
-    (:314-316); trimesh's vertex merging is not reproduced."""
+    (:314-316).  ``weld=True``: ``vertices``, ``faces`` and ``vertices_scaled`` are those of ``meshops.weld`` (``digits=8``) applied to
+    float64(float32(vertices)) before scaling — where the reference's ``trimesh.Trimesh(...)`` merges: after the PLY's f4 rounding and
+    before ``apply_scale``.  The default changes nothing."""
+    if not isinstance(weld, bool):
+        raise ValueError(f"weld must be a bool, got {weld!r}")
     res = geomargs.positive_int(resolution, "resolution")
     _check_even(res)
     if res < 2:
@@ -172,5 +176,7 @@ def extract_mesh(decoder, resolution: int, scale: float = 1.0, translation=0, ce
     vertices, faces = field_to_mesh(pred, res, smooth_after=smooth_after, smooth_all=smooth_all)
     t = torch.as_tensor(translation).to(dev, torch.float64).expand(3)
     c = torch.as_tensor(centroid).to(dev, torch.float64).expand(3)
+    if weld:
+        vertices, faces, _ = meshops.weld((vertices.to(torch.float32).to(torch.float64), faces), digits=meshops.WELD_DIGITS, device=dev)
     scaled = vertices.to(torch.float32).to(torch.float64) * float(scale) + t + c
     return Mesh(vertices, faces, scaled)

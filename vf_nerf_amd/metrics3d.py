@@ -15,6 +15,10 @@ threshold — without copying either mesh to the host.
 * ``chamfer_from_points`` / ``chamfer_distance`` — the reference's four numbers with the reference's combination.
 * ``precision_recall_fscore`` — shares of points within a threshold of the other set.
 * ``score_mesh`` — both from one sampling and one search per direction, shaped like an entry of the reference's ``3d-metrics.json``.
+* ``normal_consistency`` — the mean |n(p) . n(nearest point of the other surface)| in both directions, the third number beside chamfer
+  distance and F-score: a sample's normal is the unit normal of the face it was drawn from (``meshops.face_normals``), the neighbour
+  comes with its index from the grid search, the dots from csrc/vfn_normals.hip, the sums along the fixed tree.
+  ``score_mesh(..., normals=True)`` adds it to the entry as "normal consistency" from the same samples and searches.
 
 Inputs are numpy arrays or torch tensors on any device; a mesh is a ``mesh.Mesh`` (its ``vertices_scaled`` are used) or a
 ``(vertices, faces)`` pair.  No CPU fallback: ``lib.VfnError`` when no device is visible.
@@ -27,7 +31,8 @@ dictionary come from ``vf_nerf_amd.refuse`` (``reconstruction_meshes``, ``metric
 a specification of ours: not verified against Open3D or the ``evaluate_3d_reconstruction`` package).
 
 Out of scope: the voxel down-sampling of
-the ``evaluate_3d_reconstruction`` package, trimesh's vertex merging, and PLY reading / writing.  The random numbers are torch's, not
+the ``evaluate_3d_reconstruction`` package.  Trimesh's vertex merging is ``meshops.weld``, PLY reading / writing ``vf_nerf_amd.ply``.
+The random numbers are torch's, not
 numpy's: a sampled point set is distributed as trimesh's, it is not the same set.
 """
 from __future__ import annotations
@@ -39,7 +44,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import geomargs, icp, lib
+from . import geomargs, icp, lib, meshops
 from .geomargs import LIMIT
 
 SEARCHES = ("all_pairs", "grid")
@@ -261,6 +266,58 @@ def _both_directions(pred_points, ref_points, threshold: float, device=None, sea
     return host[:14].reshape(2, 7)
 
 
+def _normal_direction(q: torch.Tensor, qn: torch.Tensor, t: torch.Tensor, tn: torch.Tensor, threshold: float, info: torch.Tensor,
+                      ninfo: torch.Tensor) -> torch.Tensor:
+    """One direction WITH normals -> device [8]: ``_direction``'s seven numbers from the grid search's distances (the all-pairs kernel's
+    to the bit), then the sum of |qn . tn[nearest]| along the fixed tree."""
+    with torch.cuda.device(q.device):
+        grid = _grid(t, None)
+        index, sq, _ = lib.nn_nearest(q, grid.nearest_args(), MAX_RINGS, order=icp.query_order(q, None, grid), info=info)
+    dots = lib.normal_dots(qn, tn, index, info=ninfo)
+    return torch.cat((_direction(torch.sqrt(sq), threshold), lib.reduce_stats(dots, math.inf)[:1]))
+
+
+def _both_directions_normals(p: torch.Tensor, pn: torch.Tensor, r: torch.Tensor, rn: torch.Tensor, threshold: float):
+    """Device points and unit normals of both sample sets -> (host [2,7] as ``_both_directions``, the "normal consistency" entry).  Both
+    searches go through the grid kernel: the all-pairs kernel has no index.  One read of the results, the two sums of dots with it."""
+    dev = p.device
+    info = torch.zeros(1, dtype=torch.int64, device=dev)
+    ninfo = torch.zeros(1, dtype=torch.int64, device=dev)
+    one = _normal_direction(r, rn, p, pn, threshold, info, ninfo)
+    two = _normal_direction(p, pn, r, rn, threshold, info, ninfo)
+    host = torch.cat((one, two, info.to(torch.float64), ninfo.to(torch.float64))).cpu().numpy()
+    lib.nn_check(int(host[16]))
+    lib.normals_check(int(host[17]), "normal consistency")
+    a, b = float(host[15] / p.shape[0]), float(host[7] / r.shape[0])
+    return np.stack((host[0:7], host[8:15])), {"pred_to_ref": a, "ref_to_pred": b, "mean": (a + b) / 2.0}
+
+
+def _sample_normals(vertices, faces, face_index: torch.Tensor) -> torch.Tensor:
+    """The unit normal of the face every sample was drawn from (a torch gather), on the samples' device."""
+    return meshops.face_normals((vertices, faces), normalise=True, device=face_index.device)[face_index].contiguous()
+
+
+def _rotate(normals: torch.Tensor, transformation: np.ndarray) -> torch.Tensor:
+    """Normals under the 3 x 3 block of a [4,4] rigid transformation: ``icp.transform_points``'s kernel with the translation zero."""
+    rotation = np.array(transformation, dtype=np.float64, copy=True)
+    rotation[:3, 3] = 0.0
+    return icp.transform_points(normals, rotation, device=normals.device)
+
+
+def normal_consistency(pred_mesh, ref_mesh, num_points: int = 1000000, generator: Optional[torch.Generator] = None, uniforms=None,
+                       device=None) -> dict:
+    """{"pred_to_ref", "ref_to_pred", "mean"}: ``num_points`` samples of each surface (pred first, then ref, from the same generator, or
+    the same ``uniforms`` for both), every sample with the unit normal of its face; per direction the mean of |n(p) . n(q)| over the
+    samples p of one surface with q the nearest sample of the other (ties to the lowest index), and the mean of the two means.  The
+    absolute value because neither mesh's winding is trusted.  Sums along the fixed tree (``lib.reduce_stats``), divided on the host."""
+    pv, pf = _check_mesh(pred_mesh, "pred_mesh")
+    rv, rf = _check_mesh(ref_mesh, "ref_mesh")
+    num_points = geomargs.positive_int(num_points, "num_points")
+    pred_points, pred_face = sample_surface(pv, pf, num_points, generator=generator, uniforms=uniforms, device=device)
+    ref_points, ref_face = sample_surface(rv, rf, num_points, generator=generator, uniforms=uniforms, device=device)
+    return _both_directions_normals(pred_points, _sample_normals(pv, pf, pred_face), ref_points, _sample_normals(rv, rf, ref_face), 0.0)[1]
+
+
 def chamfer_from_points(pred_points, ref_points, device=None, search: str = "all_pairs") -> Tuple[float, float, float, float]:
     """utils.py:350-367 on two point sets -> (mean, median, min, max) as Python floats: per direction the mean / median / min / max of
     the squared nearest distances, then the sum of the means, the sum of the medians, the min of the mins, the max of the maxes.  The
@@ -294,7 +351,8 @@ def precision_recall_fscore(pred_points, ref_points, threshold: float, device=No
 
 
 def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: float = 0.05, generator: Optional[torch.Generator] = None,
-               uniforms=None, device=None, icp_align: bool = False, icp_threshold: Optional[float] = None, search: str = "all_pairs") -> dict:
+               uniforms=None, device=None, icp_align: bool = False, icp_threshold: Optional[float] = None, search: str = "all_pairs",
+               normals: bool = False) -> dict:
     """One entry of the reference's ``3d-metrics.json`` (methods.py:794-801): {"chamfer distance": {mean, median, min, max}, "precision",
     "recall", "fscore"} (plus the two counts), from ONE sampling of each mesh and ONE nearest-neighbour search per direction shared
     by both metrics.  ``uniforms`` ([num_points,3]) is used for BOTH meshes when given.
@@ -304,8 +362,15 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
     entry gains "icp": {"transformation" (nested lists), "fitness", "inlier_rmse", "iterations"}.  With ``icp_align=False`` nothing
     changes: the same keys, values and draws from the generator as without the keyword.
 
-    ``search="grid"``: the two scoring searches go through the grid kernel (``nearest``); the dictionary is the same to the bit."""
+    ``search="grid"``: the two scoring searches go through the grid kernel (``nearest``); the dictionary is the same to the bit.
+
+    ``normals=True``: the entry gains "normal consistency": {"pred_to_ref", "ref_to_pred", "mean"} (``normal_consistency``, from the same
+    samples; with ``icp_align`` the pred normals are rotated by the result's 3 x 3 block).  The two scoring searches then go through the
+    grid kernel whatever ``search`` says — the all-pairs kernel has no index — and every other key is what it is without ``normals``,
+    bit for bit.  With ``normals=False`` nothing changes."""
     search = _check_search(search)
+    if not isinstance(normals, (bool, np.bool_)):
+        raise ValueError(f"normals must be a bool, got {normals!r}")
     pv, pf = _check_mesh(pred_mesh, "pred_mesh")
     rv, rf = _check_mesh(ref_mesh, "ref_mesh")
     num_points = geomargs.positive_int(num_points, "num_points")
@@ -314,16 +379,25 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
         raise ValueError(f"icp_align must be a bool, got {icp_align!r}")
     if icp_align:
         icp_radius = icp._check_radius(threshold if icp_threshold is None else icp_threshold, "icp_threshold")
-    pred_points, _ = sample_surface(pv, pf, num_points, generator=generator, uniforms=uniforms, device=device)
-    ref_points, _ = sample_surface(rv, rf, num_points, generator=generator, uniforms=uniforms, device=device)
+    pred_points, pred_face = sample_surface(pv, pf, num_points, generator=generator, uniforms=uniforms, device=device)
+    ref_points, ref_face = sample_surface(rv, rf, num_points, generator=generator, uniforms=uniforms, device=device)
+    if normals:
+        pred_normals, ref_normals = _sample_normals(pv, pf, pred_face), _sample_normals(rv, rf, ref_face)
     aligned = None
     if icp_align:
         aligned = icp.align(pred_points, ref_points, icp_radius, device=pred_points.device)
         pred_points = icp.transform_points(pred_points, aligned.transformation, device=pred_points.device)
-    rows = _both_directions(pred_points, ref_points, threshold, device, **_search_kw(search))
+        if normals:
+            pred_normals = _rotate(pred_normals, aligned.transformation)
+    if normals:
+        rows, consistency = _both_directions_normals(pred_points, pred_normals, ref_points, ref_normals, threshold)
+    else:
+        rows = _both_directions(pred_points, ref_points, threshold, device, **_search_kw(search))
     mean, median, mn, mx = _chamfer(rows[0], rows[1])
     out = {"chamfer distance": {"mean": mean, "median": median, "min": mn, "max": mx}}
     out.update(_prf(rows[1], rows[0]))
+    if normals:
+        out["normal consistency"] = consistency
     if aligned is not None:
         out["icp"] = {"transformation": aligned.transformation.tolist(), "fitness": aligned.fitness, "inlier_rmse": aligned.inlier_rmse,
                       "iterations": aligned.iterations}

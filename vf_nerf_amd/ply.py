@@ -2,15 +2,17 @@
 ``tsdf-mesh/tsdf.ply`` (evaluation/methods.py:665) — vertices ``x y z`` (``float``, or ``double``), optionally ``red green blue`` as
 ``uchar``, faces as ``property list uchar int vertex_indices`` — ASCII or ``binary_little_endian``.
 
-* ``write_ply(path, vertices, faces, colours=None, *, binary=True, vertex_dtype="f4")`` — colours in [0, 1] are written as
-  ``rint(c 255)`` clipped to [0, 255] (for ``c = b / 255`` that is b again); uint8 colours are written as they are.
-* ``read_ply(path)`` -> ``(vertices float64 [n,3], faces int64 [m,3], colours uint8 [n,3] | None)`` for those layouts.  Extra vertex
-  properties (``nx ny nz``, ``alpha``, ...) are skipped, ``uint`` / ``int`` indices and the name ``vertex_index`` are accepted: enough to
+* ``write_ply(path, vertices, faces, colours=None, *, binary=True, vertex_dtype="f4", normals=None)`` — colours in [0, 1] are written
+  as ``rint(c 255)`` clipped to [0, 255] (for ``c = b / 255`` that is b again); uint8 colours are written as they are.  ``normals``
+  ([n,3] floating point) are written as ``nx ny nz`` in the vertex type, after ``x y z`` and before the colours — Open3D's order.
+* ``read_ply(path)`` -> ``(vertices float64 [n,3], faces int64 [m,3], colours uint8 [n,3] | None)`` for those layouts;
+  ``read_ply(path, normals=True)`` returns a fourth value, the normals as float64 [n,3], or None when the file has no ``nx ny nz``.
+  Other vertex properties (``alpha``, ...) are skipped, ``uint`` / ``int`` indices and the name ``vertex_index`` are accepted: enough to
   load a ground-truth ``*_mesh.ply`` into ``refuse.metrics_3d``.  Anything else is refused by name: big-endian files, faces that are
   not triangles, elements other than ``vertex`` and ``face`` in front of them, list properties on vertices.
 
-Vertex normals are NOT written (the reference calls ``compute_vertex_normals()`` before it writes): out of scope.  Device tensors are
-accepted and downloaded."""
+The reference calls ``compute_vertex_normals()`` before it writes: ``meshops.vertex_normals`` computes them, ``normals=`` writes them.
+Device tensors are accepted and downloaded."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -45,8 +47,9 @@ def colour_bytes(colours) -> np.ndarray:
     return np.clip(np.rint(c.astype(np.float64) * 255.0), 0.0, 255.0).astype(np.uint8)
 
 
-def write_ply(path, vertices, faces, colours=None, *, binary: bool = True, vertex_dtype: str = "f4") -> None:
-    """Write the mesh (vertices [n,3] floating point, faces [m,3] integers, 0-based, optional colours [n,3]) to ``path``."""
+def write_ply(path, vertices, faces, colours=None, *, binary: bool = True, vertex_dtype: str = "f4", normals=None) -> None:
+    """Write the mesh (vertices [n,3] floating point, faces [m,3] integers, 0-based, optional colours [n,3], optional normals [n,3]
+    floating point) to ``path``.  Without ``normals`` the file has no ``nx ny nz`` properties."""
     if vertex_dtype not in ("f4", "f8"):
         raise ValueError(f"vertex_dtype must be 'f4' or 'f8', got {vertex_dtype!r}")
     v, f = _host(vertices), _host(faces)
@@ -61,19 +64,32 @@ def write_ply(path, vertices, faces, colours=None, *, binary: bool = True, verte
     c = None if colours is None else colour_bytes(colours)
     if c is not None and c.shape[0] != v.shape[0]:
         raise ValueError(f"{c.shape[0]} colours for {v.shape[0]} vertices")
+    nrm = None
+    if normals is not None:
+        nrm = _host(normals)
+        if nrm.ndim != 2 or nrm.shape[1] != 3 or nrm.dtype.kind != "f":
+            raise ValueError(f"normals must be floating point [n,3], got {nrm.dtype} {nrm.shape}")
+        if nrm.shape[0] != v.shape[0]:
+            raise ValueError(f"{nrm.shape[0]} normals for {v.shape[0]} vertices")
+        nrm = nrm.astype("<" + vertex_dtype)
     v = v.astype("<" + vertex_dtype)
     f = f.astype("<i4")
     header = ["ply", f"format {'binary_little_endian' if binary else 'ascii'} 1.0", f"element vertex {v.shape[0]}"]
     header += [f"property {'float' if vertex_dtype == 'f4' else 'double'} {a}" for a in "xyz"]
+    if nrm is not None:
+        header += [f"property {'float' if vertex_dtype == 'f4' else 'double'} {a}" for a in ("nx", "ny", "nz")]
     if c is not None:
         header += [f"property uchar {a}" for a in ("red", "green", "blue")]
     header += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
     with open(path, "wb") as fh:
         fh.write(("\n".join(header) + "\n").encode("ascii"))
         if binary:
-            fields = [("p", "<" + vertex_dtype, (3,))] + ([("c", "u1", (3,))] if c is not None else [])
+            fields = ([("p", "<" + vertex_dtype, (3,))] + ([("n", "<" + vertex_dtype, (3,))] if nrm is not None else [])
+                      + ([("c", "u1", (3,))] if c is not None else []))
             rec = np.empty(v.shape[0], dtype=np.dtype(fields))            # (packed: no padding between the fields)
             rec["p"] = v
+            if nrm is not None:
+                rec["n"] = nrm
             if c is not None:
                 rec["c"] = c
             fh.write(rec.tobytes())
@@ -85,6 +101,8 @@ def write_ply(path, vertices, faces, colours=None, *, binary: bool = True, verte
             lines = []
             for i in range(v.shape[0]):                                   # str of a NumPy scalar: the shortest text that reads back to its bits
                 row = [str(x) for x in v[i]]
+                if nrm is not None:
+                    row += [str(x) for x in nrm[i]]
                 if c is not None:
                     row += [str(int(b)) for b in c[i]]
                 lines.append(" ".join(row))
@@ -132,8 +150,9 @@ def _parse_header(fh):
     return fmt, elements
 
 
-def read_ply(path) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
-    """-> (vertices float64 [n,3], faces int64 [m,3], colours uint8 [n,3] or None)."""
+def read_ply(path, normals: bool = False):
+    """-> (vertices float64 [n,3], faces int64 [m,3], colours uint8 [n,3] or None); with ``normals=True`` a fourth value: the ``nx ny nz``
+    of the vertices as float64 [n,3], or None when the file has none."""
     with open(path, "rb") as fh:
         fmt, elements = _parse_header(fh)
         names = [e[0] for e in elements]
@@ -146,6 +165,9 @@ def read_ply(path) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
         if len(set(pnames)) != len(pnames) or not all(a in pnames for a in "xyz"):
             raise PlyError(f"the vertex element needs distinct properties with x, y and z, got {pnames}")
         has_colour = all(a in pnames for a in ("red", "green", "blue"))
+        has_normals = all(a in pnames for a in ("nx", "ny", "nz"))
+        if has_normals and any(t not in ("f4", "f8") for p, t in vprops if p in ("nx", "ny", "nz")):
+            raise PlyError("vertex normals must be float or double")
         if has_colour and any(t != "u1" for p, t in vprops if p in ("red", "green", "blue")):
             raise PlyError("vertex colours must be uchar")
         m, fprops = (elements[1][1], elements[1][2]) if len(elements) > 1 else (0, [])
@@ -189,4 +211,9 @@ def read_ply(path) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
         colours = np.stack([cols[a].astype(np.uint8) for a in ("red", "green", "blue")], axis=1) if n else np.zeros((0, 3), dtype=np.uint8)
     if faces.size and (faces.min() < 0 or faces.max() >= n):
         raise PlyError(f"a face index lies outside [0, {n})")
-    return vertices, faces.reshape(-1, 3), colours
+    if not normals:
+        return vertices, faces.reshape(-1, 3), colours
+    vertex_normals = None
+    if has_normals:
+        vertex_normals = np.stack([cols[a].astype(np.float64) for a in ("nx", "ny", "nz")], axis=1) if n else np.zeros((0, 3), dtype=np.float64)
+    return vertices, faces.reshape(-1, 3), colours, vertex_normals

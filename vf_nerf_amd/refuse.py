@@ -18,7 +18,9 @@ specification of ours, not verified against Open3D).
 
 ``refuse_rgbd`` is ``refuse`` with the views' images fused along with the depth, as the reference's ``refuse()`` does (nothing it reports
 depends on the colour; the mesh it returns is coloured) -> (vertices, faces, vertex colours); ``vf_nerf_amd.ply`` reads and writes PLY
-files.  Out of scope: vertex normals in the PLY, trimesh's vertex merging.
+files (with vertex normals, if given: ``meshops.vertex_normals``); trimesh's vertex merging is ``meshops.weld``.
+
+``metrics_3d(..., normals=True)`` adds "normal consistency" to every entry (``metrics3d.normal_consistency``).
 """
 from __future__ import annotations
 
@@ -118,15 +120,16 @@ def reconstruction_meshes(tsdf_mesh, intrinsics, poses, height: int, width: int,
 
 def metrics_3d(tsdf_mesh, gt_mesh, intrinsics, poses, height: int, width: int, num_points: int = 1000000, distance_thresh: float = 0.01,
                generator: Optional[torch.Generator] = None, uniforms=None, iterations: int = ITERATIONS, lam: float = LAM,
-               icp_align: bool = False, icp_threshold: Optional[float] = None, search: str = "all_pairs", **refuse_args) -> Dict[str, dict]:
+               icp_align: bool = False, icp_threshold: Optional[float] = None, search: str = "all_pairs", normals: bool = False, **refuse_args) -> Dict[str, dict]:
     """The dictionary the reference writes to ``3d-metrics.json`` (methods.py:732-741): keys ``tsdf``, ``refused_tsdf``,
     ``tsdf_smoothed``, ``refused_tsdf_smoothed``, each ``metrics3d.score_mesh(mesh, gt_mesh)`` — {"chamfer distance": {mean, median,
     min, max}, "precision", "recall", "fscore", ...} — scored in that order with the one ``generator`` (or the same ``uniforms``).  ``icp_align`` / ``icp_threshold`` go to
     ``metrics3d.score_mesh`` (every entry then has an "icp" key), and so does ``search`` ("all_pairs" or "grid": the eight searches
-    through the grid kernel, the same dictionary to the bit)."""
+    through the grid kernel, the same dictionary to the bit) and ``normals`` (True: every entry gains "normal consistency")."""
     search = metrics3d._check_search(search)
     meshes = reconstruction_meshes(tsdf_mesh, intrinsics, poses, height, width, iterations=iterations, lam=lam, **refuse_args)
     dev = meshes["tsdf"][0].device
     return {name: metrics3d.score_mesh(meshes[name], gt_mesh, num_points=num_points, distance_thresh=distance_thresh, generator=generator,
-                                       uniforms=uniforms, device=dev, icp_align=icp_align, icp_threshold=icp_threshold, search=search)
+                                       uniforms=uniforms, device=dev, icp_align=icp_align, icp_threshold=icp_threshold, search=search,
+                                       **({"normals": True} if normals else {}))
             for name in MESH_NAMES}

@@ -27,8 +27,8 @@ and its bits; the geometry of a coloured volume is bit-equal to the colourless o
 is visible.
 
 ``refuse()`` and Laplacian smoothing (``tsdf-smoothed.ply``) are ``vf_nerf_amd.refuse``: a mesh's depth rasterised on the device
-(``vf_nerf_amd.raster``) and re-fused by this volume.  PLY reading / writing is ``vf_nerf_amd.ply``.  Out of scope: vertex normals in
-the PLY (the reference calls ``compute_vertex_normals()`` before writing), the hashed volume.
+(``vf_nerf_amd.raster``) and re-fused by this volume.  PLY reading / writing is ``vf_nerf_amd.ply``, the vertex
+normals the reference computes before writing (``compute_vertex_normals()``) are ``meshops.vertex_normals``.  Out of scope: the hashed volume.
 """
 from __future__ import annotations
 
