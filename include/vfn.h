@@ -903,7 +903,8 @@ int vfn_image_abs_err(const float* a, const float* b, int64_t V, int64_t H, int6
  * maps and the mesh that metrics_3d scores, with the semantics of a uniform TSDF volume — projective integration with a running mean,
  * classic marching cubes on the zero level set.  Two deliberate differences: the volume is DENSE over a box the caller gives (not
  * hashed 16^3 blocks opened near back-projected points, so a voxel in free space in front of a surface collects tsdf = 1 observations
- * that a hashed volume would never have allocated; the zero crossing lies inside the truncation band either way), and colour is
+ * that a hashed volume would never have allocated; the zero crossing lies inside the truncation band either way — the block-sparse
+ * volume of the next section opens blocks of 8^3 voxels of this same lattice near the points), and colour is
  * optional: a volume without one keeps its entry points and its bits, a volume with one adds colour[nx, ny, nz, 3] (below).
  * Volume: tsdf[nx, ny, nz] and weight[nx, ny, nz], float32, C order (k fastest), zero-filled by the caller before the first view;
  * voxel (i, j, k) has its centre at origin + (index + 0.5) voxel_length.  nx ny nz < 2^31, voxel_length > 0, sdf_trunc > 0.
@@ -970,6 +971,63 @@ int vfn_tsdf_emit_colours(const float* tsdf, const float* weight, const float* c
                           const int32_t* counts, const int32_t* offsets, double* tri_cols, void* stream);
 int vfn_tsdf_vertex_colours(const int64_t* ids, int64_t n_slots, const double* tri_cols, int32_t* first, int64_t n_vertices,
                             double* colours, void* stream);
+
+/* =============================================================================================
+ * A block-sparse TSDF volume (csrc/vfn_tsdf.hip, after the dense entry points): the SAME voxel lattice as above — origin, dims = (nx, ny,
+ * nz), voxel_length as float32, voxel (i, j, k) centred at origin + ((float)index + 0.5f) vl with the GLOBAL index — held as blocks of
+ * 8^3 voxels that exist only near the back-projected depth points.  Every voxel it holds carries the bits of the dense volume over the
+ * same lattice; dims are not bound by 2^31 voxels.  Limits: each dim <= 2^24; the block lattice nb = ceil(dims / 8) has nbx nby nbz <
+ * 2^31; n_blocks 512 < 2^31.
+ * Storage: block_of[nbx, nby, nbz] int32 (-1: absent), block_coords[n_blocks, 3] int32, tsdf / weight [n_blocks, 8, 8, 8] float32 and
+ * colour [n_blocks, 8, 8, 8, 3] float32 (byte units), C order, 16-B aligned, zero-filled when a block is opened.  Block ids are given by
+ * the caller (vf_nerf_amd/tsdf.py: in order of allocation call, inside a call in ascending C order of the block lattice, from
+ * torch.nonzero of the marks — no atomics decide a number) and never change.
+ *   vfn_tsdf_sparse_mark  one lane per pixel of depth[V, H, W]; cameras[V, 17] (double) = C[12], fx, fy, cx, cy, q with C the first three
+ *                     rows of the float64 inverse of the 4x4 whose first three rows are the float32 extrinsic rows promoted (the matrix
+ *                     the integration uses), fx fy cx cy the float32 intrinsics promoted and q = sqrt(1 / (fx fx) + 1 / (fy fy)).  With
+ *                     o, vl, tr the float32 origin, voxel_length and sdf_trunc promoted, all in float64, every operation rounded once in
+ *                     the association written, no contraction:
+ *                       d = (double)depth[v, u];  skip unless d > 0
+ *                       a = ((double)u - cx) / fx;  b = ((double)v - cy) / fy
+ *                       P[c] = ((C[c][0] (a d) + C[c][1] (b d)) + C[c][2] d) + C[c][3]
+ *                       r = (tr + (0.5 (d + tr)) q) + 2.0 vl
+ *                       lo[c] = floor(((P[c] - r) - o[c]) / (8.0 vl));  hi[c] = floor(((P[c] + r) - o[c]) / (8.0 vl))
+ *                       skip unless hi[c] >= 0 and lo[c] <= nb[c] - 1 on every axis (a NaN skips);  clamp both to [0, nb[c] - 1]
+ *                       marks[bi, bj, bk] = 1 for lo <= (bi, bj, bk) <= hi
+ *                     marks[nbx, nby, nbz] (uint8) is zeroed by the caller; the store is a plain byte store of the constant 1 (lanes that
+ *                     race store the same value; a lane may read the byte and skip the store).  Why this radius: DESIGN 6p.
+ *   vfn_tsdf_sparse_integrate / _rgb  all V views into EVERY block of block_coords, one workgroup of 128 lanes per block, a lane owning 4
+ *                     consecutive k voxels.  Per voxel and view the arithmetic is vfn_tsdf_integrate's (vfn_tsdf_integrate_rgb's) — the
+ *                     same device function — with x, y, z from the global index 8 block_coords + local; views in index order; a view is
+ *                     skipped for a block only by the dense kernel's exact brick test.  A voxel whose global index is >= dims is never
+ *                     updated and keeps weight == 0.  A block is read and written once per call, whatever V is.
+ *   vfn_tsdf_sparse_count / _emit / _emit_colours  the extraction of vfn_tsdf_count / _emit / _emit_colours over n_blocks 512 positions:
+ *                     position p is block p >> 9 and local cell ((p >> 6) & 7, (p >> 3) & 7, p & 7), the global cell g = 8 block_coords
+ *                     + local.  A cell with g[c] + 1 >= dims[c] on any axis counts 0; a corner comes from this block or from the
+ *                     neighbour block_of names, and an absent neighbour voids the cell like a corner with weight == 0.  Case, triangle
+ *                     order, vertex position (with the global lattice index) and colour are the dense formulas: a vertex has the dense
+ *                     mesh's bits, and vfn_mesh_dedup joins it across blocks.  counts / offsets: n_blocks 512 int32.
+ * ============================================================================================= */
+int vfn_tsdf_sparse_mark(uint8_t* marks, int32_t nbx, int32_t nby, int32_t nbz, float ox, float oy, float oz, float voxel_length,
+                         float sdf_trunc, const float* depth, int32_t height, int32_t width, const double* cameras, int32_t n_views,
+                         void* stream);
+int vfn_tsdf_sparse_integrate(float* tsdf, float* weight, const int32_t* block_coords, int32_t n_blocks, int32_t nx, int32_t ny,
+                              int32_t nz, float ox, float oy, float oz, float voxel_length, float sdf_trunc, const float* depth,
+                              int32_t height, int32_t width, const float* intrinsics, const float* extrinsics, int32_t n_views,
+                              void* stream);
+int vfn_tsdf_sparse_integrate_rgb(float* tsdf, float* weight, float* colour, const int32_t* block_coords, int32_t n_blocks, int32_t nx,
+                                  int32_t ny, int32_t nz, float ox, float oy, float oz, float voxel_length, float sdf_trunc,
+                                  const float* depth, const uint8_t* rgb, int32_t height, int32_t width, const float* intrinsics,
+                                  const float* extrinsics, int32_t n_views, void* stream);
+int vfn_tsdf_sparse_count(const float* tsdf, const float* weight, const int32_t* block_of, const int32_t* block_coords, int32_t n_blocks,
+                          int32_t nx, int32_t ny, int32_t nz, int32_t* counts, int32_t* offsets, int64_t* info, void* scan_ws,
+                          int64_t scan_ws_bytes, void* stream);
+int vfn_tsdf_sparse_emit(const float* tsdf, const float* weight, const int32_t* block_of, const int32_t* block_coords, int32_t n_blocks,
+                         int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz, float voxel_length, const int32_t* counts,
+                         const int32_t* offsets, double* tri_verts, void* stream);
+int vfn_tsdf_sparse_emit_colours(const float* tsdf, const float* weight, const float* colour, const int32_t* block_of,
+                                 const int32_t* block_coords, int32_t n_blocks, int32_t nx, int32_t ny, int32_t nz,
+                                 const int32_t* counts, const int32_t* offsets, double* tri_cols, void* stream);
 
 /* =============================================================================================
  * Rasterising a mesh's depth, and Laplacian smoothing (csrc/vfn_raster.hip): what evaluation/methods.py:33-72 (refuse: the mesh's depth

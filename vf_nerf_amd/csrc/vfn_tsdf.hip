@@ -435,3 +435,329 @@ extern "C" int vfn_tsdf_vertex_colours(const int64_t* ids, int64_t n_slots, cons
                        (const int*)first, (long long)n_vertices, colours);
     return vfn_check_launch("vfn_tsdf_vertex_colours");
 }
+
+// ---- the block-sparse volume (include/vfn.h: "A block-sparse TSDF volume") ------------------------------------------------
+// Blocks of BLOCK^3 voxels of the SAME lattice, opened near the back-projected depth points and stored one after another:
+//   mark       one lane per pixel of every view, float64: the blocks its point's ball touches get a byte 1 (a plain store of a constant;
+//              lanes that race store the same value).  Numbering the new blocks is torch plumbing on the marks.
+//   integrate  one workgroup of 128 lanes per block, a lane owns RUN consecutive k voxels (always 16-B aligned inside a block: only the
+//              vector form).  x, y, z come from the GLOBAL index through centre(), the views are tested with brick_may_see at the block's
+//              extreme in-lattice centres and applied by integrate_view<COLOUR> — the dense kernel's own code, so a voxel holds the dense
+//              volume's bits.  Voxels of an edge block beyond dims are never updated.
+//   count/emit a third source of vfn_mc_extract.h: position p is block p >> 9, local cell (p >> 6) & 7, (p >> 3) & 7, p & 7; corners
+//              come from this block or from the neighbour block_of names; an absent neighbour voids the cell.  vertex() is Lattice's with
+//              the global index: the dense mesh's position bits.
+namespace {
+
+constexpr int BLOCK = 8, BLOCK_VOXELS = BLOCK * BLOCK * BLOCK;
+constexpr int SP_THREADS = BLOCK_VOXELS / RUN;            // 128 lanes: two waves
+static_assert(SP_THREADS == 128 && BLOCK % RUN == 0, "a lane's run stays inside one row of a block");
+
+struct MarkArgs {
+    const float* depth;        // [V, H, W]
+    const double* cam;         // [V, 17]: C[12] (camera -> world rows), fx fy cx cy, q
+    unsigned char* marks;      // [nbx, nby, nbz]
+    int n, h, w;
+    int nb[3];
+    double o[3], vl, tr;
+};
+
+__global__ __launch_bounds__(256) void vfn_tsdf_sparse_mark_kernel(MarkArgs a) {
+    const long long pixels = (long long)a.h * a.w;
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= pixels * a.n) return;
+    const int view = (int)(p / pixels);
+    const long long pix = p - (long long)view * pixels;
+    const int v = (int)(pix / a.w), u = (int)(pix - (long long)v * a.w);
+    const double d = (double)a.depth[p];
+    if (!(d > 0.0)) return;
+    const double* __restrict__ c = a.cam + (long long)view * 17;
+    const double fx = c[12], fy = c[13], cx = c[14], cy = c[15], q = c[16];
+    const double ca = ((double)u - cx) / fx, cb = ((double)v - cy) / fy;
+    const double ad = ca * d, bd = cb * d;
+    const double r = (a.tr + (0.5 * (d + a.tr)) * q) + 2.0 * a.vl;
+    const double edge = 8.0 * a.vl;
+    int lo[3], hi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double P = ((c[4 * k] * ad + c[4 * k + 1] * bd) + c[4 * k + 2] * d) + c[4 * k + 3];
+        double l = floor(((P - r) - a.o[k]) / edge), h = floor(((P + r) - a.o[k]) / edge);
+        const double last = (double)(a.nb[k] - 1);
+        if (!(h >= 0.0) || !(l <= last)) return;              // outside the block lattice, or NaN
+        l = l < 0.0 ? 0.0 : l;
+        h = h > last ? last : h;
+        lo[k] = (int)l;
+        hi[k] = (int)h;
+    }
+    for (int bi = lo[0]; bi <= hi[0]; ++bi)
+        for (int bj = lo[1]; bj <= hi[1]; ++bj) {
+            unsigned char* __restrict__ row = a.marks + ((long long)bi * a.nb[1] + bj) * a.nb[2];
+            for (int bk = lo[2]; bk <= hi[2]; ++bk)
+                if (row[bk] == 0) row[bk] = 1;
+        }
+}
+
+struct SparseVolume {
+    float* tsdf;               // [n_blocks, 8, 8, 8]
+    float* weight;
+    const int* coords;         // [n_blocks, 3]
+    int nx, ny, nz;
+    float ox, oy, oz, vl, trunc;
+};
+
+template <bool COLOUR>
+__global__ __launch_bounds__(SP_THREADS) void vfn_tsdf_sparse_integrate_kernel(SparseVolume vol, Views vs, Colour<COLOUR> cl) {
+    __shared__ unsigned long long seen[SP_THREADS / 64];
+    const long long blk = blockIdx.x;
+    const int t = threadIdx.x;
+    const int b0 = vol.coords[blk * 3] * BLOCK, b1 = vol.coords[blk * 3 + 1] * BLOCK, b2 = vol.coords[blk * 3 + 2] * BLOCK;
+    const int i = b0 + (t >> 4), j = b1 + ((t >> 1) & 7), k0 = b2 + (t & 1) * RUN;
+    const int cnt = (i < vol.nx && j < vol.ny) ? max(0, min(RUN, vol.nz - k0)) : 0;      // voxels beyond dims are never updated
+    const long long off = blk * BLOCK_VOXELS + (long long)t * RUN;
+
+    float ts[RUN], wt[RUN], z[RUN];
+    float col[COLOUR ? RUN : 1][3] = {};
+    {
+        const float4 a = *reinterpret_cast<const float4*>(vol.tsdf + off), c = *reinterpret_cast<const float4*>(vol.weight + off);
+        ts[0] = a.x; ts[1] = a.y; ts[2] = a.z; ts[3] = a.w;
+        wt[0] = c.x; wt[1] = c.y; wt[2] = c.z; wt[3] = c.w;
+    }
+    if constexpr (COLOUR) {
+        const float4* __restrict__ q = reinterpret_cast<const float4*>(cl.colour + off * 3);
+        const float4 a = q[0], b4 = q[1], c = q[2];
+        col[0][0] = a.x; col[0][1] = a.y; col[0][2] = a.z; col[1][0] = a.w;
+        col[1][1] = b4.x; col[1][2] = b4.y; col[2][0] = b4.z; col[2][1] = b4.w;
+        col[2][2] = c.x; col[3][0] = c.y; col[3][1] = c.z; col[3][2] = c.w;
+    }
+    const float x = centre(vol.ox, i, vol.vl), y = centre(vol.oy, j, vol.vl);
+#pragma unroll
+    for (int r = 0; r < RUN; ++r) z[r] = centre(vol.oz, k0 + r, vol.vl);
+
+    // the block's extreme in-lattice voxel centres (a block of the block lattice holds at least one voxel of the lattice)
+    const float lo[3] = {centre(vol.ox, b0, vol.vl), centre(vol.oy, b1, vol.vl), centre(vol.oz, b2, vol.vl)};
+    const float hi[3] = {centre(vol.ox, min(b0 + BLOCK, vol.nx) - 1, vol.vl), centre(vol.oy, min(b1 + BLOCK, vol.ny) - 1, vol.vl),
+                         centre(vol.oz, min(b2 + BLOCK, vol.nz) - 1, vol.vl)};
+    const float wf = (float)vs.w, hf = (float)vs.h;
+
+    for (int base = 0; base < vs.n; base += SP_THREADS) {
+        const int mine = base + t;
+        const bool may = mine < vs.n && brick_may_see(vs.extr + (long long)mine * 12, vs.intr + (long long)mine * 4, lo, hi, wf, hf);
+        const unsigned long long ballot = __ballot(may);
+        if ((t & 63) == 0) seen[t >> 6] = ballot;
+        __syncthreads();
+        for (int g = 0; g < SP_THREADS / 64; ++g) {
+            const unsigned long long m64 = seen[g];
+            unsigned m_lo = __builtin_amdgcn_readfirstlane((unsigned)m64), m_hi = __builtin_amdgcn_readfirstlane((unsigned)(m64 >> 32));
+            while (m_lo) {                                    // ascending view order
+                const int bit = __builtin_ctz(m_lo);
+                m_lo &= m_lo - 1;
+                integrate_view<COLOUR>(vs, cl, base + g * 64 + bit, x, y, z, cnt, vol.trunc, ts, wt, col);
+            }
+            while (m_hi) {
+                const int bit = __builtin_ctz(m_hi);
+                m_hi &= m_hi - 1;
+                integrate_view<COLOUR>(vs, cl, base + g * 64 + 32 + bit, x, y, z, cnt, vol.trunc, ts, wt, col);
+            }
+        }
+        __syncthreads();
+    }
+
+    *reinterpret_cast<float4*>(vol.tsdf + off) = make_float4(ts[0], ts[1], ts[2], ts[3]);
+    *reinterpret_cast<float4*>(vol.weight + off) = make_float4(wt[0], wt[1], wt[2], wt[3]);
+    if constexpr (COLOUR) {
+        float4* __restrict__ q = reinterpret_cast<float4*>(cl.colour + off * 3);
+        q[0] = make_float4(col[0][0], col[0][1], col[0][2], col[1][0]);
+        q[1] = make_float4(col[1][1], col[1][2], col[2][0], col[2][1]);
+        q[2] = make_float4(col[2][2], col[3][0], col[3][1], col[3][2]);
+    }
+}
+
+// the sparse source of vfn_mc_extract.h; c[] is the GLOBAL cell index, so Lattice::vertex gives the dense mesh's bits
+struct SparseLattice {
+    using Value = float;
+    using Emit = Lattice::Emit;
+    Lattice at;               // origin / voxel length / dims of the lattice (its tsdf / weight are the block storage)
+    const int* block_of;      // [nbx, nby, nbz], -1 for absent
+    const int* coords;        // [n_blocks, 3]
+    int nby, nbz;
+    long long n_positions;    // n_blocks * 512
+
+    __host__ __device__ long long positions() const { return n_positions; }
+
+    // the storage index of lattice voxel g (inside dims), -1 when its block is absent; `home` / b: the block the cell belongs to
+    __device__ __forceinline__ long long voxel(const int g[3], const int home[3], long long b) const {
+        const int bb[3] = {g[0] >> 3, g[1] >> 3, g[2] >> 3};
+        long long id = b;
+        if (bb[0] != home[0] || bb[1] != home[1] || bb[2] != home[2]) id = block_of[((long long)bb[0] * nby + bb[1]) * nbz + bb[2]];
+        if (id < 0) return -1;
+        return id * BLOCK_VOXELS + (((g[0] & 7) * BLOCK + (g[1] & 7)) * BLOCK + (g[2] & 7));
+    }
+
+    __device__ __forceinline__ bool eval(long long p, int c[3], float v[8], int& top, unsigned&) const {
+        const long long b = p >> 9;
+        const int home[3] = {coords[b * 3], coords[b * 3 + 1], coords[b * 3 + 2]};
+        c[0] = home[0] * BLOCK + (int)((p >> 6) & 7);
+        c[1] = home[1] * BLOCK + (int)((p >> 3) & 7);
+        c[2] = home[2] * BLOCK + (int)(p & 7);
+        if (c[0] + 1 >= at.nx || c[1] + 1 >= at.ny || c[2] + 1 >= at.nz) return false;
+        int t = 0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int g[3] = {c[0] + INC[q][0], c[1] + INC[q][1], c[2] + INC[q][2]};
+            const long long idx = voxel(g, home, b);
+            if (idx < 0 || at.weight[idx] == 0.f) return false;   // an absent block voids the cell like an unobserved corner
+            v[q] = at.tsdf[idx];
+            t |= (v[q] < 0.f ? 1 : 0) << q;
+        }
+        top = t;
+        return t != 0 && t != 255;
+    }
+
+    __device__ __forceinline__ void emit_setup(const int[3], Emit&) const {}
+    __device__ __forceinline__ void vertex(const int c[3], const float v[8], const Emit& em, int e, double out[3]) const { at.vertex(c, v, em, e, out); }
+};
+
+struct SparseLatticeColours {
+    using Value = float;
+    using Emit = Lattice::Emit;
+    SparseLattice sp;
+    const float* colour;      // [n_blocks, 8, 8, 8, 3]
+
+    __host__ __device__ long long positions() const { return sp.positions(); }
+    __device__ __forceinline__ bool eval(long long p, int c[3], float v[8], int& top, unsigned& status) const { return sp.eval(p, c, v, top, status); }
+    __device__ __forceinline__ void emit_setup(const int[3], Emit&) const {}
+
+    __device__ __forceinline__ void vertex(const int c[3], const float v[8], const Emit&, int e, double out[3]) const {
+        int ql, qu, axis;
+        edge_ends(e, ql, qu, axis);
+        const int home[3] = {c[0] >> 3, c[1] >> 3, c[2] >> 3};
+        const long long b = sp.block_of[((long long)home[0] * sp.nby + home[1]) * sp.nbz + home[2]];
+        const int gl[3] = {c[0] + INC[ql][0], c[1] + INC[ql][1], c[2] + INC[ql][2]};
+        const int gu[3] = {c[0] + INC[qu][0], c[1] + INC[qu][1], c[2] + INC[qu][2]};
+        const long long il = sp.voxel(gl, home, b), iu = sp.voxel(gu, home, b);      // (both present: eval passed)
+        const double fl = fabs((double)v[ql]), fu = fabs((double)v[qu]);
+        const double r = fl / (fl + fu);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+            out[ch] = ((1.0 - r) * (double)colour[il * 3 + ch] + r * (double)colour[iu * 3 + ch]) / 255.0;
+    }
+};
+
+int check_sparse_dims(int32_t nx, int32_t ny, int32_t nz, int32_t n_blocks, float vl, const char* what) {
+    VFN_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1 && nx <= (1 << 24) && ny <= (1 << 24) && nz <= (1 << 24),
+                "%s: dims (%d, %d, %d) must lie in [1, 2^24]", what, nx, ny, nz);
+    const long long nbx = (nx + BLOCK - 1) / BLOCK, nby = (ny + BLOCK - 1) / BLOCK, nbz = (nz + BLOCK - 1) / BLOCK;
+    VFN_REQUIRE(nbx * nby < (1ll << 31) && nbx * nby * nbz < (1ll << 31), "%s: the block lattice of dims (%d, %d, %d) exceeds 2^31 blocks", what,
+                nx, ny, nz);
+    VFN_REQUIRE(n_blocks >= 0 && (long long)n_blocks * BLOCK_VOXELS < (1ll << 31) && n_blocks <= nbx * nby * nbz,
+                "%s: %d blocks are outside the limits", what, n_blocks);
+    VFN_REQUIRE(vl > 0.f && vl - vl == 0.f, "%s: voxel_length must be positive and finite", what);
+    return VFN_OK;
+}
+
+int make_sparse_lattice(SparseLattice& a, const float* tsdf, const float* weight, const int32_t* block_of, const int32_t* coords, int32_t n_blocks,
+                        int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz, float vl, const char* what) {
+    const int rc = check_sparse_dims(nx, ny, nz, n_blocks, vl, what);
+    if (rc != VFN_OK) return rc;
+    VFN_REQUIRE(n_blocks == 0 || (tsdf && weight && block_of && coords), "%s: NULL volume", what);
+    a.at = Lattice{tsdf, weight, nx, ny, nz, 0ll, ox, oy, oz, vl};
+    a.block_of = (const int*)block_of;
+    a.coords = (const int*)coords;
+    a.nby = (ny + BLOCK - 1) / BLOCK;
+    a.nbz = (nz + BLOCK - 1) / BLOCK;
+    a.n_positions = (long long)n_blocks * BLOCK_VOXELS;
+    return VFN_OK;
+}
+
+template <bool COLOUR>
+int sparse_integrate(const char* what, float* tsdf, float* weight, float* colour, const int32_t* coords, int32_t n_blocks, int32_t nx, int32_t ny,
+                     int32_t nz, float ox, float oy, float oz, float voxel_length, float sdf_trunc, const float* depth, const unsigned char* rgb,
+                     int32_t height, int32_t width, const float* intrinsics, const float* extrinsics, int32_t n_views, void* stream) {
+    const int rc = check_sparse_dims(nx, ny, nz, n_blocks, voxel_length, what);
+    if (rc != VFN_OK) return rc;
+    VFN_REQUIRE(sdf_trunc > 0.f && sdf_trunc - sdf_trunc == 0.f, "%s: sdf_trunc must be positive and finite", what);
+    VFN_REQUIRE(n_views >= 0 && height >= 1 && width >= 1 && (long long)height * width < (1ll << 31),
+                "%s: bad views (%d of %d x %d)", what, n_views, height, width);
+    if (n_views == 0 || n_blocks == 0) return VFN_OK;
+    VFN_REQUIRE(tsdf && weight && coords && (!COLOUR || colour), "%s: NULL volume", what);
+    VFN_REQUIRE(depth && intrinsics && extrinsics && (!COLOUR || rgb), "%s: NULL view argument", what);
+    VFN_REQUIRE(((uintptr_t)tsdf & 15) == 0 && ((uintptr_t)weight & 15) == 0 && ((uintptr_t)colour & 15) == 0, "%s: the block storage must be 16-B aligned",
+                what);
+    SparseVolume vol{tsdf, weight, (const int*)coords, nx, ny, nz, ox, oy, oz, voxel_length, sdf_trunc};
+    Views vs{depth, intrinsics, extrinsics, n_views, height, width};
+    Colour<COLOUR> cl;
+    if constexpr (COLOUR) {
+        cl.colour = colour;
+        cl.rgb = rgb;
+    }
+    hipLaunchKernelGGL((vfn_tsdf_sparse_integrate_kernel<COLOUR>), dim3((unsigned)n_blocks), dim3(SP_THREADS), 0, (hipStream_t)stream, vol, vs, cl);
+    return vfn_check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int vfn_tsdf_sparse_mark(uint8_t* marks, int32_t nbx, int32_t nby, int32_t nbz, float ox, float oy, float oz, float voxel_length,
+                                    float sdf_trunc, const float* depth, int32_t height, int32_t width, const double* cameras, int32_t n_views,
+                                    void* stream) {
+    const char* what = "vfn_tsdf_sparse_mark";
+    VFN_REQUIRE(nbx >= 1 && nby >= 1 && nbz >= 1 && (long long)nbx * nby < (1ll << 31) && (long long)nbx * nby * nbz < (1ll << 31),
+                "%s: the block lattice (%d, %d, %d) must be positive with fewer than 2^31 blocks", what, nbx, nby, nbz);
+    VFN_REQUIRE(voxel_length > 0.f && voxel_length - voxel_length == 0.f && sdf_trunc > 0.f && sdf_trunc - sdf_trunc == 0.f,
+                "%s: voxel_length and sdf_trunc must be positive and finite", what);
+    VFN_REQUIRE(n_views >= 0 && height >= 1 && width >= 1 && (long long)height * width < (1ll << 31),
+                "%s: bad views (%d of %d x %d)", what, n_views, height, width);
+    if (n_views == 0) return VFN_OK;
+    VFN_REQUIRE(marks && depth && cameras, "%s: NULL argument", what);
+    const long long lanes = (long long)height * width * n_views;
+    VFN_REQUIRE((lanes + 255) / 256 < (1ll << 31), "%s: %lld pixels exceed one launch", what, lanes);
+    MarkArgs a{depth, cameras, marks, n_views, height, width, {nbx, nby, nbz}, {(double)ox, (double)oy, (double)oz}, (double)voxel_length,
+               (double)sdf_trunc};
+    hipLaunchKernelGGL(vfn_tsdf_sparse_mark_kernel, dim3(blocks_for(lanes)), dim3(256), 0, (hipStream_t)stream, a);
+    return vfn_check_launch(what);
+}
+
+extern "C" int vfn_tsdf_sparse_integrate(float* tsdf, float* weight, const int32_t* block_coords, int32_t n_blocks, int32_t nx, int32_t ny,
+                                         int32_t nz, float ox, float oy, float oz, float voxel_length, float sdf_trunc, const float* depth,
+                                         int32_t height, int32_t width, const float* intrinsics, const float* extrinsics, int32_t n_views,
+                                         void* stream) {
+    return sparse_integrate<false>("vfn_tsdf_sparse_integrate", tsdf, weight, nullptr, block_coords, n_blocks, nx, ny, nz, ox, oy, oz, voxel_length,
+                                   sdf_trunc, depth, nullptr, height, width, intrinsics, extrinsics, n_views, stream);
+}
+
+extern "C" int vfn_tsdf_sparse_integrate_rgb(float* tsdf, float* weight, float* colour, const int32_t* block_coords, int32_t n_blocks, int32_t nx,
+                                             int32_t ny, int32_t nz, float ox, float oy, float oz, float voxel_length, float sdf_trunc,
+                                             const float* depth, const uint8_t* rgb, int32_t height, int32_t width, const float* intrinsics,
+                                             const float* extrinsics, int32_t n_views, void* stream) {
+    return sparse_integrate<true>("vfn_tsdf_sparse_integrate_rgb", tsdf, weight, colour, block_coords, n_blocks, nx, ny, nz, ox, oy, oz,
+                                  voxel_length, sdf_trunc, depth, rgb, height, width, intrinsics, extrinsics, n_views, stream);
+}
+
+extern "C" int vfn_tsdf_sparse_count(const float* tsdf, const float* weight, const int32_t* block_of, const int32_t* block_coords, int32_t n_blocks,
+                                     int32_t nx, int32_t ny, int32_t nz, int32_t* counts, int32_t* offsets, int64_t* info, void* scan_ws,
+                                     int64_t scan_ws_bytes, void* stream) {
+    SparseLattice a;
+    const int rc = make_sparse_lattice(a, tsdf, weight, block_of, block_coords, n_blocks, nx, ny, nz, 0.f, 0.f, 0.f, 1.f, "vfn_tsdf_sparse_count");
+    if (rc != VFN_OK) return rc;
+    return vfn_mc_count(a, counts, offsets, info, scan_ws, scan_ws_bytes, (hipStream_t)stream, "vfn_tsdf_sparse_count");
+}
+
+extern "C" int vfn_tsdf_sparse_emit(const float* tsdf, const float* weight, const int32_t* block_of, const int32_t* block_coords, int32_t n_blocks,
+                                    int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz, float voxel_length, const int32_t* counts,
+                                    const int32_t* offsets, double* tri_verts, void* stream) {
+    SparseLattice a;
+    const int rc = make_sparse_lattice(a, tsdf, weight, block_of, block_coords, n_blocks, nx, ny, nz, ox, oy, oz, voxel_length, "vfn_tsdf_sparse_emit");
+    if (rc != VFN_OK) return rc;
+    return vfn_mc_emit(a, counts, offsets, tri_verts, (hipStream_t)stream, "vfn_tsdf_sparse_emit");
+}
+
+extern "C" int vfn_tsdf_sparse_emit_colours(const float* tsdf, const float* weight, const float* colour, const int32_t* block_of,
+                                            const int32_t* block_coords, int32_t n_blocks, int32_t nx, int32_t ny, int32_t nz,
+                                            const int32_t* counts, const int32_t* offsets, double* tri_cols, void* stream) {
+    SparseLatticeColours a;
+    const int rc = make_sparse_lattice(a.sp, tsdf, weight, block_of, block_coords, n_blocks, nx, ny, nz, 0.f, 0.f, 0.f, 1.f,
+                                       "vfn_tsdf_sparse_emit_colours");
+    if (rc != VFN_OK) return rc;
+    VFN_REQUIRE(n_blocks == 0 || colour, "vfn_tsdf_sparse_emit_colours: NULL colour volume");
+    a.colour = colour;
+    return vfn_mc_emit(a, counts, offsets, tri_cols, (hipStream_t)stream, "vfn_tsdf_sparse_emit_colours");
+}

@@ -37,7 +37,7 @@ def _ensure_package(name: str) -> None:
 
 
 def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scalars=None, patch_mesh: bool = True,
-            patch_metrics: bool = False, patch_tsdf_mesh: bool = False, tsdf_vertex_normals=None) -> None:
+            patch_metrics: bool = False, patch_tsdf_mesh: bool = False, tsdf_vertex_normals=None, tsdf_sparse=None) -> None:
     """``patch_clip=False`` leaves ``torch.nn.utils.clip_grad_norm_`` PyTorch's own function (no process-wide replacement): a step session then
     parks its gradient in the optimizer's flat buffer with every ``param.grad`` None, the trainer's clip call finds nothing to scale, and
     ``optimizer.step()`` all-reduces (more than one rank), clips with the model's ``scheduler_config.clip_norm`` — the value the trainer
@@ -57,9 +57,13 @@ def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scal
     volume: the coloured ``tsdf-mesh/tsdf.ply``) and keeps the reference's function as
     ``methods._reference_tsdf_mesh``; off by default, and ``False`` after ``True`` puts it back.
     ``tsdf_vertex_normals`` (None: leave as is) sets ``evaluator.TSDF_VERTEX_NORMALS``: True makes ``evaluator.tsdf_mesh`` write the vertex
-    normals (``meshops.vertex_normals``) into ``tsdf.ply``, as the reference's ``compute_vertex_normals()`` does; off by default."""
+    normals (``meshops.vertex_normals``) into ``tsdf.ply``, as the reference's ``compute_vertex_normals()`` does; off by default.
+    ``tsdf_sparse`` (None: leave as is) sets ``evaluator.TSDF_SPARSE``: True makes ``evaluator.tsdf_mesh`` fuse into the block-sparse
+    volume (``tsdf.SparseTSDFVolume``), which has no 2^31 voxel limit; off by default."""
     if tsdf_vertex_normals is not None:
         evaluator.TSDF_VERTEX_NORMALS = bool(tsdf_vertex_normals)
+    if tsdf_sparse is not None:
+        evaluator.TSDF_SPARSE = bool(tsdf_sparse)
     for dotted, module in _ALIASES.items():
         parts = dotted.split(".")
         for i in range(1, len(parts)):

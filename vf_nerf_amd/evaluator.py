@@ -34,6 +34,9 @@ SPARSE_COLOURS = True
 # tsdf_mesh writes nx ny nz (meshops.vertex_normals of the fused mesh) into tsdf.ply; False: the file without normals.
 # dropin.install(tsdf_vertex_normals=...) sets it.
 TSDF_VERTEX_NORMALS = False
+# tsdf_mesh fuses into the block-sparse volume (tsdf.SparseTSDFVolume: no 2^31 voxel limit on the box of the depths); False: the dense
+# volume.  dropin.install(tsdf_sparse=...) sets it.
+TSDF_SPARSE = False
 
 
 @torch.no_grad()
@@ -197,7 +200,8 @@ def tsdf_mesh(eval_path: str, dataset_config) -> None:
     ``tsdf.reference_depth`` states the reference's millimetre round trip, the box of the back-projected depths) and written to
     ``tsdf-mesh/tsdf.ply`` (``ply.write_ply``: binary, float vertices, uchar colours).  The reference calls ``compute_vertex_normals()``
     first: with the module switch ``TSDF_VERTEX_NORMALS`` set the file also holds ``meshops.vertex_normals`` of the fused mesh (the
-    extraction already merges its vertices: no weld); by default it does not.  Installed by ``dropin.install(patch_tsdf_mesh=True)``."""
+    extraction already merges its vertices: no weld); by default it does not.  With ``TSDF_SPARSE`` set the fusion runs in the
+    block-sparse volume, which a scene spanning more than 2^31 voxels does not stop.  Installed by ``dropin.install(patch_tsdf_mesh=True)``."""
     from PIL import Image
     from . import meshops, ply, tsdf
     dataset_dict = importlib.import_module("datasets.normal_datasets").dataset_dict
@@ -216,7 +220,8 @@ def tsdf_mesh(eval_path: str, dataset_config) -> None:
         k = dataset.intrinsics[i] if dataset_config.dataset_name in ["dtu", "deepfashion"] else dataset.intrinsics
         intrinsics.append(torch.as_tensor(k).detach().cpu().to(torch.float64)[:3, :3])
         poses.append(torch.as_tensor(dataset.poses[i]).detach().cpu().to(torch.float64))
-    vertices, faces, colours = tsdf.fuse_rgbd_maps(torch.stack(depths), np.stack(images), torch.stack(intrinsics), torch.stack(poses))
+    vertices, faces, colours = tsdf.fuse_rgbd_maps(torch.stack(depths), np.stack(images), torch.stack(intrinsics), torch.stack(poses),
+                                                   **({"sparse": True} if TSDF_SPARSE else {}))
     mesh_path = os.path.join(eval_path, "tsdf-mesh")
     os.makedirs(mesh_path, exist_ok=True)
     if TSDF_VERTEX_NORMALS:

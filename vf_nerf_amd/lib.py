@@ -44,6 +44,8 @@ EXPORTS = (
     "vfn_nn_sqdist", "vfn_tri_areas", "vfn_cumsum_workspace_bytes", "vfn_cumsum_f64", "vfn_sample_surface",
     "vfn_reduce_stats_workspace_bytes", "vfn_reduce_stats",
     "vfn_tsdf_integrate", "vfn_tsdf_count", "vfn_tsdf_emit", "vfn_tsdf_integrate_rgb", "vfn_tsdf_emit_colours", "vfn_tsdf_vertex_colours",
+    "vfn_tsdf_sparse_mark", "vfn_tsdf_sparse_integrate", "vfn_tsdf_sparse_integrate_rgb", "vfn_tsdf_sparse_count", "vfn_tsdf_sparse_emit",
+    "vfn_tsdf_sparse_emit_colours",
     "vfn_raster_depth", "vfn_smooth_laplacian_step",
     "vfn_transform_points", "vfn_nn_radius", "vfn_icp_accumulate_workspace_bytes", "vfn_icp_accumulate",
     "vfn_nn_nearest", "vfn_nn_nearest_list",
@@ -1771,6 +1773,106 @@ def tsdf_extract_coloured(tsdf: torch.Tensor, weight: torch.Tensor, colour: torc
     vertices, faces, colours = _extract_slots(lambda *out: _check(load().vfn_tsdf_count(*vol, *out), "vfn_tsdf_count"),
                                               lambda *out: _check(load().vfn_tsdf_emit(*vol, *box, *out), "vfn_tsdf_emit"),
                                               (nx - 1) * (ny - 1) * (nz - 1), dev, "TSDF extraction", per_slot=colours_of)
+    return vertices, faces, colours if colours is not None else torch.empty(0, 3, dtype=torch.float64, device=dev)
+
+
+# the block-sparse volume (include/vfn.h: "A block-sparse TSDF volume"; tsdf.SparseTSDFVolume owns the numbering and the tables)
+TSDF_BLOCK = 8
+
+
+def tsdf_block_lattice(dims: Sequence[int]):
+    """ceil(dims / 8) per axis."""
+    return tuple((int(n) + TSDF_BLOCK - 1) // TSDF_BLOCK for n in dims)
+
+
+def tsdf_sparse_mark(marks: torch.Tensor, origin: Sequence[float], voxel_length: float, sdf_trunc: float, depth: torch.Tensor,
+                     cameras: torch.Tensor) -> None:
+    """marks[nbx,nby,nbz] uint8 (zeroed by the caller) gets a 1 in every block near a back-projected point of depth[V,H,W]; cameras[V,17]
+    float64 = camera -> world rows, fx fy cx cy, q.  See include/vfn.h for the rule."""
+    if marks.dim() != 3 or marks.numel() < 1 or marks.numel() >= (1 << 31):
+        raise VfnError(f"marks must be [nbx,nby,nbz] with fewer than 2^31 blocks, got {tuple(marks.shape)}")
+    if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1 or depth.shape[1] * depth.shape[2] >= (1 << 31):
+        raise VfnError(f"depth must be [V,H,W] within the limits of one call, got {tuple(depth.shape)}")
+    v, h, w = depth.shape
+    if tuple(cameras.shape) != (v, 17):
+        raise VfnError(f"{v} views need cameras [{v},17], got {tuple(cameras.shape)}")
+    if depth.device != marks.device or cameras.device != marks.device:
+        raise VfnError("the views and the marks live on different devices")
+    with torch.cuda.device(marks.device):
+        _check(load().vfn_tsdf_sparse_mark(_ptr(marks, "marks", torch.uint8), *(C.c_int32(n) for n in marks.shape),
+                                           *(C.c_float(float(o)) for o in origin), C.c_float(float(voxel_length)), C.c_float(float(sdf_trunc)),
+                                           _ptr(depth, "depth"), C.c_int32(h), C.c_int32(w), _ptr(cameras, "cameras", torch.float64),
+                                           C.c_int32(v), _stream()), "vfn_tsdf_sparse_mark")
+
+
+def _tsdf_sparse_args(tsdf: torch.Tensor, weight: torch.Tensor, block_coords: torch.Tensor, dims: Sequence[int], block_of=None, colour=None):
+    n = tsdf.shape[0] if tsdf.dim() == 4 else -1
+    blk = (TSDF_BLOCK,) * 3
+    if n < 0 or tuple(tsdf.shape[1:]) != blk or weight.shape != tsdf.shape or tuple(block_coords.shape) != (n, 3):
+        raise VfnError(f"tsdf / weight must be [n,8,8,8] with block_coords [n,3], got {tuple(tsdf.shape)}, {tuple(weight.shape)} and "
+                       f"{tuple(block_coords.shape)}")
+    if n * TSDF_BLOCK ** 3 >= (1 << 31):
+        raise VfnError(f"{n} blocks exceed the 2^31 voxel limit")
+    if colour is not None and tuple(colour.shape) != tuple(tsdf.shape) + (3,):
+        raise VfnError(f"colour must be [n,8,8,8,3], got {tuple(colour.shape)}")
+    if block_of is not None and tuple(block_of.shape) != tsdf_block_lattice(dims):
+        raise VfnError(f"block_of must be {tsdf_block_lattice(dims)} for dims {tuple(dims)}, got {tuple(block_of.shape)}")
+    for t in (weight, block_coords, block_of, colour):
+        if t is not None and t.device != tsdf.device:
+            raise VfnError("the arrays of the sparse volume live on different devices")
+    return n, tuple(C.c_int32(int(d)) for d in dims)
+
+
+def tsdf_sparse_integrate(tsdf: torch.Tensor, weight: torch.Tensor, colour: Optional[torch.Tensor], block_coords: torch.Tensor,
+                          dims: Sequence[int], origin: Sequence[float], voxel_length: float, sdf_trunc: float, depth: torch.Tensor,
+                          rgb: Optional[torch.Tensor], intrinsics: torch.Tensor, extrinsics: torch.Tensor) -> None:
+    """All views into every block of tsdf / weight [n,8,8,8] (colour [n,8,8,8,3] with rgb[V,H,W,3] uint8, or both None), in place: the
+    dense volume's arithmetic at the global voxel index 8 block_coords + local.  See include/vfn.h."""
+    if (colour is None) != (rgb is None):
+        raise VfnError("colour and rgb go together")
+    n, d3 = _tsdf_sparse_args(tsdf, weight, block_coords, dims, colour=colour)
+    v, h, w = _tsdf_view_args(tsdf, depth, intrinsics, extrinsics, rgb)
+    box = tuple(C.c_float(float(o)) for o in origin) + (C.c_float(float(voxel_length)), C.c_float(float(sdf_trunc)))
+    views = (C.c_int32(h), C.c_int32(w), _ptr(intrinsics, "intrinsics"), _ptr(extrinsics, "extrinsics"), C.c_int32(v), _stream())
+    with torch.cuda.device(tsdf.device):
+        if colour is None:
+            _check(load().vfn_tsdf_sparse_integrate(_ptr(tsdf, "tsdf"), _ptr(weight, "weight"), _ptr(block_coords, "block_coords", torch.int32),
+                                                    C.c_int32(n), *d3, *box, _ptr(depth, "depth"), *views), "vfn_tsdf_sparse_integrate")
+        else:
+            _check(load().vfn_tsdf_sparse_integrate_rgb(_ptr(tsdf, "tsdf"), _ptr(weight, "weight"), _ptr(colour, "colour"),
+                                                        _ptr(block_coords, "block_coords", torch.int32), C.c_int32(n), *d3, *box,
+                                                        _ptr(depth, "depth"), _ptr(rgb, "rgb", torch.uint8), *views),
+                   "vfn_tsdf_sparse_integrate_rgb")
+
+
+def tsdf_sparse_extract(tsdf: torch.Tensor, weight: torch.Tensor, colour: Optional[torch.Tensor], block_of: torch.Tensor,
+                        block_coords: torch.Tensor, dims: Sequence[int], origin: Sequence[float], voxel_length: float):
+    """The zero level set of the blocks through ``_extract_slots`` -> (vertices, faces) or, with ``colour``, (vertices, faces, colours):
+    the dense extraction's vertex bits, blocks in id order and cells in local C order."""
+    n, d3 = _tsdf_sparse_args(tsdf, weight, block_coords, dims, block_of=block_of, colour=colour)
+    dev = tsdf.device
+    vol = (_ptr(tsdf, "tsdf"), _ptr(weight, "weight"))
+    tables = (_ptr(block_of, "block_of", torch.int32), _ptr(block_coords, "block_coords", torch.int32), C.c_int32(n)) + d3
+    box = tuple(C.c_float(float(o)) for o in origin) + (C.c_float(float(voxel_length)),)
+
+    def colours_of(scanned, ids, n_vert):
+        n_slots = ids.shape[0]
+        tri_cols = torch.empty(n_slots, 3, dtype=torch.float64, device=dev)
+        _check(load().vfn_tsdf_sparse_emit_colours(*vol, _ptr(colour, "colour"), *tables, *scanned, _ptr(tri_cols, "tri_cols", torch.float64),
+                                                   _stream()), "vfn_tsdf_sparse_emit_colours")
+        first = torch.empty(max(n_vert, 1), dtype=torch.int32, device=dev)
+        out = torch.empty(n_vert, 3, dtype=torch.float64, device=dev)
+        _check(load().vfn_tsdf_vertex_colours(_ptr(ids, "ids", torch.int64), C.c_int64(n_slots), _ptr(tri_cols, "tri_cols", torch.float64),
+                                              _ptr(first, "first", torch.int32), C.c_int64(n_vert),
+                                              _ptr(out, "colours", torch.float64) if n_vert else None, _stream()), "vfn_tsdf_vertex_colours")
+        return out
+
+    vertices, faces, colours = _extract_slots(lambda *out: _check(load().vfn_tsdf_sparse_count(*vol, *tables, *out), "vfn_tsdf_sparse_count"),
+                                              lambda *out: _check(load().vfn_tsdf_sparse_emit(*vol, *tables, *box, *out), "vfn_tsdf_sparse_emit"),
+                                              n * TSDF_BLOCK ** 3, dev, "sparse TSDF extraction",
+                                              per_slot=colours_of if colour is not None else None)
+    if colour is None:
+        return vertices, faces
     return vertices, faces, colours if colours is not None else torch.empty(0, 3, dtype=torch.float64, device=dev)
 
 

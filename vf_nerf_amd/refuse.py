@@ -39,12 +39,12 @@ MESH_NAMES = ("tsdf", "refused_tsdf", "tsdf_smoothed", "refused_tsdf_smoothed") 
 
 def refuse(mesh, intrinsics, poses, height: int, width: int, bounds=None, voxel_length: float = tsdf.VOXEL_LENGTH,
            sdf_trunc: float = tsdf.SDF_TRUNC, depth_trunc: float = DEPTH_TRUNC, near: float = raster.NEAR, far: float = raster.FAR,
-           pixel_centre: float = raster.PIXEL_CENTRE, device=None):
+           pixel_centre: float = raster.PIXEL_CENTRE, device=None, sparse: bool = False):
     """Render the mesh's depth from every view, drop depths >= ``depth_trunc``, fuse the maps again -> (vertices, faces).  ``bounds`` as
     in ``tsdf.fuse_depth_maps`` (None: the back-projected depth points, padded by ``sdf_trunc``).  Two empty tensors when no camera
-    sees anything."""
+    sees anything.  ``sparse`` goes to the fusion (``tsdf.fuse_depth_maps``: the block-sparse volume)."""
     return _refuse(mesh, None, intrinsics, poses, height, width, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc,
-                   depth_trunc=depth_trunc, near=near, far=far, pixel_centre=pixel_centre, device=device)
+                   depth_trunc=depth_trunc, near=near, far=far, pixel_centre=pixel_centre, device=device, sparse=sparse)
 
 
 def refuse_rgbd(mesh, rgb, intrinsics, poses, height: int, width: int, **refuse_args):
@@ -58,20 +58,22 @@ def refuse_rgbd(mesh, rgb, intrinsics, poses, height: int, width: int, **refuse_
 
 
 def _refuse(mesh, rgb, intrinsics, poses, height, width, bounds=None, voxel_length=tsdf.VOXEL_LENGTH, sdf_trunc=tsdf.SDF_TRUNC,
-            depth_trunc=DEPTH_TRUNC, near=raster.NEAR, far=raster.FAR, pixel_centre=raster.PIXEL_CENTRE, device=None):
+            depth_trunc=DEPTH_TRUNC, near=raster.NEAR, far=raster.FAR, pixel_centre=raster.PIXEL_CENTRE, device=None, sparse=False):
     if isinstance(depth_trunc, bool) or not isinstance(depth_trunc, (int, float, np.integer, np.floating)) or not float(depth_trunc) > 0:
         raise ValueError(f"depth_trunc must be a positive number, got {depth_trunc!r}")
     vl, _ = geomargs.positive32(voxel_length, "voxel_length"), geomargs.positive32(sdf_trunc, "sdf_trunc")
     if bounds is not None:
-        tsdf.bounds_box(bounds, vl)                                        # every refusal that needs no device comes before the first launch
+        tsdf.bounds_box(bounds, vl, bool(sparse))                          # every refusal that needs no device comes before the first launch
     if rgb is not None:
         n_views = 1 if geomargs.as_tensor(poses, "poses").dim() == 2 else int(geomargs.as_tensor(poses, "poses").shape[0])
         tsdf._stack_rgb(rgb, (n_views, height, width))
     depth = raster.rasterize_depth_counted(mesh, intrinsics, poses, height, width, near=near, far=far, pixel_centre=pixel_centre, device=device)[0]
     depth = torch.where(depth >= float(depth_trunc), torch.zeros_like(depth), depth)
     if rgb is None:
-        return tsdf.fuse_depth_maps(depth, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depth.device)
-    return tsdf.fuse_rgbd_maps(depth, rgb, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depth.device)
+        return tsdf.fuse_depth_maps(depth, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depth.device,
+                                    sparse=bool(sparse))
+    return tsdf.fuse_rgbd_maps(depth, rgb, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depth.device,
+                               sparse=bool(sparse))
 
 
 def vertex_adjacency(faces: torch.Tensor, n_vertices: int) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -5,6 +5,9 @@
   volume, ``extract_mesh`` triangulates the zero level set with classic marching cubes.  ``TSDFVolume(..., colour=True)`` fuses every
   view's RGB image together with its depth (the reference's ``TSDFVolumeColorType.RGB8``); ``extract_coloured_mesh`` adds a colour per
   vertex.
+* ``SparseTSDFVolume`` — the same lattice held as blocks of 8^3 voxels opened near the back-projected depth points: no 2^31 voxel limit,
+  memory that grows with the surface, every held voxel with the dense volume's bits and — on the allocation rule of include/vfn.h — the
+  dense volume's mesh.  ``sparse=True`` on the ``fuse_*`` functions fuses into it; the default stays dense.
 * ``reference_depth`` — a depth map as ``tsdf_mesh`` hands it to the fusion: millimetres as uint16, truncated at ``depth_trunc``.
 * ``fuse_depth_maps`` — depth maps + cameras -> mesh; the box defaults to the back-projected valid depth points, padded by ``sdf_trunc``.
   ``fuse_rgbd_maps`` — the same with the views' images -> (vertices, faces, vertex colours).
@@ -14,12 +17,13 @@
 
 The semantics are modelled on a uniform TSDF volume's integration and extraction as ``tsdf_mesh`` drives one (voxel length 4/512,
 ``sdf_trunc`` 0.04, extrinsic = inv(pose)); include/vfn.h states the arithmetic operation for operation and tests/tsdf_restatement.py
-restates it in NumPy (tests/tsdf_colour_restatement.py: the colour), which the device equals bit for bit.  One deliberate difference
-from the reference's fusion:
+restates it in NumPy (tests/tsdf_colour_restatement.py: the colour; tests/tsdf_sparse_restatement.py: the blocks), which the device equals
+bit for bit.  One deliberate difference from the reference's fusion:
 
-* the volume is DENSE over a box the caller gives, not hashed 16^3 blocks opened near back-projected points.  A voxel in free space in
-  front of a surface therefore collects ``tsdf = 1`` observations here in cases where the hashed volume would never have allocated it;
-  the zero crossing lies inside the truncation band either way.
+* ``TSDFVolume`` is DENSE over a box the caller gives, not hashed 16^3 blocks opened near back-projected points.  A voxel in free space
+  in front of a surface therefore collects ``tsdf = 1`` observations here in cases where the hashed volume would never have allocated it;
+  the zero crossing lies inside the truncation band either way.  ``SparseTSDFVolume`` opens blocks near the points as the hashed volume
+  does, but blocks of 8^3 voxels of the dense lattice, by a rule under which its mesh is the dense one.
 
 A mesh is ``(vertices float64 [n,3], faces int64 [m,3])``, 0-based, on the device — the form ``mesh.triangulate`` returns and
 ``metrics3d.score_mesh`` accepts; a coloured mesh adds ``colours float64 [n,3]`` in [0, 1].  A volume without colour keeps its kernels
@@ -28,7 +32,7 @@ is visible.
 
 ``refuse()`` and Laplacian smoothing (``tsdf-smoothed.ply``) are ``vf_nerf_amd.refuse``: a mesh's depth rasterised on the device
 (``vf_nerf_amd.raster``) and re-fused by this volume.  PLY reading / writing is ``vf_nerf_amd.ply``, the vertex
-normals the reference computes before writing (``compute_vertex_normals()``) are ``meshops.vertex_normals``.  Out of scope: the hashed volume.
+normals the reference computes before writing (``compute_vertex_normals()``) are ``meshops.vertex_normals``.
 """
 from __future__ import annotations
 
@@ -53,6 +57,24 @@ def _check_dims(dims) -> Tuple[int, int, int]:
     d = tuple(int(n) for n in d)
     if d[0] * d[1] * d[2] >= LIMIT:
         raise ValueError(f"a volume of {d[0]} x {d[1]} x {d[2]} voxels exceeds the 2^31 limit")
+    return d
+
+
+BLOCK = 8                         # the edge of a block of the sparse volume, a compile-time constant of csrc/vfn_tsdf.hip
+DIM_LIMIT = 1 << 24               # a lattice index is exact as float32 up to here
+
+
+def _check_sparse_dims(dims) -> Tuple[int, int, int]:
+    """``_check_dims`` for the block-sparse volume: no bound on the voxels; each dim <= 2^24 and fewer than 2^31 blocks of 8^3."""
+    d = tuple(dims)
+    if len(d) != 3 or any(isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 1 for n in d):
+        raise ValueError(f"dims must be three positive integers, got {dims!r}")
+    d = tuple(int(n) for n in d)
+    if max(d) > DIM_LIMIT:
+        raise ValueError(f"a sparse volume of {d[0]} x {d[1]} x {d[2]} voxels exceeds 2^24 voxels along an axis")
+    nb = lib.tsdf_block_lattice(d)
+    if nb[0] * nb[1] * nb[2] >= LIMIT:
+        raise ValueError(f"a sparse volume of {d[0]} x {d[1]} x {d[2]} voxels has {nb[0]} x {nb[1]} x {nb[2]} blocks: beyond the 2^31 limit")
     return d
 
 
@@ -212,6 +234,155 @@ class TSDFVolume:
         return lib.tsdf_extract_coloured(self.tsdf, self.weight, self.colour, self.origin, self.voxel_length)
 
 
+def mark_cameras(k: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """What the allocation kernel reads per view, float64 [V,17] (host): C[12], the first three rows of ``numpy.linalg.inv`` of the 4x4 built
+    from the float32 extrinsic rows ``e`` [V,12] promoted to float64 — the allocation inverts exactly the matrix the integration uses —,
+    then fx fy cx cy (the float32 intrinsics ``k`` [V,4] promoted) and q = sqrt(1 / (fx fx) + 1 / (fy fy))."""
+    k64, e64 = k.numpy().astype(np.float64), e.numpy().astype(np.float64)
+    out = np.empty((k64.shape[0], 17), dtype=np.float64)
+    for i in range(k64.shape[0]):
+        m = np.eye(4, dtype=np.float64)
+        m[:3] = e64[i].reshape(3, 4)
+        out[i, :12] = np.linalg.inv(m)[:3].reshape(12)
+        fx, fy = k64[i, 0], k64[i, 1]
+        out[i, 12:16] = k64[i]
+        out[i, 16] = np.sqrt(np.float64(1.0) / (fx * fx) + np.float64(1.0) / (fy * fy))
+    return torch.from_numpy(out)
+
+
+class SparseTSDFVolume:
+    """A block-sparse TSDF volume over the lattice of ``TSDFVolume(origin, dims, voxel_length)``: the same ``origin`` / ``dims`` /
+    ``voxel_length`` taken as float32, voxel (i, j, k) centred at origin + ((float)index + 0.5f) voxel_length with the GLOBAL index — so
+    every voxel it holds carries the bits of the dense volume over the same lattice — but only blocks of ``BLOCK``^3 = 8^3 voxels near
+    the back-projected depth points exist.  ``dims`` are not bound by 2^31 voxels: each dim is <= 2^24, the block lattice
+    nb = ceil(dims / 8) has fewer than 2^31 blocks, and the allocated blocks hold fewer than 2^31 voxels.
+
+    The block edge is 8, not the 16 of the reference's hashed volume (which is not reproduced bit for bit anyway): 8 wastes about 30 %
+    fewer voxels around a band of +-(sdf_trunc + one voxel), and one block is two waves of lanes owning 4 consecutive k voxels each.
+
+    State, all on the device: ``block_of`` int32 [nbx,nby,nbz] (-1: absent), ``block_coords`` int32 [n_blocks,3], ``tsdf`` / ``weight``
+    float32 [n_blocks,8,8,8] and ``colour`` float32 [n_blocks,8,8,8,3] in byte units (None without colour).  Block ids are given in order
+    of allocation call and, within a call, in ascending C order of the block lattice (``torch.nonzero`` of the marks; no atomics decide a
+    number); they never change, growth is a ``torch.cat``.  Voxels of an edge block whose global index is >= dims are never updated and
+    keep weight == 0.
+
+    Allocation rule (include/vfn.h, vfn_tsdf_sparse_mark; DESIGN 6p has the argument): a pixel with depth d > 0 opens every block that
+    the axis-aligned cube of half edge r = sdf_trunc + 0.5 (d + sdf_trunc) q + 2 voxel_length around its back-projected point touches,
+    q = sqrt(1 / fx^2 + 1 / fy^2).  With it, every cell the dense extraction triangulates has its eight corners in allocated blocks:
+    after ONE ``integrate`` of all views the mesh is the dense volume's mesh.  A voxel of a block holds the bits of a dense volume
+    that was zero until the call that opened the block."""
+
+    def __init__(self, origin, dims, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC, device=None, colour: bool = False):
+        self.dims = _check_sparse_dims(dims)
+        self.voxel_length = geomargs.positive32(voxel_length, "voxel_length")
+        self.sdf_trunc = geomargs.positive32(sdf_trunc, "sdf_trunc")
+        o = np.asarray(origin.detach().cpu() if isinstance(origin, torch.Tensor) else origin, dtype=np.float64).reshape(-1)
+        if o.shape != (3,) or not np.isfinite(o.astype(np.float32)).all():
+            raise ValueError(f"origin must be three finite numbers, got {origin!r}")
+        self.origin = tuple(float(x) for x in o.astype(np.float32))
+        self.device = geomargs.device(device, "TSDF fusion")
+        self.block_dims = lib.tsdf_block_lattice(self.dims)
+        self._has_colour = bool(colour)
+        self.reset()
+
+    def reset(self) -> None:
+        """Back to no blocks."""
+        dev, blk = self.device, (BLOCK,) * 3
+        self.block_of = torch.full(self.block_dims, -1, dtype=torch.int32, device=dev)
+        self.block_coords = torch.zeros(0, 3, dtype=torch.int32, device=dev)
+        self.tsdf = torch.zeros((0,) + blk, dtype=torch.float32, device=dev)
+        self.weight = torch.zeros((0,) + blk, dtype=torch.float32, device=dev)
+        self.colour = torch.zeros((0,) + blk + (3,), dtype=torch.float32, device=dev) if self._has_colour else None
+
+    @property
+    def n_blocks(self) -> int:
+        return int(self.block_coords.shape[0])
+
+    @property
+    def memory_bytes(self) -> int:
+        """The bytes of the state: table, coordinates and voxel arrays."""
+        return sum(t.numel() * t.element_size() for t in (self.block_of, self.block_coords, self.tsdf, self.weight, self.colour) if t is not None)
+
+    def _views(self, depth, intrinsics, pose, rgb, need_rgb: bool):
+        d = _stack_depths(depth)
+        v = d.shape[0]
+        if need_rgb and (rgb is None) != (self.colour is None):
+            raise ValueError("rgb is required by a volume with colour" if rgb is None else "rgb was given to a volume without colour")
+        c = None if rgb is None else _stack_rgb(rgb, d.shape)
+        k = split_intrinsics(intrinsics, v)
+        e = extrinsics_from_poses(pose, v)
+        _check_depth_values(d, "depth")
+        return d.to(self.device, torch.float32).contiguous(), c, k, e
+
+    def _allocate(self, d: torch.Tensor, k: torch.Tensor, e: torch.Tensor) -> int:
+        marks = torch.zeros(self.block_dims, dtype=torch.uint8, device=self.device)
+        lib.tsdf_sparse_mark(marks, self.origin, self.voxel_length, self.sdf_trunc, d, mark_cameras(k, e).to(self.device))
+        new = marks.bool() & (self.block_of < 0)
+        coords = torch.nonzero(new)                               # ascending C order; its size is the one host read
+        n_new, n_old = int(coords.shape[0]), self.n_blocks
+        if n_new == 0:
+            return 0
+        if (n_old + n_new) * BLOCK ** 3 >= LIMIT:
+            raise ValueError(f"{n_old + n_new} blocks of {BLOCK}^3 voxels exceed the 2^31 limit")
+        self.block_of[new] = torch.arange(n_old, n_old + n_new, dtype=torch.int32, device=self.device)
+        self.block_coords = torch.cat([self.block_coords, coords.to(torch.int32)])
+        blk = (n_new,) + (BLOCK,) * 3
+        self.tsdf = torch.cat([self.tsdf, torch.zeros(blk, dtype=torch.float32, device=self.device)])
+        self.weight = torch.cat([self.weight, torch.zeros(blk, dtype=torch.float32, device=self.device)])
+        if self.colour is not None:
+            self.colour = torch.cat([self.colour, torch.zeros(blk + (3,), dtype=torch.float32, device=self.device)])
+        return n_new
+
+    def allocate(self, depth, intrinsics, pose) -> int:
+        """Opens the blocks near the back-projected points of the views (arguments as ``integrate``) -> the number of new blocks."""
+        d, _, k, e = self._views(depth, intrinsics, pose, None, False)
+        return self._allocate(d, k, e)
+
+    def integrate(self, depth, intrinsics, pose, rgb=None, allocate: bool = True) -> None:
+        """``TSDFVolume.integrate``'s arguments.  First opens the blocks of all its views (unless ``allocate=False``), then applies all
+        its views, in index order, to EVERY block allocated so far — one pass over the blocks, whatever V is."""
+        d, c, k, e = self._views(depth, intrinsics, pose, rgb, True)
+        if allocate:
+            self._allocate(d, k, e)
+        if self.n_blocks == 0:
+            return
+        lib.tsdf_sparse_integrate(self.tsdf, self.weight, self.colour, self.block_coords, self.dims, self.origin, self.voxel_length,
+                                  self.sdf_trunc, d, None if c is None else _rgb_bytes(c, self.device), k.to(self.device), e.to(self.device))
+
+    def extract_mesh(self):
+        """-> (vertices float64 [n,3], faces int64 [m,3], 0-based) on the device: blocks in id order, cells in local C order, vertices
+        numbered by first appearance, each with the dense extraction's position bits."""
+        if self.n_blocks == 0:
+            return geomargs.empty_mesh(self.device)
+        return lib.tsdf_sparse_extract(self.tsdf, self.weight, None, self.block_of, self.block_coords, self.dims, self.origin, self.voxel_length)
+
+    def extract_coloured_mesh(self):
+        """``extract_mesh`` of a volume with colour -> (vertices, faces, colours float64 [n,3] in [0,1])."""
+        if self.colour is None:
+            raise ValueError("extract_coloured_mesh needs a volume with colour (SparseTSDFVolume(..., colour=True))")
+        if self.n_blocks == 0:
+            return geomargs.empty_mesh(self.device) + (torch.empty(0, 3, dtype=torch.float64, device=self.device),)
+        return lib.tsdf_sparse_extract(self.tsdf, self.weight, self.colour, self.block_of, self.block_coords, self.dims, self.origin,
+                                       self.voxel_length)
+
+    def to_dense(self):
+        """-> (tsdf, weight[, colour]) as [nx,ny,nz] (colour [nx,ny,nz,3]) device tensors, absent voxels zero — for tests and small
+        scenes: a lattice of 2^31 voxels or more is refused."""
+        nx, ny, nz = self.dims
+        if nx * ny * nz >= LIMIT:
+            raise ValueError(f"to_dense: a lattice of {nx} x {ny} x {nz} voxels exceeds the 2^31 limit")
+        nb = self.block_dims
+        bi, bj, bk = (self.block_coords[:, c].long() for c in range(3))
+
+        def spread(blocks, tail=()):
+            out = torch.zeros((nb[0], BLOCK, nb[1], BLOCK, nb[2], BLOCK) + tail, dtype=blocks.dtype, device=self.device)
+            out[bi, :, bj, :, bk, :] = blocks
+            return out.reshape((nb[0] * BLOCK, nb[1] * BLOCK, nb[2] * BLOCK) + tail)[:nx, :ny, :nz].contiguous()
+
+        dense = (spread(self.tsdf), spread(self.weight))
+        return dense if self.colour is None else dense + (spread(self.colour, (3,)),)
+
+
 def depth_bounds(depths: torch.Tensor, k: torch.Tensor, poses: torch.Tensor) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
     """min / max (float64 [3] each, host) of the valid depth points of depths[V,H,W] back-projected through fx fy cx cy and the
     camera-to-world poses — torch on the depth maps' device; None when no pixel is valid."""
@@ -236,8 +407,9 @@ def depth_bounds(depths: torch.Tensor, k: torch.Tensor, poses: torch.Tensor) -> 
     return lo.cpu(), hi.cpu()
 
 
-def bounds_box(bounds, vl: float):
-    """(min[3], max[3]) -> (origin float64 [3], dims): ceil(extent / voxel_length) voxels per axis, at least one."""
+def bounds_box(bounds, vl: float, sparse: bool = False):
+    """(min[3], max[3]) -> (origin float64 [3], dims): ceil(extent / voxel_length) voxels per axis, at least one.  ``sparse``: the dims
+    are held to the block-sparse volume's limits, not to the dense volume's 2^31 voxels."""
     if len(bounds) != 2:
         raise ValueError("bounds must be (min[3], max[3])")
     lo, hi = (np.asarray(b.detach().cpu() if isinstance(b, torch.Tensor) else b, dtype=np.float64).reshape(-1) for b in bounds)
@@ -246,29 +418,32 @@ def bounds_box(bounds, vl: float):
     extent = (hi - lo) / vl
     if not (extent < LIMIT).all():
         raise ValueError(f"a box of {extent} voxels exceeds the 2^31 limit")
-    return lo, _check_dims(tuple(max(1, int(math.ceil(float(x)))) for x in extent))
+    return lo, (_check_sparse_dims if sparse else _check_dims)(tuple(max(1, int(math.ceil(float(x)))) for x in extent))
 
 
 _box = bounds_box          # (the name before it became public)
 
 
-def fuse_depth_maps(depths, intrinsics, poses, bounds=None, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC, device=None):
+def fuse_depth_maps(depths, intrinsics, poses, bounds=None, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC, device=None,
+                    sparse: bool = False):
     """Depth maps [V,H,W] (or one [H,W]) with their cameras -> (vertices, faces): one volume, one integration pass, one extraction.
     ``bounds`` = (min[3], max[3]) of the box; None: the min / max of the back-projected valid depth points, padded by ``sdf_trunc``.
-    The box is covered by ceil(extent / voxel_length) voxels per axis (at least one)."""
-    return _fuse_maps(depths, None, intrinsics, poses, bounds, voxel_length, sdf_trunc, device)
+    The box is covered by ceil(extent / voxel_length) voxels per axis (at least one).  ``sparse=True`` fuses into a
+    ``SparseTSDFVolume`` over the same box and lattice — held to its limits, not to 2^31 voxels — and returns its mesh."""
+    return _fuse_maps(depths, None, intrinsics, poses, bounds, voxel_length, sdf_trunc, device, sparse)
 
 
 def fuse_rgbd_maps(depths, colours, intrinsics, poses, bounds=None, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC,
-                   device=None):
+                   device=None, sparse: bool = False):
     """``fuse_depth_maps`` with the views' images ``colours`` (uint8 [V,H,W,3] / [H,W,3], or float32 in [0, 1] quantised as the PNG is)
-    -> (vertices, faces, vertex_colours float64 [n,3] in [0,1]); the vertices and faces are ``fuse_depth_maps``' for the same depths."""
+    -> (vertices, faces, vertex_colours float64 [n,3] in [0,1]); the vertices and faces are ``fuse_depth_maps``' for the same depths.
+    ``sparse`` as in ``fuse_depth_maps``."""
     if colours is None:
         raise ValueError("colours is required (fuse_depth_maps fuses depth alone)")
-    return _fuse_maps(depths, colours, intrinsics, poses, bounds, voxel_length, sdf_trunc, device)
+    return _fuse_maps(depths, colours, intrinsics, poses, bounds, voxel_length, sdf_trunc, device, sparse)
 
 
-def _fuse_maps(depths, colours, intrinsics, poses, bounds, voxel_length, sdf_trunc, device):
+def _fuse_maps(depths, colours, intrinsics, poses, bounds, voxel_length, sdf_trunc, device, sparse=False):
     vl, tr = geomargs.positive32(voxel_length, "voxel_length"), geomargs.positive32(sdf_trunc, "sdf_trunc")
     d = _stack_depths(depths, "depths")
     v = d.shape[0]
@@ -276,7 +451,7 @@ def _fuse_maps(depths, colours, intrinsics, poses, bounds, voxel_length, sdf_tru
     k = split_intrinsics(intrinsics, v)
     e = extrinsics_from_poses(poses, v)
     _check_depth_values(d, "depths")                           # (on whatever device the maps live)
-    box = None if bounds is None else bounds_box(bounds, vl)         # every refusal that needs no device comes before the device is asked for
+    box = None if bounds is None else bounds_box(bounds, vl, sparse)         # every refusal that needs no device comes before the device is asked for
     dev = geomargs.device(device if device is not None else (d.device if d.is_cuda else None), "TSDF fusion")
     d = d.to(dev, torch.float32).contiguous()
     if box is None:
@@ -284,7 +459,14 @@ def _fuse_maps(depths, colours, intrinsics, poses, bounds, voxel_length, sdf_tru
         found = depth_bounds(d, k, p.unsqueeze(0) if p.dim() == 2 else p)
         if found is None:
             return geomargs.empty_mesh(dev) + (() if c is None else (torch.empty(0, 3, dtype=torch.float64, device=dev),))
-        box = bounds_box((found[0].numpy() - tr, found[1].numpy() + tr), vl)
+        box = bounds_box((found[0].numpy() - tr, found[1].numpy() + tr), vl, sparse)
+    if sparse:
+        vol = SparseTSDFVolume(box[0], box[1], voxel_length=vl, sdf_trunc=tr, device=dev, colour=c is not None)
+        vol._allocate(d, k, e)
+        if vol.n_blocks:
+            lib.tsdf_sparse_integrate(vol.tsdf, vol.weight, vol.colour, vol.block_coords, vol.dims, vol.origin, vol.voxel_length, vol.sdf_trunc, d,
+                                      None if c is None else _rgb_bytes(c, dev), k.to(dev), e.to(dev))
+        return vol.extract_mesh() if c is None else vol.extract_coloured_mesh()
     vol = TSDFVolume(box[0], box[1], voxel_length=vl, sdf_trunc=tr, device=dev, colour=c is not None)
     if c is None:
         lib.tsdf_integrate(vol.tsdf, vol.weight, vol.origin, vol.voxel_length, vol.sdf_trunc, d, k.to(dev), e.to(dev))
@@ -353,32 +535,36 @@ def _render_maps(model, poses, intrinsics, height, width, epoch, split_size, whi
 def fuse_rendered_views(model, poses, intrinsics, height: int, width: int, epoch: int, bounds=None, voxel_length: float = VOXEL_LENGTH,
                         sdf_trunc: float = SDF_TRUNC, as_reference: bool = True, depth_scale: float = DEPTH_SCALE,
                         depth_trunc: float = DEPTH_TRUNC, split_size: int = 512, white: bool = False, n_streams: int = 2,
-                        min_chunk: Optional[int] = None):
+                        min_chunk: Optional[int] = None, sparse: bool = False):
     """render-images -> tsdf-mesh in one call: the model's views (camera-to-world ``poses`` [V,4,4], ``intrinsics`` shared or per view)
     rendered at ``height`` x ``width``, their depth maps — as ``tsdf_mesh`` stores them when ``as_reference`` (``reference_depth``) —
     fused into a volume over ``bounds`` and triangulated.  The depth maps never leave the device; -> (vertices, faces).
 
     A rendered depth below zero (compositing can leave one on a ray without a surface) is no measurement and becomes 0 — where the
-    reference's unchecked uint16 cast in practice wraps it past ``depth_trunc``, which zeroes it too.  Non-finite depths are refused."""
+    reference's unchecked uint16 cast in practice wraps it past ``depth_trunc``, which zeroes it too.  Non-finite depths are refused.
+    ``sparse`` as in ``fuse_depth_maps``."""
     depths = render_depth_maps(model, poses, intrinsics, height, width, epoch, split_size=split_size, white=white, n_streams=n_streams,
                                min_chunk=min_chunk)
     depths = torch.where(depths < 0, torch.zeros_like(depths), depths)
     if as_reference:
         depths = reference_depth(depths, depth_scale=depth_scale, depth_trunc=depth_trunc)
-    return fuse_depth_maps(depths, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depths.device)
+    return fuse_depth_maps(depths, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depths.device,
+                           sparse=sparse)
 
 
 @torch.no_grad()
 def fuse_rendered_rgbd(model, poses, intrinsics, height: int, width: int, epoch: int, bounds=None, voxel_length: float = VOXEL_LENGTH,
                        sdf_trunc: float = SDF_TRUNC, as_reference: bool = True, depth_scale: float = DEPTH_SCALE,
                        depth_trunc: float = DEPTH_TRUNC, split_size: int = 512, white: bool = False, n_streams: int = 2,
-                       min_chunk: Optional[int] = None):
+                       min_chunk: Optional[int] = None, sparse: bool = False):
     """``fuse_rendered_views`` with colour: the same arguments and the same depth handling, the rendered rgb kept as the PNG's bytes
     (``render_rgbd_maps``) and fused with the depth -> (vertices, faces, vertex_colours).  The vertices and faces are
-    ``fuse_rendered_views``' for the same random stream; ``ply.write_ply`` writes the result as the reference's ``tsdf.ply``."""
+    ``fuse_rendered_views``' for the same random stream; ``ply.write_ply`` writes the result as the reference's ``tsdf.ply``.
+    ``sparse`` as in ``fuse_depth_maps``."""
     depths, images = render_rgbd_maps(model, poses, intrinsics, height, width, epoch, split_size=split_size, white=white, n_streams=n_streams,
                                       min_chunk=min_chunk)
     depths = torch.where(depths < 0, torch.zeros_like(depths), depths)
     if as_reference:
         depths = reference_depth(depths, depth_scale=depth_scale, depth_trunc=depth_trunc)
-    return fuse_rgbd_maps(depths, images, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depths.device)
+    return fuse_rgbd_maps(depths, images, intrinsics, poses, bounds=bounds, voxel_length=voxel_length, sdf_trunc=sdf_trunc, device=depths.device,
+                          sparse=sparse)
