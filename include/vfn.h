@@ -1108,6 +1108,40 @@ int vfn_vertex_normals(const double* face_normals, int64_t m, const int64_t* row
 int vfn_normal_dots(const double* qn, int64_t n, const double* tn, int64_t m, const int64_t* index, double* out, int64_t* info, void* stream);
 
 /* =============================================================================================
+ * Voxel down-sampling of a point set (csrc/vfn_voxel.hip; vf_nerf_amd/voxel.py, metrics3d.voxel_down_sample): the first step of the
+ * evaluate_3d_reconstruction protocol the reference's metrics_3d calls — both clouds are down-sampled before they are registered and
+ * before precision and recall are counted, so that every occupied voxel votes once.  A SPECIFICATION of ours that imitates Open3D's
+ * voxel_down_sample AS REMEMBERED: neither Open3D nor that package is available to compare against, and Open3D's hash map fixes no
+ * order of summation; ours does.  Everything is float64, evaluated without contraction in the association written here, with no
+ * floating-point atomics: no bit depends on the schedule.  Keys, tables and counts are int64.
+ *   The frame (host arithmetic, Python floats): h = voxel_size, finite and > 0 with a normal square;
+ *                       origin_k = min_k(points) - 0.5 h             (Open3D's voxel_min_bound)
+ *                       dims_k   = floor((max_k(points) - origin_k) / h) + 1 <= 2^VFN_VOXEL_AXIS_BITS
+ *   vfn_voxel_keys    reads points[n, 3] and the HOST values origin[3], h; one lane per point:
+ *                       c_k = floor((p_k - origin_k) / h)              a subtraction and a true division, in exactly this expression
+ *                       keys[i] = (c_0 << 42) | (c_1 << 21) | c_2      as int64
+ *                     A non-finite coordinate: info bit 1, keys[i] = -1.  A c_k outside [0, 2^21) (NaN included; only an origin that is
+ *                     not the box's can do that): info bit 2, keys[i] = -1.  No key indexes memory in this kernel.
+ *   Order and numbering (the caller's, by a STABLE ascending sort of the keys): a voxel is a maximal run of equal keys; voxels are
+ *                     numbered in ascending key — lexicographic (c_0, c_1, c_2) —; inside a voxel the points stand in ascending original
+ *                     index; start[V + 1] (int64) holds every voxel's first sorted position and n.
+ *   vfn_voxel_means   reads sorted_values[n, channels] (the rows gathered into sorted order, 1 <= channels <= 9) and start[n_voxels + 1];
+ *                     one lane per voxel, per channel:
+ *                       S = x_b;  S = S + x_(b+1);  ...  S = S + x_(e-1)       b = start[v], e = start[v + 1]: ascending position
+ *                       means[v, c] = S / (double)(e - b)
+ *                     The sum STARTS FROM THE FIRST ELEMENT, not from +0.0: a voxel holding one -0.0 keeps it.  The table is not
+ *                     trusted: a segment that is empty, decreasing or outside [0, n] gets NaN in its row and info bit 2, and nothing is
+ *                     read through it.  A voxel holding every point is walked by one lane: slow, and correct.
+ * info[0] (int64, zero-filled by the caller, only OR-ed into).  Limits: 1 <= n < 2^31, 1 <= n_voxels <= n.  Every argument check
+ * answers before any launch.
+ * ============================================================================================= */
+#define VFN_VOXEL_AXIS_BITS 21        /* a voxel index per axis lies in [0, 2^21): three of them fill 63 bits of an int64 key */
+#define VFN_VOXEL_MAX_CHANNELS 9      /* points, normals and colours of one cloud in one call */
+int vfn_voxel_keys(const double* points, int64_t n, const double* origin, double voxel_size, int64_t* keys, int64_t* info, void* stream);
+int vfn_voxel_means(const double* sorted_values, int64_t n, int32_t channels, const int64_t* start, int64_t n_voxels, double* means,
+                    int64_t* info, void* stream);
+
+/* =============================================================================================
  * Optimizer side of a training step over ONE flat fp32 buffer (train/vector_field_nerf_train.py:254-260:
  * torch.nn.utils.clip_grad_norm_(model.parameters(), clip); optimizer.step()).  The unique parameters — and their gradients
  * and Adam moments — are laid out contiguously, sorted into up to four REGIONS [start, end) of equal multiplicity `mult` =

@@ -7,6 +7,8 @@
 * ``align`` — the ICP loop: search, 17 sums on the device (``vfn_icp_accumulate``), ONE host read per iteration, a rigid 3 x 3 solve on
   the host in float64 (rotation + translation, no scale).
 * ``transform_points`` — a point set under a 4 x 4 rigid transformation, with the arithmetic the search applies on the fly.
+* ``align_stages`` — ``align`` coarse to fine on voxel-down-sampled copies (``metrics3d.voxel_down_sample``), the staged registration of
+  the external package's protocol; rigid, no scale.
 
 This is a specification, not a recording: neither Open3D nor the external package is available to compare against, and neither
 publishes its arithmetic.  The defaults that imitate Open3D's ``registration_icp`` — 30 iterations, relative fitness / rmse criteria of
@@ -237,6 +239,83 @@ def align(source_points, target_points, max_correspondence_distance, init=None, 
     DESIGN 6l).  The defaults imitate Open3D's and are not verified against it."""
     return _align(source_points, target_points, max_correspondence_distance, init, max_iteration, relative_fitness, relative_rmse, device,
                   reorder=True)
+
+
+@dataclasses.dataclass
+class StagedResult(Result):
+    """``Result`` of ``align_stages``: ``transformation`` is the composed one, ``fitness`` / ``inlier_rmse`` / ``converged`` the last stage's,
+    ``iterations`` the total, ``history`` every stage's searches one after the other (each entry with its "stage"; an entry's
+    transformation is its stage's own, from the identity, of the source as that stage received it)."""
+    stages: List[dict]                 # per stage: voxel_size, the radius, source_points / target_points after down-sampling, and
+                                       # that stage's transformation, fitness, inlier_rmse, iterations, converged
+
+
+def compose(a, b) -> np.ndarray:
+    """The rigid [4,4] a . b in plain Python floats: every entry of the 3 x 3 block the sum of three products in ascending k,
+    (a_i0 b_0j + a_i1 b_1j) + a_i2 b_2j, the translation that sum over b's translation plus a's; last row 0 0 0 1.  No BLAS enters
+    the bits."""
+    a, b = [[float(x) for x in row] for row in a], [[float(x) for x in row] for row in b]
+    out = np.eye(4)
+    for i in range(3):
+        for j in range(4):
+            s = (a[i][0] * b[0][j] + a[i][1] * b[1][j]) + a[i][2] * b[2][j]
+            out[i, j] = s + a[i][3] if j == 3 else s
+    return out
+
+
+def _check_stages(stages) -> List[tuple]:
+    from . import voxel                 # (metrics3d imports this module and voxel alike)
+    if isinstance(stages, (str, bytes)) or not hasattr(stages, "__iter__"):
+        raise ValueError(f"stages must be a sequence of (voxel_size or None, max_correspondence_distance, max_iteration), got {stages!r}")
+    out = []
+    for k, stage in enumerate(stages):
+        if isinstance(stage, (str, bytes)) or not hasattr(stage, "__len__") or len(stage) != 3:
+            raise ValueError(f"stages[{k}] must be (voxel_size or None, max_correspondence_distance, max_iteration), got {stage!r}")
+        size, radius, iterations = stage
+        size = None if size is None else voxel.check_voxel_size(size, f"stages[{k}] voxel_size")
+        radius = _check_radius(radius, f"stages[{k}] max_correspondence_distance")
+        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 0:
+            raise ValueError(f"stages[{k}] max_iteration must be a non-negative integer, got {iterations!r}")
+        out.append((size, radius, int(iterations)))
+    if not out:
+        raise ValueError("stages is empty")
+    return out
+
+
+def align_stages(source_points, target_points, stages, init=None, device=None) -> StagedResult:
+    """The staged registration of the ``evaluate_3d_reconstruction`` protocol: coarse to fine on voxel-down-sampled copies.  ``stages`` is
+    a sequence of (voxel_size or None, max_correspondence_distance, max_iteration).  With T = ``init`` (or the identity), per stage:
+    the source is moved by T (``transform_points``); the moved source and the target are down-sampled at the stage's voxel size
+    (``metrics3d.voxel_down_sample``; None: taken as they are); ``align`` runs on the two from the identity; T <- T_stage . T
+    (``compose``: Python floats, no BLAS).  -> ``StagedResult``.
+
+    Rigid, with NO scale: the Tanks-and-Temples evaluation scripts that this schedule follows estimate a scale in their registration;
+    this does not.  The schedule, like ``align`` and the down-sampling, is a specification of ours, not verified against Open3D or the
+    external package."""
+    from . import voxel
+    src, tgt = _check_points(source_points, "source_points"), _check_points(target_points, "target_points")
+    stages = _check_stages(stages)
+    t_k = _check_transform(init, "init")
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        src, tgt = _dev_points(src, dev), _dev_points(tgt, dev)
+        t_k = np.eye(4) if t_k is None else t_k
+        history: List[dict] = []
+        report: List[dict] = []
+        targets = {None: tgt}              # the target down-sampled once per voxel size
+        for k, (size, radius, iterations) in enumerate(stages):
+            moved = lib.transform_points(src, _twelve(t_k))
+            if size is not None:
+                moved = voxel.down_sample_device(moved, size).points
+                if size not in targets:
+                    targets[size] = voxel.down_sample_device(tgt, size).points
+            res = align(moved, targets[size], radius, max_iteration=iterations, device=dev)
+            t_k = compose(res.transformation, t_k)
+            history += [dict(entry, stage=k) for entry in res.history]
+            report.append({"voxel_size": size, "max_correspondence_distance": radius, "source_points": int(moved.shape[0]),
+                           "target_points": int(targets[size].shape[0]), "transformation": res.transformation, "fitness": res.fitness,
+                           "inlier_rmse": res.inlier_rmse, "iterations": res.iterations, "converged": res.converged})
+    return StagedResult(t_k, res.fitness, res.inlier_rmse, sum(s["iterations"] for s in report), res.converged, history, report)
 
 
 def _align(source_points, target_points, max_correspondence_distance, init, max_iteration, relative_fitness, relative_rmse, device,

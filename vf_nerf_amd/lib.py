@@ -51,6 +51,7 @@ EXPORTS = (
     "vfn_nn_nearest", "vfn_nn_nearest_list",
     "vfn_image_quantize8", "vfn_image_scores_workspace_bytes", "vfn_image_scores", "vfn_image_abs_err",
     "vfn_face_normals", "vfn_vertex_normals", "vfn_normal_dots",
+    "vfn_voxel_keys", "vfn_voxel_means",
 )
 
 
@@ -2014,6 +2015,64 @@ def normal_dots(qn: torch.Tensor, tn: torch.Tensor, index: torch.Tensor, info: O
     if own and n:
         normals_check(int(info.cpu()), "normal dots")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# voxel down-sampling (csrc/vfn_voxel.hip; vf_nerf_amd/voxel.py is the public surface).  Everything float64 / int64, contiguous, on one device.
+# ------------------------------------------------------------------------------------------------
+def voxel_limits():
+    """-> (voxels per axis at most, channels of one means call at most): 2^VFN_VOXEL_AXIS_BITS, VFN_VOXEL_MAX_CHANNELS."""
+    return 1 << header_constant("VFN_VOXEL_AXIS_BITS"), header_constant("VFN_VOXEL_MAX_CHANNELS")
+
+
+def voxel_check(status: int, what: str = "voxel down-sampling") -> None:
+    if status & GEOM_STATUS_NONFINITE:
+        raise VfnError(f"{what}: a non-finite coordinate")
+    if status & GEOM_STATUS_INDEX:
+        raise VfnError(f"{what}: a voxel index outside [0, 2^{header_constant('VFN_VOXEL_AXIS_BITS')}) or a segment outside its range")
+
+
+def voxel_keys(points: torch.Tensor, origin, voxel_size: float, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """points[n,3], three host floats, the voxel edge -> keys[n] int64 (include/vfn.h: vfn_voxel_keys); -1 where a coordinate is not
+    finite or a voxel index leaves [0, 2^21).  A bad input raises — or, with the caller's zero-filled ``info`` (int64 [1]), sets its
+    bits (``voxel_check``)."""
+    n = points.shape[0]
+    if points.dim() != 2 or points.shape[1] != 3 or len(origin) != 3:
+        raise VfnError(f"voxel_keys: points must be [n,3] and origin three values, got {tuple(points.shape)} and {len(origin)}")
+    dev = points.device
+    ptr = _ptr(points, "points", torch.float64)
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_voxel_keys(ptr, C.c_int64(n), (C.c_double * 3)(*(float(o) for o in origin)), C.c_double(voxel_size),
+                                     _ptr(keys, "keys", torch.int64), _ptr(info, "info", torch.int64), _stream()), "vfn_voxel_keys")
+    if own:
+        voxel_check(int(info.cpu()))
+    return keys
+
+
+def voxel_means(sorted_values: torch.Tensor, start: torch.Tensor, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sorted_values[n,C] (1 <= C <= 9), start[V+1] int64 -> means[V,C]: every segment's serial sum in ascending position, started from
+    its first row, over its count (include/vfn.h: vfn_voxel_means); NaN for a segment that is empty, decreasing or outside [0, n].
+    ``info`` as in ``voxel_keys``."""
+    if sorted_values.dim() != 2 or start.dim() != 1:
+        raise VfnError(f"voxel_means: sorted_values must be [n,C] and start [V+1], got {tuple(sorted_values.shape)} and {tuple(start.shape)}")
+    n, channels = sorted_values.shape
+    n_voxels = start.shape[0] - 1
+    if not 1 <= channels <= voxel_limits()[1]:
+        raise VfnError(f"voxel_means: {channels} channels; one call takes 1 to {voxel_limits()[1]}")
+    if not 1 <= n_voxels <= n:
+        raise VfnError(f"voxel_means: start must have between 2 and n + 1 = {n + 1} entries, got {start.shape[0]}")
+    dev = sorted_values.device
+    ptr = _ptr(sorted_values, "sorted_values", torch.float64)
+    means = torch.empty(n_voxels, channels, dtype=torch.float64, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_voxel_means(ptr, C.c_int64(n), C.c_int32(channels), _ptr(start, "start", torch.int64), C.c_int64(n_voxels),
+                                      _ptr(means, "means", torch.float64), _ptr(info, "info", torch.int64), _stream()), "vfn_voxel_means")
+    if own:
+        voxel_check(int(info.cpu()))
+    return means
 
 
 # ------------------------------------------------------------------------------------------------

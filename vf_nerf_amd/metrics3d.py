@@ -30,8 +30,14 @@ dictionary come from ``vf_nerf_amd.refuse`` (``reconstruction_meshes``, ``metric
 ``score_mesh(..., icp_align=True)`` first aligns the pred samples to the ref samples with ``vf_nerf_amd.icp.align`` (point-to-point ICP,
 a specification of ours: not verified against Open3D or the ``evaluate_3d_reconstruction`` package).
 
-Out of scope: the voxel down-sampling of
-the ``evaluate_3d_reconstruction`` package.  Trimesh's vertex merging is ``meshops.weld``, PLY reading / writing ``vf_nerf_amd.ply``.
+``voxel_down_sample`` is the first step of the ``evaluate_3d_reconstruction`` package's protocol (vf_nerf_amd/voxel.py,
+csrc/vfn_voxel.hip): one point per occupied voxel, the mean of the voxel's points.  ``precision_recall_fscore``, ``score_mesh`` and
+``refuse.metrics_3d`` take ``voxel_size=`` and then count on the down-sampled clouds, where every occupied voxel votes once;
+``icp.align_stages`` is that protocol's staged registration.  All of it is a specification of ours that imitates Open3D's
+``voxel_down_sample`` as remembered, not verified against Open3D or the package.
+
+Out of scope: scale in ICP, and the ``evaluate_3d_reconstruction`` package's cropping, histograms and coloured error clouds.
+Trimesh's vertex merging is ``meshops.weld``, PLY reading / writing ``vf_nerf_amd.ply``.
 The random numbers are torch's, not
 numpy's: a sampled point set is distributed as trimesh's, it is not the same set.
 """
@@ -44,7 +50,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import geomargs, icp, lib, meshops
+from . import geomargs, icp, lib, meshops, voxel
 from .geomargs import LIMIT
 
 SEARCHES = ("all_pairs", "grid")
@@ -106,6 +112,31 @@ def _check_cells(cells) -> Optional[int]:
 
 def _dev_points(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
     return t.to(dev, torch.float64).contiguous()
+
+
+VoxelDownSample = voxel.VoxelDownSample
+
+
+def voxel_down_sample(points, voxel_size, normals=None, colours=None, device=None) -> VoxelDownSample:
+    """points[n,3] -> a ``VoxelDownSample``: ``points`` [V,3], the mean of the points of every occupied voxel of edge ``voxel_size``
+    (voxels in ascending (c_0, c_1, c_2), c_k = floor((p_k - origin_k) / voxel_size), origin = the bounding box's lower corner less
+    half a voxel); ``normals`` / ``colours`` ([n,3]) averaged with them as plain means, not re-normalised; ``counts`` [V],
+    ``voxel_of_point`` [n], and the host values ``origin`` and ``dims``.  A mean is the serial sum in ascending original index over
+    the count (include/vfn.h: vfn_voxel_means).  Imitates Open3D's ``voxel_down_sample`` as remembered; not verified against it.
+    ``vf_nerf_amd.voxel.down_sample`` has the details and the refusals."""
+    return voxel.down_sample(points, voxel_size, normals=normals, colours=colours, device=device)
+
+
+def _check_voxel(voxel_size) -> Optional[float]:
+    return None if voxel_size is None else voxel.check_voxel_size(voxel_size)
+
+
+def _voxel_pair(pred_points, ref_points, voxel_size: float, device=None):
+    """Both point sets on the device, each down-sampled at ``voxel_size`` in its own frame -> (pred, ref, the "voxel" entry)."""
+    p, r = _check_points(pred_points, "pred_points"), _check_points(ref_points, "ref_points")
+    dev = _device(device)
+    p, r = (voxel.down_sample_device(_dev_points(x, dev), voxel_size).points for x in (p, r))
+    return p, r, {"size": voxel_size, "pred_points": int(p.shape[0]), "ref_points": int(r.shape[0])}
 
 
 def grid_edge(extent, m: int, cells: Optional[int] = None) -> float:
@@ -339,20 +370,33 @@ def chamfer_distance(pred_mesh, ref_mesh, num_points: int = 2500000, generator: 
     return chamfer_from_points(pred_points, ref_points, device=device, search=search)
 
 
-def precision_recall_fscore(pred_points, ref_points, threshold: float, device=None, search: str = "all_pairs") -> dict:
+def precision_recall_fscore(pred_points, ref_points, threshold: float, device=None, search: str = "all_pairs", voxel_size=None) -> dict:
     """precision = the share of pred points whose nearest ref point is closer than ``threshold`` (distance < threshold), recall = the
     share of ref points whose nearest pred point is closer than ``threshold``, fscore = 2 P R / (P + R), 0 when P + R = 0.  The counts
-    are returned too (``pred_within``, ``ref_within``).  This is the plain definition on the two point sets as given; it is NOT claimed
-    equal to the external ``evaluate_3d_reconstruction`` package the reference calls, which also voxel-down-samples both clouds and
-    optionally aligns them with ICP first.  ``search`` as in ``nearest_distances``."""
+    are returned too (``pred_within``, ``ref_within``).  ``search`` as in ``nearest_distances``.
+
+    With ``voxel_size=None`` this is the plain definition on the two point sets as given: a share of POINTS, so a region with many
+    points weighs more.  With a value both sets are first replaced by their ``voxel_down_sample`` at that edge, each in its own frame,
+    so that every occupied voxel votes once, as the external ``evaluate_3d_reconstruction`` package the reference calls does before it
+    counts; the result gains "voxel": {"size", "pred_points", "ref_points"}.  That package's choice of the edge is ``threshold / 2``
+    — as remembered, not verified.  Neither form is claimed equal to that package's numbers: the down-sampling imitates Open3D's as
+    remembered, and the package's cropping is not done here."""
     threshold = _check_threshold(threshold)
-    rows = _both_directions(pred_points, ref_points, threshold, device, **_search_kw(search))
-    return _prf(rows[1], rows[0])
+    search_kw = _search_kw(search)
+    voxel_size = _check_voxel(voxel_size)
+    if voxel_size is None:
+        rows = _both_directions(pred_points, ref_points, threshold, device, **search_kw)
+        return _prf(rows[1], rows[0])
+    p, r, entry = _voxel_pair(pred_points, ref_points, voxel_size, device)
+    rows = _both_directions(p, r, threshold, p.device, **search_kw)
+    out = _prf(rows[1], rows[0])
+    out["voxel"] = entry
+    return out
 
 
 def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: float = 0.05, generator: Optional[torch.Generator] = None,
                uniforms=None, device=None, icp_align: bool = False, icp_threshold: Optional[float] = None, search: str = "all_pairs",
-               normals: bool = False) -> dict:
+               normals: bool = False, voxel_size=None) -> dict:
     """One entry of the reference's ``3d-metrics.json`` (methods.py:794-801): {"chamfer distance": {mean, median, min, max}, "precision",
     "recall", "fscore"} (plus the two counts), from ONE sampling of each mesh and ONE nearest-neighbour search per direction shared
     by both metrics.  ``uniforms`` ([num_points,3]) is used for BOTH meshes when given.
@@ -367,10 +411,22 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
     ``normals=True``: the entry gains "normal consistency": {"pred_to_ref", "ref_to_pred", "mean"} (``normal_consistency``, from the same
     samples; with ``icp_align`` the pred normals are rotated by the result's 3 x 3 block).  The two scoring searches then go through the
     grid kernel whatever ``search`` says — the all-pairs kernel has no index — and every other key is what it is without ``normals``,
-    bit for bit.  With ``normals=False`` nothing changes."""
+    bit for bit.  With ``normals=False`` nothing changes.
+
+    ``voxel_size``: both sample sets are replaced by their ``voxel_down_sample`` at that edge — after the sampling, and after the ICP
+    move when ``icp_align=True`` (the alignment itself runs on the samples as drawn, so the "icp" entry does not depend on the keyword)
+    — and chamfer distance, precision, recall and F-score are taken on the results, through ``search`` as given; the entry gains
+    "voxel": {"size", "pred_points", "ref_points"}.  Every occupied voxel then votes once, as in the external
+    ``evaluate_3d_reconstruction`` package, whose edge is ``distance_thresh / 2`` — as remembered, not verified.  Together with
+    ``normals=True`` it raises ``ValueError``: a voxel's normal for normal consistency is not defined here.  With ``voxel_size=None``
+    nothing changes: the same keys, bits and draws from the generator as without the keyword."""
     search = _check_search(search)
     if not isinstance(normals, (bool, np.bool_)):
         raise ValueError(f"normals must be a bool, got {normals!r}")
+    voxel_size = _check_voxel(voxel_size)
+    if voxel_size is not None and normals:
+        raise ValueError("voxel_size together with normals=True: a voxel's normal for normal consistency is not defined here (the mean of "
+                         "unit normals is no unit normal, and no face belongs to a voxel)")
     pv, pf = _check_mesh(pred_mesh, "pred_mesh")
     rv, rf = _check_mesh(ref_mesh, "ref_mesh")
     num_points = geomargs.positive_int(num_points, "num_points")
@@ -391,6 +447,9 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
             pred_normals = _rotate(pred_normals, aligned.transformation)
     if normals:
         rows, consistency = _both_directions_normals(pred_points, pred_normals, ref_points, ref_normals, threshold)
+    elif voxel_size is not None:
+        pred_points, ref_points, voxel_entry = _voxel_pair(pred_points, ref_points, voxel_size, pred_points.device)
+        rows = _both_directions(pred_points, ref_points, threshold, pred_points.device, **_search_kw(search))
     else:
         rows = _both_directions(pred_points, ref_points, threshold, device, **_search_kw(search))
     mean, median, mn, mx = _chamfer(rows[0], rows[1])
@@ -398,6 +457,8 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
     out.update(_prf(rows[1], rows[0]))
     if normals:
         out["normal consistency"] = consistency
+    if voxel_size is not None:
+        out["voxel"] = voxel_entry
     if aligned is not None:
         out["icp"] = {"transformation": aligned.transformation.tolist(), "fitness": aligned.fitness, "inlier_rmse": aligned.inlier_rmse,
                       "iterations": aligned.iterations}
