@@ -1142,6 +1142,54 @@ int vfn_voxel_means(const double* sorted_values, int64_t n, int32_t channels, co
                     int64_t* info, void* stream);
 
 /* =============================================================================================
+ * Connected components of a triangle mesh (csrc/vfn_cc.hip, csrc/vfn_cc_core.h; vf_nerf_amd/meshops.py: connected_components,
+ * filter_components): what a fused mesh consists of, so that its small detached pieces can be culled before it is scored.  A
+ * SPECIFICATION of ours that follows Open3D's cluster_connected_triangles and trimesh's split AS REMEMBERED: neither is available to
+ * compare against, and neither fixes a numbering of the components or an order of summation; ours does.  Labels, counts and tables
+ * are int64, the forest int32, areas float64 evaluated without contraction in the association written here, with no floating-point
+ * atomics.  The forest's intermediate states depend on the schedule; no output does.
+ *   Nodes and connectivity.  The nodes are the faces 0 .. m-1 of faces[m, 3] over n vertices.
+ *                     "edge":   two faces are connected when they share an undirected edge {a, b}, a != b, among their corner pairs
+ *                               (0,1), (1,2), (2,0).  A corner pair with a == b is no edge.  An edge shared by three or more faces
+ *                               connects all of them.
+ *                     "vertex": two faces are connected when they name a common vertex.
+ *                     A component is a class of the transitive closure.
+ *   Labels.           The ROOT of a component is its lowest face index.  Components are numbered 0 .. K-1 in ascending root;
+ *                     first_face[K] holds the roots.  face_label[m] is the number of the face's component.  vertex_label[n] is the
+ *                     LOWEST label among the faces that name the vertex (in "vertex" mode they all carry one label); -1 for a vertex
+ *                     that no face names.  face_count[K] is exact.
+ *   Areas.            area[K]: the vfn_tri_areas values of the component's faces in ascending face index, x_0 .. x_(c-1), added by
+ *                     vfn_cc_segment_sums' rule below.
+ *   The items (the caller's, torch plumbing).  "edge": the 3m corner pairs, all pairs (0,1) in face order, then all (1,2), then all
+ *                     (2,0), key = min(a, b) * n + max(a, b) (-1 where a == b), node = the face, sorted ascending by key with a
+ *                     STABLE sort.  "vertex": the incidences (vertex, face), each once, ascending by vertex then face, key = the
+ *                     vertex, node = the face.  Faces that hold one key stand next to each other: uniting neighbours unites them all.
+ *   vfn_cc_union_runs reads keys[n_items] (sorted), nodes[n_items]; updates parent[n_nodes] (int32), which the CALLER fills with the
+ *                     identity.  One lane per item i >= 1: where keys[i] == keys[i-1] >= 0, the trees of nodes[i-1] and nodes[i] are
+ *                     united — a concurrent union-find (csrc/vfn_cc_core.h): parent[x] <= x at all times; only a root is ever hooked,
+ *                     by a compare-and-swap parent[a]: a -> b with b < a both found as roots, the finds repeated when it fails; path
+ *                     halving by compare-and-swap.  After the launch two nodes are in one tree exactly when a chain of united pairs
+ *                     joins them, and every tree's root is its lowest node — whatever the schedule.  A node outside [0, n_nodes):
+ *                     info bit 2, the pair is not followed.  A parent outside [0, its node] (a forest that is not ours): info bit 2.
+ *   vfn_cc_flatten    reads parent[n_nodes] AFTER the unions (another launch), writes root[n_nodes] (int64): where v's parent chain
+ *                     ends.  A parent outside [0, its node]: info bit 2, root[v] = -1, the chain is dropped there.
+ *   vfn_cc_segment_sums  reads sorted_values[n] and start[n_segments + 1]; one WAVE of 64 lanes per segment [b, e) = [start[v], start[v + 1]):
+ *                       s_t = x_(b+t);  s_t = s_t + x_(b+t+64);  s_t = s_t + x_(b+t+128);  ...      lane t, serially, from its FIRST element
+ *                       s_t = +0.0                                                               for a lane without elements
+ *                       s_t = s_t + s_(t+32) for t < 32;  then s_t = s_t + s_(t+16) for t < 16;  then 8, 4, 2, 1;   sums[v] = s_0
+ *                     — a segment of 2 x 10^6 values is 31 250 additions deep per lane, not one lane's loop.  (A lone -0.0 comes out
+ *                     as +0.0: lane 0 adds lane 32's +0.0.)  The table is not trusted: a segment that is empty, decreasing or
+ *                     outside [0, n] gets NaN and info bit 2, and nothing is read through it.
+ * info[0] (int64, zero-filled by the caller, only OR-ed into).  Limits: 1 <= n_nodes < 2^31, 1 <= n_items < 3 * 2^31, 1 <= n < 2^31,
+ * 1 <= n_segments <= n.  Every argument check answers before any launch.
+ * ============================================================================================= */
+int vfn_cc_union_runs(const int64_t* keys, const int64_t* nodes, int64_t n_items, int32_t* parent, int64_t n_nodes, int64_t* info,
+                      void* stream);
+int vfn_cc_flatten(const int32_t* parent, int64_t n_nodes, int64_t* root, int64_t* info, void* stream);
+int vfn_cc_segment_sums(const double* sorted_values, int64_t n, const int64_t* start, int64_t n_segments, double* sums, int64_t* info,
+                        void* stream);
+
+/* =============================================================================================
  * Optimizer side of a training step over ONE flat fp32 buffer (train/vector_field_nerf_train.py:254-260:
  * torch.nn.utils.clip_grad_norm_(model.parameters(), clip); optimizer.step()).  The unique parameters — and their gradients
  * and Adam moments — are laid out contiguously, sorted into up to four REGIONS [start, end) of equal multiplicity `mult` =

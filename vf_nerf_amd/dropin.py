@@ -37,7 +37,8 @@ def _ensure_package(name: str) -> None:
 
 
 def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scalars=None, patch_mesh: bool = True,
-            patch_metrics: bool = False, patch_tsdf_mesh: bool = False, tsdf_vertex_normals=None, tsdf_sparse=None) -> None:
+            patch_metrics: bool = False, patch_tsdf_mesh: bool = False, tsdf_vertex_normals=None, tsdf_sparse=None,
+            tsdf_min_component_faces=None) -> None:
     """``patch_clip=False`` leaves ``torch.nn.utils.clip_grad_norm_`` PyTorch's own function (no process-wide replacement): a step session then
     parks its gradient in the optimizer's flat buffer with every ``param.grad`` None, the trainer's clip call finds nothing to scale, and
     ``optimizer.step()`` all-reduces (more than one rank), clips with the model's ``scheduler_config.clip_norm`` — the value the trainer
@@ -59,7 +60,14 @@ def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scal
     ``tsdf_vertex_normals`` (None: leave as is) sets ``evaluator.TSDF_VERTEX_NORMALS``: True makes ``evaluator.tsdf_mesh`` write the vertex
     normals (``meshops.vertex_normals``) into ``tsdf.ply``, as the reference's ``compute_vertex_normals()`` does; off by default.
     ``tsdf_sparse`` (None: leave as is) sets ``evaluator.TSDF_SPARSE``: True makes ``evaluator.tsdf_mesh`` fuse into the block-sparse
-    volume (``tsdf.SparseTSDFVolume``), which has no 2^31 voxel limit; off by default."""
+    volume (``tsdf.SparseTSDFVolume``), which has no 2^31 voxel limit; off by default.
+    ``tsdf_min_component_faces`` (None: leave as is) sets ``evaluator.TSDF_MIN_COMPONENT_FACES``: an integer makes ``evaluator.tsdf_mesh``
+    cull the components of the fused mesh with fewer faces (``meshops.filter_components``) before it writes ``tsdf.ply``; the module's
+    default is None, the mesh as fused."""
+    if tsdf_min_component_faces is not None:
+        if isinstance(tsdf_min_component_faces, bool) or not isinstance(tsdf_min_component_faces, int) or tsdf_min_component_faces < 0:
+            raise ValueError(f"tsdf_min_component_faces must be None or an integer >= 0, got {tsdf_min_component_faces!r}")
+        evaluator.TSDF_MIN_COMPONENT_FACES = tsdf_min_component_faces
     if tsdf_vertex_normals is not None:
         evaluator.TSDF_VERTEX_NORMALS = bool(tsdf_vertex_normals)
     if tsdf_sparse is not None:

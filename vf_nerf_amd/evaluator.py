@@ -37,6 +37,9 @@ TSDF_VERTEX_NORMALS = False
 # tsdf_mesh fuses into the block-sparse volume (tsdf.SparseTSDFVolume: no 2^31 voxel limit on the box of the depths); False: the dense
 # volume.  dropin.install(tsdf_sparse=...) sets it.
 TSDF_SPARSE = False
+# tsdf_mesh culls the components of the fused mesh with fewer faces (meshops.filter_components, edge connectivity) before it writes
+# tsdf.ply; None: the mesh as fused.  dropin.install(tsdf_min_component_faces=...) sets it.
+TSDF_MIN_COMPONENT_FACES = None
 
 
 @torch.no_grad()
@@ -201,7 +204,9 @@ def tsdf_mesh(eval_path: str, dataset_config) -> None:
     ``tsdf-mesh/tsdf.ply`` (``ply.write_ply``: binary, float vertices, uchar colours).  The reference calls ``compute_vertex_normals()``
     first: with the module switch ``TSDF_VERTEX_NORMALS`` set the file also holds ``meshops.vertex_normals`` of the fused mesh (the
     extraction already merges its vertices: no weld); by default it does not.  With ``TSDF_SPARSE`` set the fusion runs in the
-    block-sparse volume, which a scene spanning more than 2^31 voxels does not stop.  Installed by ``dropin.install(patch_tsdf_mesh=True)``."""
+    block-sparse volume, which a scene spanning more than 2^31 voxels does not stop.  With ``TSDF_MIN_COMPONENT_FACES`` set the components
+    of the fused mesh with fewer faces are culled (``meshops.filter_components``) before the file is written; colours, and the normals
+    of the fused mesh if asked for, follow the vertices that stay.  Installed by ``dropin.install(patch_tsdf_mesh=True)``."""
     from PIL import Image
     from . import meshops, ply, tsdf
     dataset_dict = importlib.import_module("datasets.normal_datasets").dataset_dict
@@ -224,7 +229,14 @@ def tsdf_mesh(eval_path: str, dataset_config) -> None:
                                                    **({"sparse": True} if TSDF_SPARSE else {}))
     mesh_path = os.path.join(eval_path, "tsdf-mesh")
     os.makedirs(mesh_path, exist_ok=True)
-    if TSDF_VERTEX_NORMALS:
+    if TSDF_MIN_COMPONENT_FACES is not None:
+        normals = meshops.vertex_normals((vertices, faces)) if TSDF_VERTEX_NORMALS else None
+        vertices, faces, _, inverse = meshops.filter_components((vertices, faces), min_faces=TSDF_MIN_COMPONENT_FACES)
+        stays = (inverse >= 0).to(colours.device)
+        colours = colours[stays]
+        ply.write_ply(os.path.join(mesh_path, "tsdf.ply"), vertices, faces, colours,
+                      **({} if normals is None else {"normals": normals[stays.to(normals.device)]}))
+    elif TSDF_VERTEX_NORMALS:
         ply.write_ply(os.path.join(mesh_path, "tsdf.ply"), vertices, faces, colours, normals=meshops.vertex_normals((vertices, faces)))
     else:
         ply.write_ply(os.path.join(mesh_path, "tsdf.ply"), vertices, faces, colours)

@@ -52,6 +52,7 @@ EXPORTS = (
     "vfn_image_quantize8", "vfn_image_scores_workspace_bytes", "vfn_image_scores", "vfn_image_abs_err",
     "vfn_face_normals", "vfn_vertex_normals", "vfn_normal_dots",
     "vfn_voxel_keys", "vfn_voxel_means",
+    "vfn_cc_union_runs", "vfn_cc_flatten", "vfn_cc_segment_sums",
 )
 
 
@@ -1408,18 +1409,26 @@ def nn_check(status: int) -> None:
         raise VfnError("nearest-neighbour search: a non-finite coordinate in the queries or the targets")
 
 
-def tri_areas(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
-    """vertices[V,3] float64, faces[F,3] int64 -> areas[F].  A face index outside [0, V) or a non-finite area raises."""
-    nv, nf = vertices.shape[0], faces.shape[0]
-    areas = torch.empty(nf, dtype=torch.float64, device=faces.device)
-    info = torch.zeros(1, dtype=torch.int64, device=faces.device)
-    _check(load().vfn_tri_areas(_ptr(vertices, "vertices", torch.float64) if nv else None, C.c_int64(nv), _ptr(faces, "faces", torch.int64),
-                                C.c_int64(nf), _ptr(areas, "areas", torch.float64), _ptr(info, "info", torch.int64), _stream()), "vfn_tri_areas")
-    status = int(info.cpu())
+def tri_areas_check(status: int, nv: int) -> None:
     if status & GEOM_STATUS_INDEX:
         raise VfnError(f"triangle areas: a face index lies outside [0, {nv})")
     if status & GEOM_STATUS_NONFINITE:
         raise VfnError("triangle areas: a non-finite area (non-finite or overflowing vertex coordinates)")
+
+
+def tri_areas(vertices: torch.Tensor, faces: torch.Tensor, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vertices[V,3] float64, faces[F,3] int64 -> areas[F].  A face index outside [0, V) or a non-finite area raises — or, with the
+    caller's zero-filled ``info`` (int64 [1]), sets its bits (``tri_areas_check``) and nothing is read here."""
+    nv, nf = vertices.shape[0], faces.shape[0]
+    areas = torch.empty(nf, dtype=torch.float64, device=faces.device)
+    own = info is None
+    if own:
+        info = torch.zeros(1, dtype=torch.int64, device=faces.device)
+    _check(load().vfn_tri_areas(_ptr(vertices, "vertices", torch.float64) if nv else None, C.c_int64(nv), _ptr(faces, "faces", torch.int64),
+                                C.c_int64(nf), _ptr(areas, "areas", torch.float64), _ptr(info, "info", torch.int64), _stream()), "vfn_tri_areas")
+    if not own:
+        return areas
+    tri_areas_check(int(info.cpu()), nv)
     return areas
 
 
@@ -2073,6 +2082,72 @@ def voxel_means(sorted_values: torch.Tensor, start: torch.Tensor, info: Optional
     if own:
         voxel_check(int(info.cpu()))
     return means
+
+
+# ------------------------------------------------------------------------------------------------
+# connected components (csrc/vfn_cc.hip; vf_nerf_amd/meshops.py is the public surface).  Keys, nodes, tables int64, the forest int32,
+# values float64; contiguous, on one device.
+# ------------------------------------------------------------------------------------------------
+def cc_check(status: int, what: str = "connected components") -> None:
+    if status & GEOM_STATUS_INDEX:
+        raise VfnError(f"{what}: a node, a parent or a segment lies outside its range")
+
+
+def cc_union_runs(keys: torch.Tensor, nodes: torch.Tensor, parent: torch.Tensor, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sorted keys[k] with their nodes[k] (int64) and the forest parent[n] (int32, the caller's identity) -> parent, updated in place:
+    where keys[i] == keys[i-1] >= 0 the trees of nodes[i-1] and nodes[i] are one (include/vfn.h: vfn_cc_union_runs).  A node outside
+    [0, n) raises — or, with the caller's zero-filled ``info`` (int64 [1]), sets its bits (``cc_check``)."""
+    if keys.dim() != 1 or nodes.dim() != 1 or parent.dim() != 1 or keys.shape[0] != nodes.shape[0]:
+        raise VfnError(f"cc_union_runs: keys and nodes must be [k] and parent [n], got {tuple(keys.shape)}, {tuple(nodes.shape)} and "
+                       f"{tuple(parent.shape)}")
+    if keys.shape[0] < 1 or parent.shape[0] < 1:
+        raise VfnError(f"cc_union_runs: {keys.shape[0]} items on {parent.shape[0]} nodes; both counts must be at least 1")
+    dev = parent.device
+    args = (_ptr(keys, "keys", torch.int64), _ptr(nodes, "nodes", torch.int64), C.c_int64(keys.shape[0]), _ptr(parent, "parent", torch.int32),
+            C.c_int64(parent.shape[0]))
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_cc_union_runs(*args, _ptr(info, "info", torch.int64), _stream()), "vfn_cc_union_runs")
+    if own:
+        cc_check(int(info.cpu()))
+    return parent
+
+
+def cc_flatten(parent: torch.Tensor, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The forest parent[n] (int32) after the unions -> root[n] int64: where every node's chain ends (include/vfn.h: vfn_cc_flatten); -1
+    where a parent leaves [0, its node].  ``info`` as in ``cc_union_runs``."""
+    if parent.dim() != 1 or parent.shape[0] < 1:
+        raise VfnError(f"cc_flatten: parent must be [n] with n >= 1, got {tuple(parent.shape)}")
+    dev = parent.device
+    ptr = _ptr(parent, "parent", torch.int32)
+    root = torch.empty(parent.shape[0], dtype=torch.int64, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_cc_flatten(ptr, C.c_int64(parent.shape[0]), _ptr(root, "root", torch.int64), _ptr(info, "info", torch.int64), _stream()),
+               "vfn_cc_flatten")
+    if own:
+        cc_check(int(info.cpu()))
+    return root
+
+
+def cc_segment_sums(sorted_values: torch.Tensor, start: torch.Tensor, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sorted_values[n] float64, start[S+1] int64 -> sums[S]: every segment added by one wave in the fixed order of include/vfn.h
+    (vfn_cc_segment_sums); NaN for a segment that is empty, decreasing or outside [0, n].  ``info`` as in ``cc_union_runs``."""
+    if sorted_values.dim() != 1 or start.dim() != 1:
+        raise VfnError(f"cc_segment_sums: sorted_values must be [n] and start [S+1], got {tuple(sorted_values.shape)} and {tuple(start.shape)}")
+    n, segments = sorted_values.shape[0], start.shape[0] - 1
+    if not 1 <= segments <= n:
+        raise VfnError(f"cc_segment_sums: start must have between 2 and n + 1 = {n + 1} entries, got {start.shape[0]}")
+    dev = sorted_values.device
+    ptr = _ptr(sorted_values, "sorted_values", torch.float64)
+    sums = torch.empty(segments, dtype=torch.float64, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_cc_segment_sums(ptr, C.c_int64(n), _ptr(start, "start", torch.int64), C.c_int64(segments),
+                                          _ptr(sums, "sums", torch.float64), _ptr(info, "info", torch.int64), _stream()), "vfn_cc_segment_sums")
+    if own:
+        cc_check(int(info.cpu()))
+    return sums
 
 
 # ------------------------------------------------------------------------------------------------

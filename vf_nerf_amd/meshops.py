@@ -12,15 +12,26 @@ when it loads a mesh (methods.py:305).
   lowest index, unreferenced vertices dropped, faces remapped.  A specification of ours that follows trimesh's ``merge_vertices`` AS
   REMEMBERED — not verified against trimesh.  The merge is ``lib.mesh_dedup``'s (csrc/vfn_mesh.hip): no new hash table.
 
+* ``connected_components`` — what a mesh consists of (csrc/vfn_cc.hip, include/vfn.h): the faces are the nodes, two faces are connected
+  when they share an edge (``connectivity="edge"``) or a vertex (``"vertex"``); a concurrent union-find on the device over the sorted
+  half-edge keys (the vertex incidences), components numbered in ascending lowest face, with exact face counts and areas added in
+  a fixed order.  A specification of ours that follows Open3D's ``cluster_connected_triangles`` and trimesh's ``split`` AS REMEMBERED —
+  not verified against either; neither fixes a numbering or an order of summation.  tests/cc_restatement.py restates it in NumPy and
+  the device is held to it bit for bit.
+* ``filter_components`` — the mesh without its small pieces ("floaters"): by face count, by area, or the k largest.
+* ``remove_degenerate_faces`` / ``remove_duplicate_faces`` / ``clean`` — faces that name a vertex twice (or have no area), faces that
+  repeat an earlier face's vertex triple, and the four steps in one call.  Torch plumbing, no kernel of their own.
+
 Inputs are numpy arrays or torch tensors on any device; a mesh is a ``mesh.Mesh`` (its ``vertices_scaled`` are used) or a
 ``(vertices, faces)`` pair.  Outputs are device tensors.  No CPU fallback: ``lib.VfnError`` when no device is visible.  A face index
 outside [0, n) is refused on the host (``ValueError``) before anything is launched.
 
-Out of scope: angle-weighted or uniform vertex normals, orienting a mesh, removing degenerate or duplicate faces.
+Out of scope: angle-weighted or uniform vertex normals, orienting a mesh, filling holes, simplification.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+import math
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -28,6 +39,8 @@ import torch
 from . import geomargs, lib
 
 WELD_DIGITS = 8                    # trimesh's merge_vertices default (digits_vertex), as remembered
+CONNECTIVITIES = ("edge", "vertex")
+SIZES = ("faces", "area")          # what ``keep_largest`` ranks by
 
 
 def _check_indices(f: torch.Tensor, n: int, name: str) -> None:
@@ -61,16 +74,22 @@ def face_normals(mesh, normalise: bool = True, device=None) -> torch.Tensor:
     return lib.face_normals(v, f, bool(normalise))
 
 
-def _vertex_faces(faces: torch.Tensor, n_vertices: int) -> Tuple[torch.Tensor, torch.Tensor]:
+def _incidences(faces: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """faces[m,3], m >= 1 -> (vertex, face) of every incidence, each once, ascending by vertex then by face."""
     m = faces.shape[0]
-    row_start = torch.zeros(n_vertices + 1, dtype=torch.int64, device=faces.device)
-    if m == 0:
-        return row_start, torch.empty(0, dtype=torch.int64, device=faces.device)
     face = torch.arange(m, dtype=torch.int64, device=faces.device)
     keys = torch.unique(torch.cat([faces[:, 0] * m + face, faces[:, 1] * m + face, faces[:, 2] * m + face]))      # sorted: by vertex, then by face
     rows = torch.div(keys, m, rounding_mode="floor")
+    return rows, (keys - rows * m).contiguous()
+
+
+def _vertex_faces(faces: torch.Tensor, n_vertices: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    row_start = torch.zeros(n_vertices + 1, dtype=torch.int64, device=faces.device)
+    if faces.shape[0] == 0:
+        return row_start, torch.empty(0, dtype=torch.int64, device=faces.device)
+    rows, incident = _incidences(faces)
     row_start[1:] = torch.cumsum(torch.bincount(rows, minlength=n_vertices), dim=0)
-    return row_start, (keys - rows * m).contiguous()
+    return row_start, incident
 
 
 def vertex_faces(faces, n_vertices: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -129,3 +148,217 @@ def weld(mesh, digits: Optional[int] = WELD_DIGITS, device=None) -> Tuple[torch.
         first = torch.full((count,), referenced.shape[0], dtype=torch.int64, device=dev).scatter_reduce(0, ids, position, reduce="amin")
         inverse[referenced] = ids
         return vr[first].contiguous(), inverse[f].contiguous(), inverse
+
+
+# ------------------------------------------------------------------------------------------------
+# connected components (csrc/vfn_cc.hip, include/vfn.h)
+# ------------------------------------------------------------------------------------------------
+class Components(NamedTuple):
+    """What ``connected_components`` returns: device tensors, except ``n_components``."""
+    face_label: torch.Tensor                   # [m] int64: the component of every face, components numbered in ascending lowest face
+    vertex_label: torch.Tensor                 # [n] int64: the lowest label among the vertex's faces; -1 for a vertex no face names
+    n_components: int                          # K (host)
+    face_count: torch.Tensor                   # [K] int64, exact
+    area: Optional[torch.Tensor]               # [K] float64 in the fixed order of include/vfn.h; None with ``areas=False``
+    first_face: torch.Tensor                   # [K] int64: every component's lowest face index, ascending
+
+
+def _check_connectivity(connectivity) -> str:
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError(f"connectivity must be one of {CONNECTIVITIES}, got {connectivity!r}")
+    return connectivity
+
+
+def _check_count(x, name: str, least: int) -> Optional[int]:
+    if x is None:
+        return None
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not least <= int(x) < geomargs.LIMIT:
+        raise ValueError(f"{name} must be None or an integer in [{least}, 2^31), got {x!r}")
+    return int(x)
+
+
+def _check_area(x, name: str) -> Optional[float]:
+    if x is None:
+        return None
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not math.isfinite(float(x)) or float(x) < 0:
+        raise ValueError(f"{name} must be None or a finite number >= 0, got {x!r}")
+    return float(x)
+
+
+def _check_filter(min_faces, min_area, keep_largest, by, connectivity):
+    if by not in SIZES:
+        raise ValueError(f"by must be one of {SIZES}, got {by!r}")
+    return (_check_count(min_faces, "min_faces", 0), _check_area(min_area, "min_area"), _check_count(keep_largest, "keep_largest", 1), by,
+            _check_connectivity(connectivity))
+
+
+def component_items(faces: torch.Tensor, n_vertices: int, connectivity: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Device faces[m,3] (m >= 1, checked) -> (keys, nodes) as ``lib.cc_union_runs`` takes them, int64: the faces that hold one key stand
+    next to each other.  "edge": the 3m corner pairs — all (0,1), then all (1,2), then all (2,0) — with key = min * n + max (-1 where
+    both ends are one vertex: no edge), sorted stably by torch.  "vertex": the rows of ``_vertex_faces``, key = the vertex."""
+    if connectivity == "vertex":
+        return _incidences(faces)
+    m = faces.shape[0]
+    a = torch.cat((faces[:, 0], faces[:, 1], faces[:, 2]))
+    b = torch.cat((faces[:, 1], faces[:, 2], faces[:, 0]))
+    keys = torch.where(a == b, torch.full_like(a, -1), torch.minimum(a, b) * n_vertices + torch.maximum(a, b))
+    keys, order = torch.sort(keys, stable=True)
+    return keys, torch.arange(m, dtype=torch.int64, device=faces.device).repeat(3)[order].contiguous()
+
+
+def _components(v: torch.Tensor, f: torch.Tensor, connectivity: str, areas: bool) -> Components:
+    """Device vertices / faces, checked -> ``Components``.  Two host reads: the number of components (inside ``torch.unique``) and the
+    four status words, together."""
+    dev, n, m = v.device, v.shape[0], f.shape[0]
+    with torch.cuda.device(dev):
+        if m == 0:
+            none = torch.empty(0, dtype=torch.int64, device=dev)
+            return Components(none, torch.full((n,), -1, dtype=torch.int64, device=dev), 0, none.clone(),
+                              torch.empty(0, dtype=torch.float64, device=dev) if areas else None, none.clone())
+        info = torch.zeros(4, dtype=torch.int64, device=dev)          # a word per stage: the first stage's complaint names the cause
+        keys, nodes = component_items(f, n, connectivity)
+        parent = torch.arange(m, dtype=torch.int32, device=dev)
+        lib.cc_union_runs(keys, nodes, parent, info=info[0:1])
+        root = lib.cc_flatten(parent, info=info[1:2])
+        first_face, face_label = torch.unique(root, return_inverse=True)          # ascending root: the numbering.  The read for K.
+        k = int(first_face.shape[0])
+        vertex_label = torch.full((n,), k, dtype=torch.int64, device=dev).scatter_reduce(0, f.reshape(-1), face_label.repeat_interleave(3),
+                                                                                        reduce="amin")
+        vertex_label = torch.where(vertex_label == k, torch.full_like(vertex_label, -1), vertex_label)
+        face_count = torch.bincount(face_label, minlength=k)
+        area = None
+        if areas:
+            per_face = lib.tri_areas(v, f, info=info[2:3])
+            order = torch.sort(face_label, stable=True)[1]          # a component's faces in ascending face index
+            start = torch.cat((torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(face_count, dim=0))).contiguous()
+            area = lib.cc_segment_sums(per_face[order].contiguous(), start, info=info[3:4])
+        unions, chains, triangles, sums = (int(x) for x in info.cpu())          # the one read of the status words
+        lib.cc_check(unions, "connected components (unions)")
+        lib.cc_check(chains, "connected components (flatten)")
+        lib.tri_areas_check(triangles, n)
+        lib.cc_check(sums, "connected components (areas)")
+    return Components(face_label, vertex_label, k, face_count, area, first_face)
+
+
+def connected_components(mesh, connectivity: str = "edge", areas: bool = True, device=None) -> Components:
+    """-> ``Components`` on the device.  The nodes are the faces; with ``connectivity="edge"`` two faces are connected when they share an
+    undirected edge {a, b}, a != b (a corner pair that names one vertex twice is no edge; an edge shared by three or more faces
+    connects them all), with ``"vertex"`` when they name a common vertex.  The root of a component is its lowest face index and the
+    components are numbered 0..K-1 in ascending root: ``first_face`` holds the roots, ``face_label`` every face's number,
+    ``vertex_label`` the lowest label among a vertex's faces (-1: no face names it), ``face_count`` the exact counts and ``area`` the
+    ``vfn_tri_areas`` values of a component's faces in ascending face index, added in the fixed order of include/vfn.h
+    (vfn_cc_segment_sums: 64 strided serial sums, then a fold by halves).  No output depends on the schedule of the union-find.
+    Follows Open3D's ``cluster_connected_triangles`` and trimesh's ``split`` as remembered; not verified against either."""
+    connectivity = _check_connectivity(connectivity)
+    if not isinstance(areas, (bool, np.bool_)):
+        raise ValueError(f"areas must be a bool, got {areas!r}")
+    v, f = _mesh_on_device(mesh, device, "mesh", "connected components")
+    return _components(v, f, connectivity, bool(areas))
+
+
+def _keep_mask(c: Components, min_faces, min_area, keep_largest, by) -> torch.Tensor:
+    """-> keep[K] bool: count >= min_faces, area >= min_area, and among the ``keep_largest`` greatest by ``by`` (ties to the lower label:
+    a stable descending sort)."""
+    keep = torch.ones(c.n_components, dtype=torch.bool, device=c.face_label.device)
+    if min_faces is not None:
+        keep &= c.face_count >= min_faces
+    if min_area is not None:
+        keep &= c.area >= min_area
+    if keep_largest is not None and c.n_components:
+        size = c.face_count if by == "faces" else c.area
+        top = torch.zeros_like(keep)
+        top[torch.sort(size, descending=True, stable=True)[1][:keep_largest]] = True
+        keep &= top
+    return keep
+
+
+def _select_faces(v: torch.Tensor, f: torch.Tensor, face_keep: torch.Tensor):
+    """The faces of the mask in their order, the vertices they name in their order and bits -> (vertices, faces, kept_faces, inverse)."""
+    kept_faces = torch.nonzero(face_keep).reshape(-1)
+    kept = f[kept_faces]
+    used = torch.zeros(v.shape[0], dtype=torch.bool, device=v.device)
+    used[kept.reshape(-1)] = True
+    inverse = torch.where(used, torch.cumsum(used, dim=0) - 1, torch.full((v.shape[0],), -1, dtype=torch.int64, device=v.device))
+    return v[used].contiguous(), inverse[kept].reshape(-1, 3).contiguous(), kept_faces, inverse
+
+
+def _filter(v, f, min_faces, min_area, keep_largest, by, connectivity, areas: bool = False):
+    """The checked arguments on device tensors -> (``filter_components``' tuple, the ``Components``, keep[K])."""
+    c = _components(v, f, connectivity, areas or min_area is not None or (keep_largest is not None and by == "area"))
+    keep = _keep_mask(c, min_faces, min_area, keep_largest, by)
+    with torch.cuda.device(v.device):
+        return _select_faces(v, f, keep[c.face_label]), c, keep
+
+
+def filter_components(mesh, min_faces=None, min_area=None, keep_largest=None, by: str = "faces", connectivity: str = "edge", device=None):
+    """-> (vertices float64 [V',3], faces int64 [m',3], kept_faces int64 [m'], inverse int64 [n]) on the device: the mesh without the
+    components that fail a criterion.  A component stays if its face count is >= ``min_faces`` and its area is >= ``min_area``; with
+    ``keep_largest=k`` it must also be among the k greatest of ALL components by ``by`` ("faces" or "area"), ties going to the lower
+    label.  The faces that stay keep their order, ``kept_faces`` names them in the input; vertices that no remaining face names are
+    dropped, the others keep their order and bits; ``inverse`` maps every input vertex to its output vertex or -1, as ``weld``'s —
+    colours and normals follow by indexing with ``inverse >= 0``.  With every criterion None: the mesh less its unreferenced vertices.
+    Components are ``connected_components``' (its caveats apply)."""
+    min_faces, min_area, keep_largest, by, connectivity = _check_filter(min_faces, min_area, keep_largest, by, connectivity)
+    v, f = _mesh_on_device(mesh, device, "mesh", "component filtering")
+    return _filter(v, f, min_faces, min_area, keep_largest, by, connectivity)[0]
+
+
+def remove_degenerate_faces(mesh, zero_area: bool = False, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (faces int64 [m',3], kept_faces int64 [m']) on the device: without the faces that name a vertex twice and, with
+    ``zero_area=True``, without those whose ``face_normals(normalise=False)`` is (0, 0, 0).  The others keep their order."""
+    if not isinstance(zero_area, (bool, np.bool_)):
+        raise ValueError(f"zero_area must be a bool, got {zero_area!r}")
+    v, f = _mesh_on_device(mesh, device, "mesh", "removing degenerate faces")
+    with torch.cuda.device(v.device):
+        bad = (f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 2] == f[:, 0])
+        if zero_area and f.shape[0]:
+            bad |= (lib.face_normals(v, f, False) == 0).all(dim=1)
+        kept = torch.nonzero(~bad).reshape(-1)
+        return f[kept].contiguous(), kept
+
+
+def remove_duplicate_faces(mesh, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (faces int64 [m',3], kept_faces int64 [m']) on the device: of the faces with one sorted vertex triple the lowest face index
+    stays, whatever the winding.  The others keep their order."""
+    v, f = _mesh_on_device(mesh, device, "mesh", "removing duplicate faces")
+    with torch.cuda.device(v.device):
+        if f.shape[0] == 0:
+            return f, torch.empty(0, dtype=torch.int64, device=v.device)
+        _, triple = torch.unique(torch.sort(f, dim=1)[0], dim=0, return_inverse=True)
+        position = torch.arange(f.shape[0], dtype=torch.int64, device=v.device)
+        first = torch.full((int(triple.max()) + 1,), f.shape[0], dtype=torch.int64, device=v.device).scatter_reduce(0, triple, position, reduce="amin")
+        kept = torch.sort(first)[0]
+        return f[kept].contiguous(), kept
+
+
+def clean(mesh, weld_digits=None, degenerate: bool = True, duplicates: bool = True, device=None, **filter_args):
+    """``weld`` at ``weld_digits`` (None: no welding), ``remove_degenerate_faces``, ``remove_duplicate_faces``, then ``filter_components``
+    with ``filter_args`` -> its tuple (vertices, faces, kept_faces, inverse): ``kept_faces`` names faces of the INPUT, ``inverse`` maps
+    the INPUT's vertices (after a weld several of them share an output vertex)."""
+    weld_digits = _check_digits(weld_digits)
+    for name, flag in (("degenerate", degenerate), ("duplicates", duplicates)):
+        if not isinstance(flag, (bool, np.bool_)):
+            raise ValueError(f"{name} must be a bool, got {flag!r}")
+    unknown = set(filter_args) - {"min_faces", "min_area", "keep_largest", "by", "connectivity"}
+    if unknown:
+        raise ValueError(f"clean: unknown arguments {sorted(unknown)}")
+    checked = _check_filter(filter_args.get("min_faces"), filter_args.get("min_area"), filter_args.get("keep_largest"),
+                            filter_args.get("by", "faces"), filter_args.get("connectivity", "edge"))
+    v, f = _mesh_on_device(mesh, device, "mesh", "mesh cleaning")
+    with torch.cuda.device(v.device):
+        first = None
+        if weld_digits is not None:
+            v, f, first = weld((v, f), weld_digits)
+        kept = torch.arange(f.shape[0], dtype=torch.int64, device=v.device)
+        if degenerate:
+            f, sub = remove_degenerate_faces((v, f))
+            kept = kept[sub]
+        if duplicates:
+            f, sub = remove_duplicate_faces((v, f))
+            kept = kept[sub]
+        (vertices, faces, sub, inverse), _, _ = _filter(v, f, *checked)
+        if first is not None and inverse.shape[0] == 0:
+            inverse = torch.full_like(first, -1)
+        elif first is not None:
+            inverse = torch.where(first >= 0, inverse[first.clamp(min=0)], torch.full_like(first, -1))
+        return vertices, faces, kept[sub], inverse

@@ -36,6 +36,9 @@ csrc/vfn_voxel.hip): one point per occupied voxel, the mean of the voxel's point
 ``icp.align_stages`` is that protocol's staged registration.  All of it is a specification of ours that imitates Open3D's
 ``voxel_down_sample`` as remembered, not verified against Open3D or the package.
 
+``score_mesh(..., min_component_faces=, keep_largest=)`` first culls the small detached pieces of the pred mesh
+(``meshops.filter_components``, csrc/vfn_cc.hip: connected components by shared edges), so that floaters draw no samples.
+
 Out of scope: scale in ICP, and the ``evaluate_3d_reconstruction`` package's cropping, histograms and coloured error clouds.
 Trimesh's vertex merging is ``meshops.weld``, PLY reading / writing ``vf_nerf_amd.ply``.
 The random numbers are torch's, not
@@ -137,6 +140,26 @@ def _voxel_pair(pred_points, ref_points, voxel_size: float, device=None):
     dev = _device(device)
     p, r = (voxel.down_sample_device(_dev_points(x, dev), voxel_size).points for x in (p, r))
     return p, r, {"size": voxel_size, "pred_points": int(p.shape[0]), "ref_points": int(r.shape[0])}
+
+
+def _check_components(min_component_faces, keep_largest) -> Optional[dict]:
+    """The two culling keywords of ``score_mesh``, checked -> the keywords of ``_cull_components``, or None when both are None."""
+    min_faces = meshops._check_count(min_component_faces, "min_component_faces", 0)
+    keep_largest = meshops._check_count(keep_largest, "keep_largest", 1)
+    return None if min_faces is None and keep_largest is None else {"min_faces": min_faces, "keep_largest": keep_largest}
+
+
+def _cull_components(vertices: torch.Tensor, faces: torch.Tensor, min_faces, keep_largest, device=None):
+    """A checked mesh where it is -> (vertices, faces, the "components" entry): ``meshops.filter_components`` by edge connectivity."""
+    v, f = meshops._mesh_on_device((vertices, faces), device, "pred_mesh", "mesh scoring")
+    (kept_vertices, kept_faces, kept_index, _), c, keep = meshops._filter(v, f, min_faces, None, keep_largest, "faces", "edge", areas=True)
+    if kept_faces.shape[0] < 1:
+        raise ValueError(f"pred_mesh: none of its {c.n_components} components is left after the culling (min_component_faces={min_faces!r}, "
+                         f"keep_largest={keep_largest!r})")
+    removed = c.area[~keep].cpu().tolist()
+    entry = {"connectivity": "edge", "found": c.n_components, "kept": c.n_components - len(removed),
+             "faces_removed": int(f.shape[0] - kept_faces.shape[0]), "area_removed": math.fsum(removed)}
+    return kept_vertices, kept_faces, entry
 
 
 def grid_edge(extent, m: int, cells: Optional[int] = None) -> float:
@@ -396,7 +419,7 @@ def precision_recall_fscore(pred_points, ref_points, threshold: float, device=No
 
 def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: float = 0.05, generator: Optional[torch.Generator] = None,
                uniforms=None, device=None, icp_align: bool = False, icp_threshold: Optional[float] = None, search: str = "all_pairs",
-               normals: bool = False, voxel_size=None) -> dict:
+               normals: bool = False, voxel_size=None, min_component_faces=None, keep_largest=None) -> dict:
     """One entry of the reference's ``3d-metrics.json`` (methods.py:794-801): {"chamfer distance": {mean, median, min, max}, "precision",
     "recall", "fscore"} (plus the two counts), from ONE sampling of each mesh and ONE nearest-neighbour search per direction shared
     by both metrics.  ``uniforms`` ([num_points,3]) is used for BOTH meshes when given.
@@ -419,7 +442,13 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
     "voxel": {"size", "pred_points", "ref_points"}.  Every occupied voxel then votes once, as in the external
     ``evaluate_3d_reconstruction`` package, whose edge is ``distance_thresh / 2`` — as remembered, not verified.  Together with
     ``normals=True`` it raises ``ValueError``: a voxel's normal for normal consistency is not defined here.  With ``voxel_size=None``
-    nothing changes: the same keys, bits and draws from the generator as without the keyword."""
+    nothing changes: the same keys, bits and draws from the generator as without the keyword.
+
+    ``min_component_faces`` / ``keep_largest``: ``pred_mesh`` alone is first replaced by its ``meshops.filter_components`` (edge
+    connectivity; ``min_faces=min_component_faces``, ``keep_largest`` ranked by faces) — before the sampling, so that detached pieces of
+    a fused mesh ("floaters") draw no samples — and the entry gains "components": {"connectivity", "found", "kept", "faces_removed",
+    "area_removed"} (``area_removed``: the correctly rounded sum of the removed components' areas).  ``ValueError`` if nothing is left.
+    With both None nothing changes: the same keys, bits and draws from the generator as without the keywords."""
     search = _check_search(search)
     if not isinstance(normals, (bool, np.bool_)):
         raise ValueError(f"normals must be a bool, got {normals!r}")
@@ -427,6 +456,7 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
     if voxel_size is not None and normals:
         raise ValueError("voxel_size together with normals=True: a voxel's normal for normal consistency is not defined here (the mean of "
                          "unit normals is no unit normal, and no face belongs to a voxel)")
+    components_kw = _check_components(min_component_faces, keep_largest)
     pv, pf = _check_mesh(pred_mesh, "pred_mesh")
     rv, rf = _check_mesh(ref_mesh, "ref_mesh")
     num_points = geomargs.positive_int(num_points, "num_points")
@@ -435,6 +465,8 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
         raise ValueError(f"icp_align must be a bool, got {icp_align!r}")
     if icp_align:
         icp_radius = icp._check_radius(threshold if icp_threshold is None else icp_threshold, "icp_threshold")
+    if components_kw is not None:
+        pv, pf, components_entry = _cull_components(pv, pf, device=device, **components_kw)
     pred_points, pred_face = sample_surface(pv, pf, num_points, generator=generator, uniforms=uniforms, device=device)
     ref_points, ref_face = sample_surface(rv, rf, num_points, generator=generator, uniforms=uniforms, device=device)
     if normals:
@@ -459,6 +491,8 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
         out["normal consistency"] = consistency
     if voxel_size is not None:
         out["voxel"] = voxel_entry
+    if components_kw is not None:
+        out["components"] = components_entry
     if aligned is not None:
         out["icp"] = {"transformation": aligned.transformation.tolist(), "fitness": aligned.fitness, "inlier_rmse": aligned.inlier_rmse,
                       "iterations": aligned.iterations}

@@ -123,20 +123,24 @@ def reconstruction_meshes(tsdf_mesh, intrinsics, poses, height: int, width: int,
 def metrics_3d(tsdf_mesh, gt_mesh, intrinsics, poses, height: int, width: int, num_points: int = 1000000, distance_thresh: float = 0.01,
                generator: Optional[torch.Generator] = None, uniforms=None, iterations: int = ITERATIONS, lam: float = LAM,
                icp_align: bool = False, icp_threshold: Optional[float] = None, search: str = "all_pairs", normals: bool = False, voxel_size=None,
-               **refuse_args) -> Dict[str, dict]:
+               min_component_faces=None, keep_largest=None, **refuse_args) -> Dict[str, dict]:
     """The dictionary the reference writes to ``3d-metrics.json`` (methods.py:732-741): keys ``tsdf``, ``refused_tsdf``,
     ``tsdf_smoothed``, ``refused_tsdf_smoothed``, each ``metrics3d.score_mesh(mesh, gt_mesh)`` — {"chamfer distance": {mean, median,
     min, max}, "precision", "recall", "fscore", ...} — scored in that order with the one ``generator`` (or the same ``uniforms``).  ``icp_align`` / ``icp_threshold`` go to
     ``metrics3d.score_mesh`` (every entry then has an "icp" key), and so does ``search`` ("all_pairs" or "grid": the eight searches
     through the grid kernel, the same dictionary to the bit), ``normals`` (True: every entry gains "normal consistency") and
-    ``voxel_size`` (a value: every entry is scored on the voxel-down-sampled clouds and gains "voxel"; None changes nothing)."""
+    ``voxel_size`` (a value: every entry is scored on the voxel-down-sampled clouds and gains "voxel"; None changes nothing).
+    ``min_component_faces`` / ``keep_largest`` go there too (a value: every one of the four meshes is scored without its small detached
+    pieces, ``meshops.filter_components``, and every entry gains "components"; both None change nothing)."""
     search = metrics3d._check_search(search)
     voxel_size = metrics3d._check_voxel(voxel_size)
     if voxel_size is not None and normals:
         raise ValueError("voxel_size together with normals=True: a voxel's normal for normal consistency is not defined here")
+    components_kw = metrics3d._check_components(min_component_faces, keep_largest)
+    components_kw = {} if components_kw is None else {"min_component_faces": min_component_faces, "keep_largest": keep_largest}
     meshes = reconstruction_meshes(tsdf_mesh, intrinsics, poses, height, width, iterations=iterations, lam=lam, **refuse_args)
     dev = meshes["tsdf"][0].device
     return {name: metrics3d.score_mesh(meshes[name], gt_mesh, num_points=num_points, distance_thresh=distance_thresh, generator=generator,
                                        uniforms=uniforms, device=dev, icp_align=icp_align, icp_threshold=icp_threshold, search=search,
-                                       **({"normals": True} if normals else {}), **({} if voxel_size is None else {"voxel_size": voxel_size}))
+                                       **({"normals": True} if normals else {}), **({} if voxel_size is None else {"voxel_size": voxel_size}), **components_kw)
             for name in MESH_NAMES}
