@@ -1190,6 +1190,77 @@ int vfn_cc_segment_sums(const double* sorted_values, int64_t n, const int64_t* s
                         void* stream);
 
 /* =============================================================================================
+ * Orientation of a triangle mesh (csrc/vfn_orient.hip, csrc/vfn_orient_core.h; vf_nerf_amd/meshops.py: orientation, orient,
+ * inconsistent_edges): the faces rewound so that two faces that share a manifold edge traverse it in opposite directions — what the
+ * contrastive marching-cubes mesh, whose cells choose their sides locally, does not give.  A SPECIFICATION of ours, not verified against
+ * trimesh's fix_normals or Open3D's orient_triangles: neither is available to compare against, and neither fixes which face of a piece
+ * keeps its winding; ours does.  The connected-components union-find with one more bit per node: labels, counts and tables are int64,
+ * the forest int32, parities and directions uint8, votes float64 evaluated without contraction in the association written here, with
+ * no floating-point atomics.  The forest's intermediate states depend on the schedule; no output does.
+ *   The items (the caller's, torch plumbing).  The 3m half-edges of faces[m, 3] exactly as the "edge" items of the connected components
+ *                     above: all corner pairs (0,1) in face order, then all (1,2), then all (2,0); for the half-edge a -> b
+ *                     key = min(a, b) * n + max(a, b) (-1 where a == b), node = the face, and a direction byte dir = (a < b); sorted
+ *                     ascending by key with a STABLE sort.
+ *   Manifold edge.    A run of equal keys >= 0 of length EXACTLY two whose two items belong to different faces.  A run of length 1
+ *                     (boundary), a run of length 3 or more (non-manifold), a corner pair with a == b (key -1) and a run of two items of
+ *                     one face impose nothing and connect nothing.
+ *   Constraint.       flip[f] says whether face f is rewound.  A manifold edge between f and g requires
+ *                       flip[f] ^ flip[g] == (dir_f == dir_g)
+ *                     — consistent neighbours traverse a shared edge in opposite directions.
+ *   Components.       The classes of the faces under manifold edges (in general finer than the "edge" components above).  The ROOT of a
+ *                     component is its lowest face index, components are numbered 0 .. K-1 in ascending root; first_face[K],
+ *                     face_label[m] and face_count[K] as above.
+ *   Orientable.       A component is orientable iff all its constraints can hold together; parity[f], the flip of f relative to its
+ *                     component's root face, is then unique.  A component that is not is reported (orientable[c] = 0), has parity 0 on
+ *                     all its faces, takes no part in the vote below, and its faces come out unchanged.
+ *   The sign of a component (the caller's `reference`): flip[f] = parity[f] ^ sign[face_label[f]], sign = 0 where not orientable.
+ *                     "first":      sign = 0, the root face keeps its winding.
+ *                     "majority":   sign = 1 iff 2 * (faces of the component with parity 1) > face_count: the sign that flips fewer
+ *                                   faces, integers only; on a tie the root keeps its winding.
+ *                     "volume" / "viewpoints": every face casts a vote t (vfn_orient_votes), a component's votes in ascending face
+ *                                   index are added by vfn_cc_segment_sums' rule, sign = 1 iff the sum is < 0 (a sum of 0, a NaN and a
+ *                                   component of one face follow the same rule).  "volume" is meaningful for closed pieces only: the
+ *                                   sum is six times the signed volume a closed piece encloses, and depends on the origin for an open one.
+ *   Flipping a face swaps its columns 1 and 2; column 0 stays.
+ *   vfn_orient_union_runs  reads keys[n_items] (sorted), nodes[n_items], dirs[n_items]; updates forest[n_nodes] (int32), which the
+ *                     CALLER fills with x << 1: a word holds (parent << 1) | parity_to_parent, so that every load and every
+ *                     compare-and-swap sees a consistent pair — hence n_nodes < 2^30.  One lane per item i >= 1: where
+ *                     keys[i-1] == keys[i] >= 0, keys[i-2] and keys[i+1] (where they exist) differ from it and nodes[i-1] != nodes[i],
+ *                     the trees of the two faces are united with the parity want = (dirs[i-1] != 0) == (dirs[i] != 0) between them — a
+ *                     concurrent parity union-find (csrc/vfn_orient_core.h): only a root is ever hooked, by a compare-and-swap
+ *                     (a, 0) -> (b, q) with b < a both found as roots; path halving by compare-and-swap composes the parities of the
+ *                     skipped link.  A unite whose two finds end at one root writes nothing: conflicts are not judged here.  After the
+ *                     launch the trees are the components, every root is its tree's lowest node, and in an orientable component the
+ *                     parity of every node relative to its root is the unique one — whatever the schedule.  A node outside
+ *                     [0, n_nodes): info bit 2, the pair is not followed.  A word whose parent lies outside [0, its node], or a root word
+ *                     with its parity bit set (a forest that is not ours): info bit 2.
+ *   vfn_orient_flatten  reads forest[n_nodes] AFTER the unions (another launch); writes root[n_nodes] (int64): where v's chain ends, and
+ *                     parity[n_nodes] (uint8): the XOR of the parity bits along it.  Reads only.  A bad word: info bit 2, root[v] = -1,
+ *                     parity[v] = 0.
+ *   vfn_orient_votes  reads vertices[n, 3], faces[m, 3], parity[m] (NULL: all 0); one lane per face, its corners (v0, v1, v2) with
+ *                     v1 and v2 exchanged where parity is set.
+ *                     mode VFN_ORIENT_VOLUME (viewpoints NULL, n_views 0):
+ *                       c = (v1.y v2.z - v1.z v2.y,  v1.z v2.x - v1.x v2.z,  v1.x v2.y - v1.y v2.x)      two products and one subtraction each
+ *                       t = (v0.x c.x + v0.y c.y) + v0.z c.z
+ *                     mode VFN_ORIENT_VIEWPOINTS (viewpoints[n_views, 3], n_views >= 1):
+ *                       a = v1 - v0;  b = v2 - v0;  c = a x b as in vfn_face_normals;  g = ((v0 + v1) + v2) / 3      per coordinate
+ *                       for j ascending: d = p_j - g;  s_j = (d.x d.x + d.y d.y) + d.z d.z;  the LOWEST j with the least s_j is taken
+ *                       t = ((c.x d.x + c.y d.y) + c.z d.z) / sqrt(s);   t = 0 where s == 0
+ *                     votes[m] = t.  One lane walks all the viewpoints — one per camera: a long list is slow and stays correct.  A
+ *                     face with an index outside [0, n): info bit 2, votes = 0, nothing is read through it.  A non-finite coordinate
+ *                     of the face or of a viewpoint: info bit 1.
+ * info[0] (int64, zero-filled by the caller, only OR-ed into).  Limits: 1 <= n_nodes < 2^30, 1 <= n_items < 3 * 2^30, 0 <= n < 2^31,
+ * 1 <= m < 2^31, 1 <= n_views < 2^31.  Every argument check answers before any launch.
+ * ============================================================================================= */
+#define VFN_ORIENT_VOLUME 0
+#define VFN_ORIENT_VIEWPOINTS 1
+int vfn_orient_union_runs(const int64_t* keys, const int64_t* nodes, const uint8_t* dirs, int64_t n_items, int32_t* forest, int64_t n_nodes,
+                          int64_t* info, void* stream);
+int vfn_orient_flatten(const int32_t* forest, int64_t n_nodes, int64_t* root, uint8_t* parity, int64_t* info, void* stream);
+int vfn_orient_votes(const double* vertices, int64_t n, const int64_t* faces, int64_t m, const uint8_t* parity, int32_t mode,
+                     const double* viewpoints, int64_t n_views, double* votes, int64_t* info, void* stream);
+
+/* =============================================================================================
  * Optimizer side of a training step over ONE flat fp32 buffer (train/vector_field_nerf_train.py:254-260:
  * torch.nn.utils.clip_grad_norm_(model.parameters(), clip); optimizer.step()).  The unique parameters — and their gradients
  * and Adam moments — are laid out contiguously, sorted into up to four REGIONS [start, end) of equal multiplicity `mult` =

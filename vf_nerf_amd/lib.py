@@ -53,6 +53,7 @@ EXPORTS = (
     "vfn_face_normals", "vfn_vertex_normals", "vfn_normal_dots",
     "vfn_voxel_keys", "vfn_voxel_means",
     "vfn_cc_union_runs", "vfn_cc_flatten", "vfn_cc_segment_sums",
+    "vfn_orient_union_runs", "vfn_orient_flatten", "vfn_orient_votes",
 )
 
 
@@ -2148,6 +2149,91 @@ def cc_segment_sums(sorted_values: torch.Tensor, start: torch.Tensor, info: Opti
     if own:
         cc_check(int(info.cpu()))
     return sums
+
+
+# ------------------------------------------------------------------------------------------------
+# orientation (csrc/vfn_orient.hip; vf_nerf_amd/meshops.py is the public surface).  Keys, nodes, roots int64, the forest int32 holding
+# (parent << 1) | parity, directions and parities uint8, votes float64; contiguous, on one device.
+# ------------------------------------------------------------------------------------------------
+ORIENT_VOLUME, ORIENT_VIEWPOINTS = 0, 1          # VFN_ORIENT_* of include/vfn.h
+ORIENT_NODE_LIMIT = 1 << 30                      # a forest word holds the parent shifted by one bit
+
+
+def orient_check(status: int, what: str = "orientation") -> None:
+    if status & GEOM_STATUS_INDEX:
+        raise VfnError(f"{what}: a node, a parent or a face index lies outside its range")
+    if status & GEOM_STATUS_NONFINITE:
+        raise VfnError(f"{what}: a non-finite coordinate")
+
+
+def orient_union_runs(keys: torch.Tensor, nodes: torch.Tensor, dirs: torch.Tensor, forest: torch.Tensor,
+                      info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sorted keys[k] with their nodes[k] (int64) and direction bytes dirs[k] (uint8), and the forest[n] (int32, the caller's
+    ``arange(n) << 1``) -> forest, updated in place: every run of exactly two equal keys >= 0 from two nodes unites them with the parity
+    ``dirs[i-1] == dirs[i]`` (include/vfn.h: vfn_orient_union_runs).  A node outside [0, n) raises — or, with the caller's zero-filled
+    ``info`` (int64 [1]), sets its bits (``orient_check``)."""
+    if keys.dim() != 1 or nodes.dim() != 1 or dirs.dim() != 1 or forest.dim() != 1 or not keys.shape[0] == nodes.shape[0] == dirs.shape[0]:
+        raise VfnError(f"orient_union_runs: keys, nodes and dirs must be [k] and forest [n], got {tuple(keys.shape)}, {tuple(nodes.shape)}, "
+                       f"{tuple(dirs.shape)} and {tuple(forest.shape)}")
+    if keys.shape[0] < 1 or not 1 <= forest.shape[0] < ORIENT_NODE_LIMIT:
+        raise VfnError(f"orient_union_runs: {keys.shape[0]} items on {forest.shape[0]} nodes; at least 1 item, and nodes in [1, 2^30)")
+    dev = forest.device
+    args = (_ptr(keys, "keys", torch.int64), _ptr(nodes, "nodes", torch.int64), _ptr(dirs, "dirs", torch.uint8), C.c_int64(keys.shape[0]),
+            _ptr(forest, "forest", torch.int32), C.c_int64(forest.shape[0]))
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_orient_union_runs(*args, _ptr(info, "info", torch.int64), _stream()), "vfn_orient_union_runs")
+    if own:
+        orient_check(int(info.cpu()))
+    return forest
+
+
+def orient_flatten(forest: torch.Tensor, info: Optional[torch.Tensor] = None):
+    """The forest[n] (int32) after the unions -> (root[n] int64, parity[n] uint8): where every node's chain ends and the XOR of the
+    parity bits along it (include/vfn.h: vfn_orient_flatten); (-1, 0) where a word is not ours.  ``info`` as in ``orient_union_runs``."""
+    if forest.dim() != 1 or not 1 <= forest.shape[0] < ORIENT_NODE_LIMIT:
+        raise VfnError(f"orient_flatten: forest must be [n] with n in [1, 2^30), got {tuple(forest.shape)}")
+    dev = forest.device
+    ptr = _ptr(forest, "forest", torch.int32)
+    root = torch.empty(forest.shape[0], dtype=torch.int64, device=dev)
+    parity = torch.empty(forest.shape[0], dtype=torch.uint8, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_orient_flatten(ptr, C.c_int64(forest.shape[0]), _ptr(root, "root", torch.int64), _ptr(parity, "parity", torch.uint8),
+                                         _ptr(info, "info", torch.int64), _stream()), "vfn_orient_flatten")
+    if own:
+        orient_check(int(info.cpu()))
+    return root, parity
+
+
+def orient_votes(vertices: torch.Tensor, faces: torch.Tensor, parity: Optional[torch.Tensor], mode: int,
+                 viewpoints: Optional[torch.Tensor] = None, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vertices[n,3] float64, faces[m,3] int64 (m >= 1), parity[m] uint8 (None: all 0) -> votes[m] float64: every face's vote for the
+    sign of its component, its corners 1 and 2 exchanged where ``parity`` is set (include/vfn.h: vfn_orient_votes).  ``mode`` is
+    ``ORIENT_VOLUME`` (no viewpoints) or ``ORIENT_VIEWPOINTS`` (viewpoints[C,3] float64, C >= 1).  ``info`` as in ``orient_union_runs``."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise VfnError(f"orient_votes: vertices must be [n,3] and faces [m,3] with m >= 1, got {tuple(vertices.shape)} and {tuple(faces.shape)}")
+    if parity is not None and tuple(parity.shape) != (faces.shape[0],):
+        raise VfnError(f"orient_votes: parity must be [{faces.shape[0]}], got {tuple(parity.shape)}")
+    if mode not in (ORIENT_VOLUME, ORIENT_VIEWPOINTS):
+        raise VfnError(f"orient_votes: mode must be ORIENT_VOLUME or ORIENT_VIEWPOINTS, got {mode!r}")
+    if mode == ORIENT_VIEWPOINTS and (viewpoints is None or viewpoints.dim() != 2 or viewpoints.shape[1] != 3 or viewpoints.shape[0] < 1):
+        raise VfnError(f"orient_votes: ORIENT_VIEWPOINTS takes viewpoints [C,3] with C >= 1, got "
+                       f"{None if viewpoints is None else tuple(viewpoints.shape)}")
+    if mode == ORIENT_VOLUME and viewpoints is not None:
+        raise VfnError("orient_votes: ORIENT_VOLUME takes no viewpoints")
+    n, m = vertices.shape[0], faces.shape[0]
+    dev = faces.device
+    args = (_ptr(vertices, "vertices", torch.float64) if n else None, C.c_int64(n), _ptr(faces, "faces", torch.int64), C.c_int64(m),
+            _ptr(parity, "parity", torch.uint8), C.c_int32(mode), _ptr(viewpoints, "viewpoints", torch.float64),
+            C.c_int64(0 if viewpoints is None else viewpoints.shape[0]))
+    votes = torch.empty(m, dtype=torch.float64, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_orient_votes(*args, _ptr(votes, "votes", torch.float64), _ptr(info, "info", torch.int64), _stream()), "vfn_orient_votes")
+    if own:
+        orient_check(int(info.cpu()))
+    return votes
 
 
 # ------------------------------------------------------------------------------------------------

@@ -25,6 +25,8 @@ import torch
 from . import geomargs, grid, lib, meshops
 
 N_COMBS = 28
+ORIENT_REFERENCES = ("first", "majority", "volume")          # meshops.REFERENCES that need nothing but the mesh
+ORIENT = None          # None, or one of ORIENT_REFERENCES: ``contrastive_marching_cubes`` then rewinds its faces (dropin.install(mesh_orient=))
 
 
 def _check_even(res: int) -> None:
@@ -81,9 +83,20 @@ def to_reference(vertices: torch.Tensor, faces: torch.Tensor):
     return vs, fs
 
 
+def _check_orient(orient):
+    if orient is not None and orient not in ORIENT_REFERENCES:
+        raise ValueError(f"orient must be None or one of {ORIENT_REFERENCES}, got {orient!r}")
+    return orient
+
+
 def contrastive_marching_cubes(comb_values, isovalue=0.0, res=100, size=2.0, udf=None, selected_indices=None):
-    """Drop-in for evaluation/utils/marching_cubes_vt.contrastive_marching_cubes (same arguments, same (vs, fs))."""
-    return to_reference(*triangulate(comb_values, isovalue=isovalue, res=res, size=size, udf=udf, selected_indices=selected_indices))
+    """Drop-in for evaluation/utils/marching_cubes_vt.contrastive_marching_cubes (same arguments, same (vs, fs)).  With the module's
+    ``ORIENT`` set (None by default: nothing changes) the faces are rewound by ``meshops.orient`` before they are listed: same vertices,
+    same faces in the same order, columns 1 and 2 of some exchanged."""
+    vertices, faces = triangulate(comb_values, isovalue=isovalue, res=res, size=size, udf=udf, selected_indices=selected_indices)
+    if ORIENT is not None:
+        _, faces, _ = meshops.orient((vertices, faces), reference=_check_orient(ORIENT))
+    return to_reference(vertices, faces)
 
 
 def _dev_field(prediction: torch.Tensor, resolution: int) -> torch.Tensor:
@@ -149,15 +162,18 @@ class Mesh(NamedTuple):
 
 @torch.no_grad()
 def extract_mesh(decoder, resolution: int, scale: float = 1.0, translation=0, centroid=0, smooth_after: bool = False,
-                 smooth_all: bool = False, max_batch: int = 100000, device=None, weld: bool = False) -> Mesh:
+                 smooth_all: bool = False, max_batch: int = 100000, device=None, weld: bool = False, orient=None) -> Mesh:
     """evaluation/methods.py:140-322 (``marching_cubes_mesh``) without files: lattice -> queries -> ``field_to_mesh``.  The lattice is
     regenerated on the device from its axis tables (no res^3 host grid), the queries stay device-resident.  ``vertices_scaled`` is
     what the PLY's f4 vertices become after ``apply_scale`` / ``apply_translation(translation)`` / ``apply_translation(centroid)``
     (:314-316).  ``weld=True``: ``vertices``, ``faces`` and ``vertices_scaled`` are those of ``meshops.weld`` (``digits=8``) applied to
     float64(float32(vertices)) before scaling — where the reference's ``trimesh.Trimesh(...)`` merges: after the PLY's f4 rounding and
-    before ``apply_scale``.  The default changes nothing."""
+    before ``apply_scale``.  The default changes nothing.  ``orient`` ("first", "majority" or "volume"; None: the faces as extracted):
+    the faces are those of ``meshops.orient(mesh, reference=orient)`` applied to the mesh this call would otherwise return — the cells
+    choose their sides locally, so the extracted faces are not consistently wound; the vertices are untouched."""
     if not isinstance(weld, bool):
         raise ValueError(f"weld must be a bool, got {weld!r}")
+    _check_orient(orient)
     res = geomargs.positive_int(resolution, "resolution")
     _check_even(res)
     if res < 2:
@@ -179,4 +195,6 @@ def extract_mesh(decoder, resolution: int, scale: float = 1.0, translation=0, ce
     if weld:
         vertices, faces, _ = meshops.weld((vertices.to(torch.float32).to(torch.float64), faces), digits=meshops.WELD_DIGITS, device=dev)
     scaled = vertices.to(torch.float32).to(torch.float64) * float(scale) + t + c
+    if orient is not None:
+        _, faces, _ = meshops.orient(Mesh(vertices, faces, scaled), reference=orient, device=dev)
     return Mesh(vertices, faces, scaled)

@@ -21,12 +21,20 @@ when it loads a mesh (methods.py:305).
 * ``filter_components`` — the mesh without its small pieces ("floaters"): by face count, by area, or the k largest.
 * ``remove_degenerate_faces`` / ``remove_duplicate_faces`` / ``clean`` — faces that name a vertex twice (or have no area), faces that
   repeat an earlier face's vertex triple, and the four steps in one call.  Torch plumbing, no kernel of their own.
+* ``orientation`` / ``orient`` — the faces rewound so that two faces sharing a manifold edge traverse it in opposite directions
+  (csrc/vfn_orient.hip, include/vfn.h): the components' union-find with one more bit per node, a parity forest under compare-and-swap,
+  exact and independent of the schedule; the sign of every component by its first face, the majority, the enclosed volume or the
+  nearest viewpoints; a non-orientable component is reported and left alone.  What the contrastive marching-cubes mesh needs before
+  ``vertex_normals`` means anything on it (``mesh.extract_mesh(..., orient=)``).  As specified by us, NOT verified against trimesh's
+  ``fix_normals`` or Open3D's ``orient_triangles``; tests/orient_restatement.py restates it in NumPy twice and the device is held to
+  it bit for bit.  ``inconsistent_edges`` counts the manifold edges wound the same way from both sides.
 
 Inputs are numpy arrays or torch tensors on any device; a mesh is a ``mesh.Mesh`` (its ``vertices_scaled`` are used) or a
 ``(vertices, faces)`` pair.  Outputs are device tensors.  No CPU fallback: ``lib.VfnError`` when no device is visible.  A face index
 outside [0, n) is refused on the host (``ValueError``) before anything is launched.
 
-Out of scope: angle-weighted or uniform vertex normals, orienting a mesh, filling holes, simplification.
+Out of scope: angle-weighted or uniform vertex normals, signed normal consistency (``vfn_normal_dots`` takes ``fabs`` by contract), filling
+holes, simplification.
 """
 from __future__ import annotations
 
@@ -41,6 +49,7 @@ from . import geomargs, lib
 WELD_DIGITS = 8                    # trimesh's merge_vertices default (digits_vertex), as remembered
 CONNECTIVITIES = ("edge", "vertex")
 SIZES = ("faces", "area")          # what ``keep_largest`` ranks by
+REFERENCES = ("first", "majority", "volume", "viewpoints")          # what fixes the sign of an orientation component
 
 
 def _check_indices(f: torch.Tensor, n: int, name: str) -> None:
@@ -301,6 +310,169 @@ def filter_components(mesh, min_faces=None, min_area=None, keep_largest=None, by
     min_faces, min_area, keep_largest, by, connectivity = _check_filter(min_faces, min_area, keep_largest, by, connectivity)
     v, f = _mesh_on_device(mesh, device, "mesh", "component filtering")
     return _filter(v, f, min_faces, min_area, keep_largest, by, connectivity)[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# orientation (csrc/vfn_orient.hip, include/vfn.h)
+# ------------------------------------------------------------------------------------------------
+class Orientation(NamedTuple):
+    """What ``orientation`` returns: device tensors, except ``n_components`` and ``inconsistent_edges``."""
+    flip: torch.Tensor                         # [m] bool: the faces whose columns 1 and 2 change places
+    face_label: torch.Tensor                   # [m] int64: the orientation component of every face, numbered in ascending lowest face
+    n_components: int                          # K (host)
+    first_face: torch.Tensor                   # [K] int64: every component's lowest face index, ascending
+    face_count: torch.Tensor                   # [K] int64, exact
+    orientable: torch.Tensor                   # [K] bool: False for a component whose constraints contradict each other (left as it is)
+    flipped_count: torch.Tensor                # [K] int64: the faces of the component that ``flip`` names
+    inconsistent_edges: int                    # the manifold edges of the INPUT whose two faces traverse them the same way (host)
+    votes: Optional[torch.Tensor]              # [K] float64: the vote sums of "volume" / "viewpoints"; None otherwise
+
+
+def _check_reference(reference, viewpoints):
+    """The checks of ``reference`` / ``viewpoints`` that need no device -> (reference, viewpoints tensor or None, wherever it is)."""
+    if reference not in REFERENCES:
+        raise ValueError(f"reference must be one of {REFERENCES}, got {reference!r}")
+    if reference != "viewpoints":
+        if viewpoints is not None:
+            raise ValueError(f"viewpoints are taken with reference='viewpoints' only, not with {reference!r}")
+        return reference, None
+    if viewpoints is None:
+        raise ValueError("reference='viewpoints' needs viewpoints [C,3]")
+    p = geomargs.as_tensor(viewpoints, "viewpoints")
+    if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] < 1 or not p.dtype.is_floating_point:
+        raise ValueError(f"viewpoints must be floating point [C,3] with C >= 1, got {p.dtype} {tuple(p.shape)}")
+    if not p.is_cuda and not bool(torch.isfinite(p).all()):          # (on the device the vote kernel's status word says so: no read here)
+        raise ValueError("viewpoints: a non-finite coordinate")
+    return reference, p
+
+
+def orient_items(faces: torch.Tensor, n_vertices: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Device faces[m,3] (m >= 1, checked) -> (keys, nodes, dirs) as ``lib.orient_union_runs`` takes them: the "edge" items of
+    ``component_items`` — the same keys in the same stable order — each with the direction byte (a < b) of its half-edge a -> b."""
+    m = faces.shape[0]
+    a = torch.cat((faces[:, 0], faces[:, 1], faces[:, 2]))
+    b = torch.cat((faces[:, 1], faces[:, 2], faces[:, 0]))
+    keys = torch.where(a == b, torch.full_like(a, -1), torch.minimum(a, b) * n_vertices + torch.maximum(a, b))
+    keys, order = torch.sort(keys, stable=True)
+    return keys, torch.arange(m, dtype=torch.int64, device=faces.device).repeat(3)[order].contiguous(), (a < b)[order].to(torch.uint8).contiguous()
+
+
+def manifold_mask(keys: torch.Tensor, nodes: torch.Tensor, dirs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k items of ``orient_items`` -> (manifold[k-1], same_way[k-1]), bool, over the ADJACENT item pairs (i, i + 1): whether the pair
+    is a manifold edge — a run of exactly two equal keys >= 0 whose items belong to two faces nodes[i] != nodes[i + 1] — and whether its
+    two half-edges run the same way, the parity the edge asks for between the faces.  Masks over all pairs, nothing compacted: no
+    host read."""
+    same = (keys[1:] == keys[:-1]) & (keys[1:] >= 0)
+    manifold = same & (nodes[1:] != nodes[:-1])
+    manifold[1:] &= ~same[:-1]                 # the run does not begin earlier ...
+    manifold[:-1] &= ~same[1:]                 # ... and does not go on
+    return manifold, dirs[1:] == dirs[:-1]
+
+
+def _count_by_label(face_label: torch.Tensor, flags: torch.Tensor, k: int) -> torch.Tensor:
+    """-> [k] int64: how many of the flagged entries carry each label.  Exact integer additions (``torch.bincount`` would read its
+    input's maximum on the host).  With few labels every addition would land on the same few words, so each label gets ``spread`` words
+    (a power of two chosen on the host from k alone, at most 2^22 words in all), entry i adds into word i % spread of its label, and the
+    words of a label are added at the end."""
+    spread = 1 << max(0, min(8, 22 - int(k).bit_length()))
+    dev = face_label.device
+    words = face_label * spread + (torch.arange(face_label.shape[0], dtype=torch.int64, device=dev) & (spread - 1))
+    return torch.zeros(k * spread, dtype=torch.int64, device=dev).scatter_add_(0, words, flags.to(torch.int64)).view(k, spread).sum(dim=1)
+
+
+def _orientation(v: torch.Tensor, f: torch.Tensor, reference: str, viewpoints: Optional[torch.Tensor]) -> Orientation:
+    """Device vertices / faces, checked -> ``Orientation``.  Two host reads: the number of components (inside ``torch.unique``), and the
+    status words with the count of inconsistent edges, together.  Nothing in between is compacted (no ``nonzero``, no boolean-mask
+    indexing, no ``bincount``): the pair test runs over the masks of all adjacent items."""
+    dev, m = v.device, f.shape[0]
+    if m >= lib.ORIENT_NODE_LIMIT:
+        raise ValueError(f"orientation: {m} faces; one call takes fewer than 2^30 (a forest word holds the parent shifted by one bit)")
+    with torch.cuda.device(dev):
+        if m == 0:
+            none = torch.empty(0, dtype=torch.int64, device=dev)
+            no = torch.empty(0, dtype=torch.bool, device=dev)
+            return Orientation(no, none, 0, none.clone(), none.clone(), no.clone(), none.clone(), 0,
+                               torch.empty(0, dtype=torch.float64, device=dev) if reference in ("volume", "viewpoints") else None)
+        info = torch.zeros(4, dtype=torch.int64, device=dev)          # a word per stage: the first stage's complaint names the cause
+        keys, nodes, dirs = orient_items(f, v.shape[0])
+        forest = torch.arange(0, 2 * m, 2, dtype=torch.int32, device=dev)          # x << 1: every face a root, parity 0
+        lib.orient_union_runs(keys, nodes, dirs, forest, info=info[0:1])
+        root, parity = lib.orient_flatten(forest, info=info[1:2])
+        first_face, face_label, face_count = torch.unique(root, return_inverse=True, return_counts=True)   # ascending root: the numbering.  The read for K.
+        k = int(first_face.shape[0])
+        # the conflict test: a manifold edge whose two faces' parities do not differ as it asks makes its component non-orientable
+        manifold, want = manifold_mask(keys, nodes, dirs)
+        a, b = nodes[:-1], nodes[1:]
+        wrong = manifold & (((parity[a] ^ parity[b]) != 0) != want)
+        orientable = _count_by_label(face_label[a], wrong, k) == 0
+        parity = torch.where(orientable[face_label], parity, torch.zeros_like(parity)).contiguous()
+        sign = torch.zeros(k, dtype=torch.bool, device=dev)
+        votes = None
+        if reference == "majority":
+            sign = 2 * _count_by_label(face_label, parity, k) > face_count                        # exact; a tie keeps the root's winding
+        elif reference in ("volume", "viewpoints"):
+            per_face = lib.orient_votes(v, f, parity, lib.ORIENT_VOLUME if reference == "volume" else lib.ORIENT_VIEWPOINTS, viewpoints,
+                                        info=info[2:3])
+            order = torch.sort(face_label, stable=True)[1]          # a component's faces in ascending face index
+            start = torch.cat((torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(face_count, dim=0))).contiguous()
+            votes = lib.cc_segment_sums(per_face[order].contiguous(), start, info=info[3:4])
+            sign = (votes < 0) & orientable
+        flip = (parity != 0) ^ sign[face_label]
+        flipped_count = _count_by_label(face_label, flip, k)
+        unions, chains, faces_status, sums, inconsistent = (int(x) for x in torch.cat((info, (manifold & want).sum().reshape(1))).cpu())   # the one read
+        lib.orient_check(unions, "orientation (unions)")
+        lib.orient_check(chains, "orientation (flatten)")
+        lib.orient_check(faces_status, "orientation (votes)")
+        lib.cc_check(sums, "orientation (vote sums)")
+    return Orientation(flip, face_label, k, first_face, face_count, orientable, flipped_count, inconsistent, votes)
+
+
+def _rewind(f: torch.Tensor, flip: torch.Tensor) -> torch.Tensor:
+    """faces with the columns 1 and 2 of the flipped faces exchanged; column 0 stays."""
+    return torch.stack((f[:, 0], torch.where(flip, f[:, 2], f[:, 1]), torch.where(flip, f[:, 1], f[:, 2])), dim=1).contiguous()
+
+
+def orientation(mesh, reference: str = "first", viewpoints=None, device=None) -> Orientation:
+    """-> ``Orientation`` on the device: which faces to rewind so that two faces that share a manifold edge traverse it in opposite
+    directions (csrc/vfn_orient.hip; include/vfn.h has the specification).  A manifold edge is an undirected edge held by exactly two
+    half-edges of two different faces; boundary edges, edges of three or more faces and corner pairs naming one vertex twice impose
+    nothing and connect nothing, so the orientation components are in general finer than ``connected_components("edge")``.  Components
+    are numbered in ascending lowest face (``first_face``).  A component whose constraints contradict each other (a Möbius strip) has
+    ``orientable`` False and none of its faces in ``flip``.  ``reference`` chooses the sign of every orientable component:
+    ``"first"`` — its lowest face keeps its winding; ``"majority"`` — the sign that flips fewer faces, the lowest face keeping its winding
+    on a tie; ``"volume"`` — the sign that makes six times the signed volume, sum of v0 . (v1 x v2), not negative: meaningful for CLOSED
+    pieces only; ``"viewpoints"`` with ``viewpoints[C,3]`` — the sign that turns the faces' normals towards their nearest viewpoint, summed
+    over the component.  The vote sums (``votes``) are float64, added in the fixed order of ``vfn_cc_segment_sums``; no output depends
+    on the schedule of the union-find.  ``inconsistent_edges`` counts the manifold edges of the input whose two faces traverse them the
+    same way.  As specified by us, not verified against trimesh's ``fix_normals`` or Open3D's ``orient_triangles``."""
+    reference, viewpoints = _check_reference(reference, viewpoints)
+    v, f = _mesh_on_device(mesh, device, "mesh", "mesh orientation")
+    if viewpoints is not None:
+        viewpoints = viewpoints.to(v.device, torch.float64).contiguous()
+    return _orientation(v, f, reference, viewpoints)
+
+
+def orient(mesh, reference: str = "first", viewpoints=None, device=None) -> Tuple[torch.Tensor, torch.Tensor, Orientation]:
+    """-> (vertices float64 [n,3], faces int64 [m,3], ``Orientation``) on the device: the mesh with the faces ``orientation`` names
+    rewound — their columns 1 and 2 exchanged, column 0, the order of the faces and the vertices as they were."""
+    reference, viewpoints = _check_reference(reference, viewpoints)
+    v, f = _mesh_on_device(mesh, device, "mesh", "mesh orientation")
+    if viewpoints is not None:
+        viewpoints = viewpoints.to(v.device, torch.float64).contiguous()
+    o = _orientation(v, f, reference, viewpoints)
+    with torch.cuda.device(v.device):
+        return v, _rewind(f, o.flip), o
+
+
+def inconsistent_edges(mesh, device=None) -> int:
+    """-> how many manifold edges of the mesh are traversed the same way by their two faces (0: consistently wound wherever that means
+    anything).  Torch plumbing over the sorted half-edges: no kernel, one host read after the index check of the input."""
+    v, f = _mesh_on_device(mesh, device, "mesh", "counting inconsistent edges")
+    if f.shape[0] == 0:
+        return 0
+    with torch.cuda.device(v.device):
+        manifold, same_way = manifold_mask(*orient_items(f, v.shape[0]))
+        return int((manifold & same_way).sum())
 
 
 def remove_degenerate_faces(mesh, zero_area: bool = False, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
