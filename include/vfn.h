@@ -1261,6 +1261,73 @@ int vfn_orient_votes(const double* vertices, int64_t n, const int64_t* faces, in
                      const double* viewpoints, int64_t n_views, double* votes, int64_t* info, void* stream);
 
 /* =============================================================================================
+ * Vertex-clustering simplification of a triangle mesh (csrc/vfn_simplify.hip; vf_nerf_amd/meshops.py: simplify_vertex_clustering): the
+ * vertices of every occupied voxel contracted into one, the faces that collapse dropped — what the reference does to a mesh before it
+ * takes vertex_normals in get_dominant_bases (utils/utils.py:216-233).  A SPECIFICATION of ours that follows Open3D's
+ * simplify_vertex_clustering (SimplificationContraction Average / Quadric) AS REMEMBERED: neither Open3D nor trimesh is available to
+ * compare against, Open3D's hash map fixes no order of summation and its quadric solve has no in-cell test; ours do.  Everything is
+ * float64, evaluated without contraction in the association written here, with no floating-point atomics: no bit depends on the
+ * schedule.  Indices, keys and tables are int64.
+ *   Clusters (the caller's, torch plumbing over the voxel unit above).  Only the vertices that some face names take part.  The frame is
+ *                     the voxel unit's over THEIR bounding box: h = voxel_size, origin_k = min_k - 0.5 h.  A vertex's cell c and key are
+ *                     vfn_voxel_keys'; clusters are numbered 0 .. K-1 in ascending key and the vertices of a cluster stand in ascending
+ *                     index (the stable sort of the voxel unit).  The cell centre and the cluster mean:
+ *                       g_k = origin_k + (c_k + 0.5) h                 an exact sum, a product, a sum; float64 elementwise
+ *                       mean = vfn_voxel_means' mean of the cluster's vertices; colours and normals ride along as further channels
+ *   vfn_face_planes   reads vertices[n, 3], faces[m, 3] and the HOST values origin[3]; one lane per face with corners (v0, v1, v2):
+ *                       c = (v1 - v0) x (v2 - v0) as in vfn_face_normals;  s = c.x c.x;  s = s + c.y c.y;  s = s + c.z c.z;  r = sqrt(s)
+ *                     r > 0 and finite:
+ *                       nrm = (c.x / r, c.y / r, c.z / r)              three divisions
+ *                       w = 0.5 r                                      the area
+ *                       e = nrm.x (v0.x - origin.x);  e = e + nrm.y (v0.y - origin.y);  e = e + nrm.z (v0.z - origin.z)
+ *                       planes[f, 0..4] = (nrm.x, nrm.y, nrm.z, e, w)
+ *                     otherwise (a face without area, or a length that is not finite) planes[f, 0..4] = five +0.0.  info bits as
+ *                     vfn_face_normals': bit 1 = a non-finite coordinate, bit 2 = a face index outside [0, n) (nothing is read through
+ *                     it; five +0.0), bit 4 = r not finite.
+ *   Items (the caller's).  The incidences (vertex, face), each once, ascending by vertex then face, sorted STABLY by the vertex's
+ *                     cluster: a cluster's items stand in ascending (vertex, face).  item_face[n_items] names their faces and
+ *                     start[K + 1] every cluster's first item and n_items.  For an item of cluster q with plane (nrm, e, w):
+ *                       u_k = g_q,k - origin_k
+ *                       d = nrm.x u.x;  d = d + nrm.y u.y;  d = d + nrm.z u.z;  d = d - e      the plane's signed distance from g_q
+ *                       wn_i = w nrm_i;  wd = w d
+ *                       its ten numbers:  wn_0 nrm_0, wn_0 nrm_1, wn_0 nrm_2, wn_1 nrm_1, wn_1 nrm_2, wn_2 nrm_2,      (A: a00 a01 a02 a11 a12 a22)
+ *                                         wd nrm_0, wd nrm_1, wd nrm_2,                                             (b)
+ *                                         wd d                                                                      (c)
+ *                     so that the cluster's quadric about its cell centre is Q(x) = x^T A x + 2 b^T x + c, the area-weighted sum of the
+ *                     squared distances of g_q + x from the planes of the cluster's faces.
+ *   vfn_cluster_quadrics  reads planes[m, 5], item_face[n_items], start[K + 1], centres[K, 3] (= g), means[K, 3] and the HOST values
+ *                     origin[3], h, rcond.  One WAVE of 64 lanes per cluster.  Each of the ten channels is added over the cluster's
+ *                     items by vfn_cc_segment_sums' rule: lane t adds items b+t, b+t+64, ... serially from its FIRST one, a lane without
+ *                     items holds +0.0, then s_t = s_t + s_(t+32) for t < 32, then 16, 8, 4, 2, 1.  Lane 0 then solves A x = -b by the
+ *                     adjugate of the symmetric matrix:
+ *                       m00 = a11 a22 - a12 a12;   m01 = a02 a12 - a01 a22;   m02 = a01 a12 - a02 a11
+ *                       m11 = a00 a22 - a02 a02;   m12 = a01 a02 - a00 a12;   m22 = a00 a11 - a01 a01      two products, one subtraction
+ *                       det = (a00 m00 + a01 m01) + a02 m02
+ *                       y_0 = (m00 b0 + m01 b1) + m02 b2;  y_1 = (m01 b0 + m11 b1) + m12 b2;  y_2 = (m02 b0 + m12 b1) + m22 b2
+ *                       x_k = -(y_k / det)
+ *                       t = ((a00 + a11) + a22) / 3
+ *                     The minimiser is ACCEPTED iff  det > rcond ((t t) t)  and  fabs(x_k) <= 0.5 h for k = 0, 1, 2; every comparison
+ *                     is false on a NaN.  (The in-cell test is ours: a near-singular cluster can never throw its vertex out of its
+ *                     cell.)  The output position and the offset z the error is taken at:
+ *                       accepted:  position_k = g_k + x_k,  z = x;       otherwise:  position = mean (its bits),  z_k = mean_k - g_k
+ *                       p_0 = (a00 z0 + a01 z1) + a02 z2;  p_1 = (a01 z0 + a11 z1) + a12 z2;  p_2 = (a02 z0 + a12 z1) + a22 z2
+ *                       error = (((z0 p_0 + z1 p_1) + z2 p_2) + 2 ((b0 z0 + b1 z1) + b2 z2)) + c
+ *                     placed[K] (uint8) is 1 where the minimiser was accepted.  The tables are not trusted: a segment that is empty,
+ *                     decreasing or outside [0, n_items], or one that holds a face index outside [0, m), gets NaN in position and
+ *                     error, placed 0 and info bit 2; nothing is read through such a bound or index.
+ *   Faces (the caller's).  The input faces with every corner replaced by its cluster; faces that name a cluster twice are dropped, of
+ *                     the faces with one sorted triple the lowest face index stays, the order and the winding of the others are
+ *                     untouched; clusters that no remaining face names are dropped, the others keep their order.
+ * info[0] (int64, zero-filled by the caller, only OR-ed into).  Limits: 0 <= n < 2^31, 1 <= m < 2^31, 1 <= n_items < 3 * 2^31,
+ * 1 <= K <= n_items, h finite and > 0 with a normal square, rcond finite in [0, 1].  Every argument check answers before any launch.
+ * ============================================================================================= */
+int vfn_face_planes(const double* vertices, int64_t n, const int64_t* faces, int64_t m, const double* origin, double* planes, int64_t* info,
+                    void* stream);
+int vfn_cluster_quadrics(const double* planes, int64_t m, const int64_t* item_face, int64_t n_items, const int64_t* start, int64_t n_clusters,
+                         const double* centres, const double* means, const double* origin, double voxel_size, double rcond,
+                         double* position, uint8_t* placed, double* error, int64_t* info, void* stream);
+
+/* =============================================================================================
  * Optimizer side of a training step over ONE flat fp32 buffer (train/vector_field_nerf_train.py:254-260:
  * torch.nn.utils.clip_grad_norm_(model.parameters(), clip); optimizer.step()).  The unique parameters — and their gradients
  * and Adam moments — are laid out contiguously, sorted into up to four REGIONS [start, end) of equal multiplicity `mult` =

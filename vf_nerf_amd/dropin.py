@@ -13,7 +13,7 @@ import importlib
 import sys
 import types
 
-from . import density, evaluator, grid, loss, mesh, nerf, networks, render_output, samplers, supervision
+from . import density, evaluator, grid, loss, mesh, nerf, networks, render_output, samplers, supervision, voxel
 
 _ALIASES = {
     "models.nerf.vector_field_nerf": nerf,
@@ -38,7 +38,7 @@ def _ensure_package(name: str) -> None:
 
 def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scalars=None, patch_mesh: bool = True,
             patch_metrics: bool = False, patch_tsdf_mesh: bool = False, tsdf_vertex_normals=None, tsdf_sparse=None,
-            tsdf_min_component_faces=None, mesh_orient=None) -> None:
+            tsdf_min_component_faces=None, tsdf_simplify_voxel=None, mesh_orient=None) -> None:
     """``patch_clip=False`` leaves ``torch.nn.utils.clip_grad_norm_`` PyTorch's own function (no process-wide replacement): a step session then
     parks its gradient in the optimizer's flat buffer with every ``param.grad`` None, the trainer's clip call finds nothing to scale, and
     ``optimizer.step()`` all-reduces (more than one rank), clips with the model's ``scheduler_config.clip_norm`` — the value the trainer
@@ -64,16 +64,23 @@ def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scal
     ``tsdf_min_component_faces`` (None: leave as is) sets ``evaluator.TSDF_MIN_COMPONENT_FACES``: an integer makes ``evaluator.tsdf_mesh``
     cull the components of the fused mesh with fewer faces (``meshops.filter_components``) before it writes ``tsdf.ply``; the module's
     default is None, the mesh as fused.
+    ``tsdf_simplify_voxel`` (None: leave as is) sets ``evaluator.TSDF_SIMPLIFY_VOXEL``: a voxel edge makes ``evaluator.tsdf_mesh`` simplify
+    the fused mesh by vertex clustering with quadric placement (``meshops.simplify_vertex_clustering``) after the culling and before
+    it writes ``tsdf.ply``, the colours following as cluster means; the module's default is None, the mesh as fused.
     ``mesh_orient`` (None: leave as is) sets ``mesh.ORIENT``: "first", "majority" or "volume" makes ``mesh.contrastive_marching_cubes``
     rewind its faces consistently (``meshops.orient``) before it lists them; the module's default is None, every bit of (vs, fs) the
     reference's."""
     # every argument is checked before any switch is set: an install() that raises leaves everything as it was
     if mesh_orient is not None and mesh_orient not in mesh.ORIENT_REFERENCES:
         raise ValueError(f"mesh_orient must be None or one of {mesh.ORIENT_REFERENCES}, got {mesh_orient!r}")
+    if tsdf_simplify_voxel is not None:
+        tsdf_simplify_voxel = voxel.check_voxel_size(tsdf_simplify_voxel, "tsdf_simplify_voxel")
     if tsdf_min_component_faces is not None:
         if isinstance(tsdf_min_component_faces, bool) or not isinstance(tsdf_min_component_faces, int) or tsdf_min_component_faces < 0:
             raise ValueError(f"tsdf_min_component_faces must be None or an integer >= 0, got {tsdf_min_component_faces!r}")
         evaluator.TSDF_MIN_COMPONENT_FACES = tsdf_min_component_faces
+    if tsdf_simplify_voxel is not None:
+        evaluator.TSDF_SIMPLIFY_VOXEL = tsdf_simplify_voxel
     if mesh_orient is not None:
         mesh.ORIENT = mesh_orient
     if tsdf_vertex_normals is not None:

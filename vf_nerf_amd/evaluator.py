@@ -40,6 +40,9 @@ TSDF_SPARSE = False
 # tsdf_mesh culls the components of the fused mesh with fewer faces (meshops.filter_components, edge connectivity) before it writes
 # tsdf.ply; None: the mesh as fused.  dropin.install(tsdf_min_component_faces=...) sets it.
 TSDF_MIN_COMPONENT_FACES = None
+# tsdf_mesh simplifies the fused mesh by vertex clustering at this voxel edge (meshops.simplify_vertex_clustering, "quadric") after the
+# component culling and before it writes tsdf.ply; None: the mesh as fused.  dropin.install(tsdf_simplify_voxel=...) sets it.
+TSDF_SIMPLIFY_VOXEL = None
 
 
 @torch.no_grad()
@@ -206,7 +209,9 @@ def tsdf_mesh(eval_path: str, dataset_config) -> None:
     extraction already merges its vertices: no weld); by default it does not.  With ``TSDF_SPARSE`` set the fusion runs in the
     block-sparse volume, which a scene spanning more than 2^31 voxels does not stop.  With ``TSDF_MIN_COMPONENT_FACES`` set the components
     of the fused mesh with fewer faces are culled (``meshops.filter_components``) before the file is written; colours, and the normals
-    of the fused mesh if asked for, follow the vertices that stay.  Installed by ``dropin.install(patch_tsdf_mesh=True)``."""
+    of the fused mesh if asked for, follow the vertices that stay.  With ``TSDF_SIMPLIFY_VOXEL`` set the mesh — after that culling — is
+    simplified by vertex clustering at that voxel edge (``meshops.simplify_vertex_clustering``, ``"quadric"``); the colours follow as
+    cluster means and the normals, if asked for, are those of the simplified mesh.  Installed by ``dropin.install(patch_tsdf_mesh=True)``."""
     from PIL import Image
     from . import meshops, ply, tsdf
     dataset_dict = importlib.import_module("datasets.normal_datasets").dataset_dict
@@ -229,7 +234,14 @@ def tsdf_mesh(eval_path: str, dataset_config) -> None:
                                                    **({"sparse": True} if TSDF_SPARSE else {}))
     mesh_path = os.path.join(eval_path, "tsdf-mesh")
     os.makedirs(mesh_path, exist_ok=True)
-    if TSDF_MIN_COMPONENT_FACES is not None:
+    if TSDF_SIMPLIFY_VOXEL is not None:
+        if TSDF_MIN_COMPONENT_FACES is not None:
+            vertices, faces, _, inverse = meshops.filter_components((vertices, faces), min_faces=TSDF_MIN_COMPONENT_FACES)
+            colours = colours[(inverse >= 0).to(colours.device)]
+        simple = meshops.simplify_vertex_clustering((vertices, faces), TSDF_SIMPLIFY_VOXEL, contraction="quadric", colours=colours)
+        ply.write_ply(os.path.join(mesh_path, "tsdf.ply"), simple.vertices, simple.faces, simple.colours,
+                      **({"normals": meshops.vertex_normals((simple.vertices, simple.faces))} if TSDF_VERTEX_NORMALS else {}))
+    elif TSDF_MIN_COMPONENT_FACES is not None:
         normals = meshops.vertex_normals((vertices, faces)) if TSDF_VERTEX_NORMALS else None
         vertices, faces, _, inverse = meshops.filter_components((vertices, faces), min_faces=TSDF_MIN_COMPONENT_FACES)
         stays = (inverse >= 0).to(colours.device)

@@ -54,6 +54,7 @@ EXPORTS = (
     "vfn_voxel_keys", "vfn_voxel_means",
     "vfn_cc_union_runs", "vfn_cc_flatten", "vfn_cc_segment_sums",
     "vfn_orient_union_runs", "vfn_orient_flatten", "vfn_orient_votes",
+    "vfn_face_planes", "vfn_cluster_quadrics",
 )
 
 
@@ -2234,6 +2235,69 @@ def orient_votes(vertices: torch.Tensor, faces: torch.Tensor, parity: Optional[t
     if own:
         orient_check(int(info.cpu()))
     return votes
+
+
+# ------------------------------------------------------------------------------------------------
+# vertex-clustering simplification (csrc/vfn_simplify.hip; vf_nerf_amd/meshops.py is the public surface).  Planes, centres, means and
+# positions float64, indices and tables int64, the placed flags uint8; contiguous, on one device.
+# ------------------------------------------------------------------------------------------------
+def simplify_check(status: int, what: str = "mesh simplification") -> None:
+    if status & GEOM_STATUS_INDEX:
+        raise VfnError(f"{what}: a face index or a segment lies outside its range")
+    if status & GEOM_STATUS_NONFINITE:
+        raise VfnError(f"{what}: a non-finite coordinate")
+    if status & GEOM_STATUS_OVERFLOW:
+        raise VfnError(f"{what}: a normal's length overflowed")
+
+
+def face_planes(vertices: torch.Tensor, faces: torch.Tensor, origin, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vertices[n,3] float64, faces[m,3] int64 (m >= 1), three host floats -> planes[m,5]: every face's unit normal, its offset
+    ``nrm . (v0 - origin)`` and its area; five +0.0 for a face without area (include/vfn.h: vfn_face_planes).  A bad input raises — or,
+    with the caller's zero-filled ``info`` (int64 [1]), sets its bits (``simplify_check``)."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1 or len(origin) != 3:
+        raise VfnError(f"face_planes: vertices must be [n,3], faces [m,3] with m >= 1 and origin three values, got {tuple(vertices.shape)}, "
+                       f"{tuple(faces.shape)} and {len(origin)}")
+    n, m = vertices.shape[0], faces.shape[0]
+    dev = faces.device
+    args = (_ptr(vertices, "vertices", torch.float64) if n else None, C.c_int64(n), _ptr(faces, "faces", torch.int64), C.c_int64(m),
+            (C.c_double * 3)(*(float(o) for o in origin)))
+    planes = torch.empty(m, 5, dtype=torch.float64, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_face_planes(*args, _ptr(planes, "planes", torch.float64), _ptr(info, "info", torch.int64), _stream()), "vfn_face_planes")
+    if own:
+        simplify_check(int(info.cpu()), "face planes")
+    return planes
+
+
+def cluster_quadrics(planes: torch.Tensor, item_face: torch.Tensor, start: torch.Tensor, centres: torch.Tensor, means: torch.Tensor, origin,
+                     voxel_size: float, rcond: float, info: Optional[torch.Tensor] = None):
+    """planes[m,5], item_face[k] and start[K+1] (int64), centres[K,3] and means[K,3], three host floats, the voxel edge and ``rcond`` ->
+    (position[K,3] float64, placed[K] uint8, error[K] float64): every cluster's ten quadric sums added by one wave in the fixed order of
+    include/vfn.h (vfn_cluster_quadrics), the minimiser by the adjugate, accepted inside its cell only; the mean otherwise.  NaN for a
+    segment that is empty, decreasing or outside [0, k], or that names a face outside [0, m).  ``info`` as in ``face_planes``."""
+    if planes.dim() != 2 or planes.shape[1] != 5 or planes.shape[0] < 1 or item_face.dim() != 1 or start.dim() != 1 or len(origin) != 3:
+        raise VfnError(f"cluster_quadrics: planes must be [m,5] with m >= 1, item_face [k], start [K+1] and origin three values, got "
+                       f"{tuple(planes.shape)}, {tuple(item_face.shape)}, {tuple(start.shape)} and {len(origin)}")
+    m, items, clusters = planes.shape[0], item_face.shape[0], start.shape[0] - 1
+    if not 1 <= clusters <= items:
+        raise VfnError(f"cluster_quadrics: start must have between 2 and k + 1 = {items + 1} entries, got {start.shape[0]}")
+    if tuple(centres.shape) != (clusters, 3) or tuple(means.shape) != (clusters, 3):
+        raise VfnError(f"cluster_quadrics: centres and means must be [{clusters},3], got {tuple(centres.shape)} and {tuple(means.shape)}")
+    dev = planes.device
+    args = (_ptr(planes, "planes", torch.float64), C.c_int64(m), _ptr(item_face, "item_face", torch.int64), C.c_int64(items),
+            _ptr(start, "start", torch.int64), C.c_int64(clusters), _ptr(centres, "centres", torch.float64), _ptr(means, "means", torch.float64),
+            (C.c_double * 3)(*(float(o) for o in origin)), C.c_double(voxel_size), C.c_double(rcond))
+    position = torch.empty(clusters, 3, dtype=torch.float64, device=dev)
+    placed = torch.empty(clusters, dtype=torch.uint8, device=dev)
+    error = torch.empty(clusters, dtype=torch.float64, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_cluster_quadrics(*args, _ptr(position, "position", torch.float64), _ptr(placed, "placed", torch.uint8),
+                                           _ptr(error, "error", torch.float64), _ptr(info, "info", torch.int64), _stream()), "vfn_cluster_quadrics")
+    if own:
+        simplify_check(int(info.cpu()), "cluster quadrics")
+    return position, placed, error
 
 
 # ------------------------------------------------------------------------------------------------

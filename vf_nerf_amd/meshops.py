@@ -28,13 +28,20 @@ when it loads a mesh (methods.py:305).
   ``vertex_normals`` means anything on it (``mesh.extract_mesh(..., orient=)``).  As specified by us, NOT verified against trimesh's
   ``fix_normals`` or Open3D's ``orient_triangles``; tests/orient_restatement.py restates it in NumPy twice and the device is held to
   it bit for bit.  ``inconsistent_edges`` counts the manifold edges wound the same way from both sides.
+* ``simplify_vertex_clustering`` — vertex-clustering simplification (csrc/vfn_simplify.hip, include/vfn.h): the vertices of every
+  occupied voxel contracted into one — ``voxel.down_sample``'s cells, numbering and means —, the faces that collapse dropped; with
+  ``contraction="quadric"`` a cluster's vertex stands at the minimiser of its faces' plane quadrics (ten sums a cluster added by one
+  wave in a fixed order, a 3 x 3 adjugate solve, accepted inside the cell only), so that corners and creases survive.  What the
+  reference does before it takes ``vertex_normals`` in ``get_dominant_bases`` (utils/utils.py:216-233).  A specification of ours that
+  follows Open3D's ``simplify_vertex_clustering`` (Average / Quadric) AS REMEMBERED — not verified against Open3D or trimesh;
+  tests/simplify_restatement.py restates it in NumPy twice and the device is held to it bit for bit.
 
 Inputs are numpy arrays or torch tensors on any device; a mesh is a ``mesh.Mesh`` (its ``vertices_scaled`` are used) or a
 ``(vertices, faces)`` pair.  Outputs are device tensors.  No CPU fallback: ``lib.VfnError`` when no device is visible.  A face index
 outside [0, n) is refused on the host (``ValueError``) before anything is launched.
 
 Out of scope: angle-weighted or uniform vertex normals, signed normal consistency (``vfn_normal_dots`` takes ``fabs`` by contract), filling
-holes, simplification.
+holes, edge-collapse (quadric-error) decimation to a target face count, the k-means step of ``get_dominant_bases``, a scale in ICP.
 """
 from __future__ import annotations
 
@@ -44,12 +51,13 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from . import geomargs, lib
+from . import geomargs, lib, voxel
 
 WELD_DIGITS = 8                    # trimesh's merge_vertices default (digits_vertex), as remembered
 CONNECTIVITIES = ("edge", "vertex")
 SIZES = ("faces", "area")          # what ``keep_largest`` ranks by
 REFERENCES = ("first", "majority", "volume", "viewpoints")          # what fixes the sign of an orientation component
+CONTRACTIONS = ("average", "quadric")          # where ``simplify_vertex_clustering`` puts a cluster's vertex
 
 
 def _check_indices(f: torch.Tensor, n: int, name: str) -> None:
@@ -482,11 +490,16 @@ def remove_degenerate_faces(mesh, zero_area: bool = False, device=None) -> Tuple
         raise ValueError(f"zero_area must be a bool, got {zero_area!r}")
     v, f = _mesh_on_device(mesh, device, "mesh", "removing degenerate faces")
     with torch.cuda.device(v.device):
-        bad = (f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 2] == f[:, 0])
-        if zero_area and f.shape[0]:
-            bad |= (lib.face_normals(v, f, False) == 0).all(dim=1)
-        kept = torch.nonzero(~bad).reshape(-1)
-        return f[kept].contiguous(), kept
+        return _without_degenerate(v, f, bool(zero_area))
+
+
+def _without_degenerate(v: torch.Tensor, f: torch.Tensor, zero_area: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``remove_degenerate_faces`` on checked device tensors, the caller's device current (``v`` is read with ``zero_area`` only)."""
+    bad = (f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 2] == f[:, 0])
+    if zero_area and f.shape[0]:
+        bad |= (lib.face_normals(v, f, False) == 0).all(dim=1)
+    kept = torch.nonzero(~bad).reshape(-1)
+    return f[kept].contiguous(), kept
 
 
 def remove_duplicate_faces(mesh, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -494,13 +507,18 @@ def remove_duplicate_faces(mesh, device=None) -> Tuple[torch.Tensor, torch.Tenso
     stays, whatever the winding.  The others keep their order."""
     v, f = _mesh_on_device(mesh, device, "mesh", "removing duplicate faces")
     with torch.cuda.device(v.device):
-        if f.shape[0] == 0:
-            return f, torch.empty(0, dtype=torch.int64, device=v.device)
-        _, triple = torch.unique(torch.sort(f, dim=1)[0], dim=0, return_inverse=True)
-        position = torch.arange(f.shape[0], dtype=torch.int64, device=v.device)
-        first = torch.full((int(triple.max()) + 1,), f.shape[0], dtype=torch.int64, device=v.device).scatter_reduce(0, triple, position, reduce="amin")
-        kept = torch.sort(first)[0]
-        return f[kept].contiguous(), kept
+        return _without_duplicates(f)
+
+
+def _without_duplicates(f: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``remove_duplicate_faces`` on checked device faces, the caller's device current."""
+    if f.shape[0] == 0:
+        return f, torch.empty(0, dtype=torch.int64, device=f.device)
+    triples, triple = torch.unique(torch.sort(f, dim=1)[0], dim=0, return_inverse=True)
+    position = torch.arange(f.shape[0], dtype=torch.int64, device=f.device)
+    first = torch.full((triples.shape[0],), f.shape[0], dtype=torch.int64, device=f.device).scatter_reduce(0, triple, position, reduce="amin")
+    kept = torch.sort(first)[0]
+    return f[kept].contiguous(), kept
 
 
 def clean(mesh, weld_digits=None, degenerate: bool = True, duplicates: bool = True, device=None, **filter_args):
@@ -534,3 +552,132 @@ def clean(mesh, weld_digits=None, degenerate: bool = True, duplicates: bool = Tr
         elif first is not None:
             inverse = torch.where(first >= 0, inverse[first.clamp(min=0)], torch.full_like(first, -1))
         return vertices, faces, kept[sub], inverse
+
+
+# ------------------------------------------------------------------------------------------------
+# vertex-clustering simplification (csrc/vfn_simplify.hip, include/vfn.h)
+# ------------------------------------------------------------------------------------------------
+class Simplified(NamedTuple):
+    """What ``simplify_vertex_clustering`` returns: device tensors, except ``n_clusters``."""
+    vertices: torch.Tensor                     # [V',3] float64: one vertex per cluster that a remaining face names, clusters in ascending key
+    faces: torch.Tensor                        # [m',3] int64: the remaining faces over the output vertices, in the input's order and winding
+    kept_faces: torch.Tensor                   # [m'] int64: the faces of the INPUT they are
+    inverse: torch.Tensor                      # [n] int64: input vertex -> output vertex; -1 where dropped, as ``weld``'s
+    colours: Optional[torch.Tensor]            # [V',3] float64 plain cluster means; None when not given
+    normals: Optional[torch.Tensor]            # [V',3] float64 plain cluster means, NOT made unit vectors again; None when not given
+    placed: torch.Tensor                       # [V'] bool: the quadric's minimiser was accepted for this vertex (all False for "average")
+    error: torch.Tensor                        # [V'] float64: the quadric's value at the output position; NaN for "average"
+    n_clusters: int                            # K (host): the occupied cells, the dropped ones included
+
+
+def _check_rcond(rcond) -> float:
+    if isinstance(rcond, bool) or not isinstance(rcond, (int, float, np.integer, np.floating)) or not math.isfinite(float(rcond)) \
+            or not 0.0 <= float(rcond) <= 1.0:
+        raise ValueError(f"rcond must be a finite number in [0, 1], got {rcond!r}")
+    return float(rcond)
+
+
+def _check_attribute(x, name: str, n: int) -> Optional[torch.Tensor]:
+    if x is None:
+        return None
+    t = geomargs.as_tensor(x, name)
+    if t.dim() != 2 or t.shape[1] != 3 or t.dtype in (torch.bool, torch.complex64, torch.complex128):
+        raise ValueError(f"{name} must be real numbers [n,3], got {t.dtype} {tuple(t.shape)}")
+    if t.shape[0] != n:
+        raise ValueError(f"{name} must have the vertices' {n} rows, got {t.shape[0]}")
+    return t
+
+
+def _cluster_items(f: torch.Tensor, cluster_of_vertex: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Device faces[m,3] (m >= 1) and every vertex's cluster -> (item_face, start[K+1]) as ``lib.cluster_quadrics`` takes them: the
+    incidences of ``_incidences`` sorted stably by the vertex's cluster, so that a cluster's items stand in ascending (vertex, face).
+    No host read (``searchsorted``, not ``bincount``)."""
+    rows, incident = _incidences(f)
+    cluster, order = torch.sort(cluster_of_vertex[rows], stable=True)
+    start = torch.searchsorted(cluster, torch.arange(k + 1, dtype=torch.int64, device=f.device))
+    return incident[order].contiguous(), start.contiguous()
+
+
+def simplify_vertex_clustering(mesh, voxel_size, contraction: str = "average", colours=None, normals=None, rcond: float = 1e-9,
+                               device=None) -> Simplified:
+    """-> ``Simplified`` on the device: the vertices of every occupied cell of edge ``voxel_size`` contracted into one, the faces that
+    collapse dropped (csrc/vfn_simplify.hip; include/vfn.h has the specification).  Only the vertices some face names take part, as
+    in ``weld``; the frame, the cells, the numbering of the clusters (ascending key) and their means are ``voxel.down_sample``'s over
+    those vertices.  ``contraction="average"`` puts a cluster's vertex at the mean of its vertices; ``"quadric"`` at the minimiser of
+    the area-weighted squared distances from the planes of the faces its vertices belong to — ten sums per cluster added by one wave
+    in the fixed order of ``vfn_cc_segment_sums``, the 3 x 3 system solved by the adjugate — where that minimiser is ACCEPTED: the
+    determinant exceeds ``rcond`` times the cube of the mean diagonal and the minimiser lies inside the cluster's cell (the in-cell test
+    is ours); every other cluster keeps its mean, with the mean's bits.  So corners and creases survive the contraction, and a flat or
+    near-singular cluster can never throw its vertex out of its cell.  ``colours`` / ``normals`` ([n,3]) follow as plain cluster means.
+    The faces are the input's with every corner replaced by its cluster, less those that name a cluster twice
+    (``remove_degenerate_faces``) and the later ones of a sorted triple (``remove_duplicate_faces``); winding and order are untouched,
+    clusters that no remaining face names are dropped.  ``"average"`` launches neither kernel of the unit.  A mesh without faces
+    returns empty tensors.
+
+    Three host reads of its own a call — the bounding box, the number of clusters with the status of the keys, the final status words —
+    beside those inside the compactions it shares with ``weld`` and ``clean`` (``nonzero``, ``unique``).  ValueError before any launch
+    on a ``voxel_size`` that is not finite and > 0 with a normal square, an unknown ``contraction``, an ``rcond`` outside [0, 1],
+    attributes without the vertices' row count, and a frame wider than 2^21 cells; a NaN / inf coordinate raises ``lib.VfnError``.
+
+    A specification of ours that follows Open3D's ``simplify_vertex_clustering`` (Average / Quadric) AS REMEMBERED, not verified
+    against Open3D or trimesh; tests/simplify_restatement.py restates it in NumPy twice and the device is held to it bit for bit."""
+    h = voxel.check_voxel_size(voxel_size)
+    if contraction not in CONTRACTIONS:
+        raise ValueError(f"contraction must be one of {CONTRACTIONS}, got {contraction!r}")
+    rcond = _check_rcond(rcond)
+    n_rows = geomargs.check_mesh(mesh, "mesh")[0].shape[0]
+    col, nrm = _check_attribute(colours, "colours", n_rows), _check_attribute(normals, "normals", n_rows)
+    v, f = _mesh_on_device(mesh, device, "mesh", "mesh simplification")
+    dev, n, m = v.device, v.shape[0], f.shape[0]
+    extras = [None if x is None else x.to(dev, torch.float64).contiguous() for x in (col, nrm)]
+    with torch.cuda.device(dev):
+        if m == 0 or n == 0:
+            none = lambda *shape, dtype=torch.float64: torch.empty(*shape, dtype=dtype, device=dev)          # noqa: E731
+            return Simplified(none(0, 3), none(0, 3, dtype=torch.int64), none(0, dtype=torch.int64),
+                              torch.full((n,), -1, dtype=torch.int64, device=dev), *(None if x is None else none(0, 3) for x in extras),
+                              none(0, dtype=torch.bool), none(0), 0)
+        used = torch.zeros(n, dtype=torch.bool, device=dev)
+        used[f.reshape(-1)] = True
+        referenced = torch.nonzero(used).reshape(-1)                      # ascending vertex index
+        vr = v[referenced].contiguous()
+        origin, _ = voxel.frame(*voxel.bounding_box(vr), h)               # read 1 (a non-finite coordinate raises here)
+        info = torch.zeros(4, dtype=torch.int64, device=dev)              # a word per stage: keys, means, planes, quadrics
+        keys = lib.voxel_keys(vr, origin, h, info=info[0:1])
+        perm, start, cluster_of_referenced, _ = voxel.table(keys, info[0:1])          # read 2: K with the status of the keys
+        k = int(start.shape[0]) - 1
+        given = [x[referenced] for x in extras if x is not None]
+        values = vr if not given else torch.cat([vr] + given, dim=1)
+        means = lib.voxel_means(values[perm].contiguous(), start, info=info[1:2])
+        cluster_of_vertex = torch.full((n,), -1, dtype=torch.int64, device=dev)
+        cluster_of_vertex[referenced] = cluster_of_referenced
+        mean_points = means[:, 0:3].contiguous()
+        if contraction == "quadric":
+            key = keys[perm[start[:-1]]]                                  # every cluster's key: (c_0 << 42) | (c_1 << 21) | c_2
+            axis_bits = lib.voxel_limits()[0].bit_length() - 1
+            mask = (1 << axis_bits) - 1
+            cells = torch.stack((key >> (2 * axis_bits), (key >> axis_bits) & mask, key & mask), dim=1).to(torch.float64)
+            centres = ((cells + 0.5) * h + torch.tensor(origin, dtype=torch.float64, device=dev)).contiguous()
+            planes = lib.face_planes(v, f, origin, info=info[2:3])
+            item_face, item_start = _cluster_items(f, cluster_of_vertex, k)
+            position, placed, error = lib.cluster_quadrics(planes, item_face, item_start, centres, mean_points, origin, h, rcond, info=info[3:4])
+            placed = placed != 0
+        else:
+            position = mean_points
+            placed = torch.zeros(k, dtype=torch.bool, device=dev)
+            error = torch.full((k,), float("nan"), dtype=torch.float64, device=dev)
+        # the faces over the clusters, cleaned; kept_faces names faces of the input
+        remapped = cluster_of_vertex[f]
+        proper, kept = _without_degenerate(position, remapped)
+        kept = kept[_without_duplicates(proper)[1]]
+        face_keep = torch.zeros(m, dtype=torch.bool, device=dev)
+        face_keep[kept] = True
+        vertices, faces, kept_faces, cluster_inverse = _select_faces(position, remapped, face_keep)
+        stays = cluster_inverse >= 0
+        inverse = torch.where(cluster_of_vertex >= 0, cluster_inverse[cluster_of_vertex.clamp(min=0)], torch.full_like(cluster_of_vertex, -1))
+        blocks = iter([means[:, c:c + 3][stays].contiguous() for c in range(3, means.shape[1], 3)])
+        out_colours, out_normals = (None if x is None else next(blocks) for x in extras)
+        _, mean_status, plane_status, quadric_status = (int(x) for x in info.cpu())          # read 3: the final status words
+        lib.voxel_check(mean_status, "mesh simplification (means)")
+        lib.simplify_check(plane_status, "mesh simplification (planes)")
+        lib.simplify_check(quadric_status, "mesh simplification (quadrics)")
+    return Simplified(vertices, faces, kept_faces, inverse, out_colours, out_normals, placed[stays], error[stays], k)
