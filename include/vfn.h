@@ -1328,6 +1328,54 @@ int vfn_cluster_quadrics(const double* planes, int64_t m, const int64_t* item_fa
                          double* position, uint8_t* placed, double* error, int64_t* info, void* stream);
 
 /* =============================================================================================
+ * Clustering points in space (csrc/vfn_kmeans.hip; vf_nerf_amd/cluster.py: kmeans; meshops.py: dominant_bases): Lloyd's k-means, the
+ * step of get_dominant_bases (utils/utils.py:216-233) that the reference leaves to sklearn.cluster.KMeans after it has decimated a mesh
+ * and taken its vertex_normals.  A SPECIFICATION of ours: the plain float64 Lloyd iteration from given seeds.  Held against
+ * scikit-learn's KMeans(init = the same seeds, n_init = 1, algorithm = "lloyd", tol = 0) on the CPU: equal labels, equal iteration
+ * counts, centres to rounding (tests/test_kmeans_host.py).  NOT verified: scikit-learn's own seeding (its greedy k-means++ and its
+ * random stream) — the seeding below is ours.  Everything is float64, evaluated without contraction in the association written here,
+ * with no floating-point atomics: every output bit is a function of the data alone.  points[n, 3] row-major, 1 <= n < 2^31,
+ * 1 <= k <= VFN_KMEANS_MAX_K.  d2(p, c) = (dx dx + dy dy) + dz dz with dx = p.x - c.x, dy = p.y - c.y, dz = p.z - c.z: the
+ * association of vfn_nn_radius.
+ *   vfn_kmeans_assign reads points, centres[k, 3] and previous[n] (int32, may be NULL); one lane per point.  label[i] (int32) = the j
+ *                     with the least d2(p_i, c_j), a tie going to the LOWEST j (the comparison is strict, j ascending; all comparisons
+ *                     are false on a NaN: label 0); sqdist[i] = that d2.  changed[0] (int64, device) is INCREASED by the number of
+ *                     points with label[i] != previous[i] — every point when previous is NULL — by an integer atomic: the count does
+ *                     not depend on the order.  previous and label may be the same array.  info bit 1 = a non-finite coordinate of a
+ *                     point or a centre.
+ *   vfn_kmeans_update reads points and label[n]; for every cluster j < k and c < 3:
+ *                       sums[j, c] = THE FIXED TREE (above, after vfn_reduce_stats) over the n values label[i] == j ? p[i, c] : +0.0,
+ *                                    lane order "near", P = ceil(n / 4096) partials per cluster
+ *                       count[j]   = the number of i with label[i] == j (int64, exact)
+ *                       centres[j, c] = sums[j, c] / (double)count[j]            where count[j] > 0
+ *                     and a cluster with count 0 KEEPS its centre: centres[k, 3] is read and written, the bits of an empty cluster's row
+ *                     are not touched; it shows in count.  A label outside [0, k): info bit 2, the point joins no cluster and nothing
+ *                     is read through the label.  info bit 1 = a non-finite coordinate.
+ *                     workspace: vfn_kmeans_update_workspace_bytes(n, k) bytes (the partials); -1 on error.
+ *   vfn_kmeans_seed   one step of farthest-point or D^2 seeding without a host read.  newest[0] (int64, DEVICE memory) names the point q
+ *                     that became a centre last:
+ *                       mind2[i] = d2(p_i, p_q)                      first != 0
+ *                       mind2[i] = min(mind2[i], d2(p_i, p_q))       first == 0   (old < d ? old : d)
+ *                     then farthest[0] (int64, device) = the i with the greatest mind2[i], a tie going to the LOWEST i; -1 when no
+ *                     mind2[i] compares (all NaN).  A maximum under a total order is associative and commutative: any reduction gives
+ *                     these bits.  newest NULL: mind2 is read as it is and only the maximum is taken.  farthest NULL: only mind2 is
+ *                     written (no workspace needed).  newest[0] outside [0, n): info bit 2, mind2 is left as it is, farthest[0] = -1
+ *                     and nothing is read through the index.  info bit 1 = a non-finite coordinate.
+ *                     workspace: vfn_kmeans_seed_workspace_bytes(n) bytes; -1 on error.
+ * The inertia is vfn_reduce_stats' sum of sqdist.  info[0] (int64, zero-filled by the caller, only OR-ed into).  Every argument check
+ * answers before any launch.
+ * ============================================================================================= */
+#define VFN_KMEANS_MAX_K 64           /* clusters of one call at most (a tile's presence mask is one 64-bit word) */
+int vfn_kmeans_assign(const double* points, int64_t n, const double* centres, int32_t k, const int32_t* previous, int32_t* label,
+                      double* sqdist, int64_t* changed, int64_t* info, void* stream);
+int64_t vfn_kmeans_update_workspace_bytes(int64_t n, int32_t k);
+int vfn_kmeans_update(const double* points, int64_t n, const int32_t* label, int32_t k, double* sums, int64_t* count, double* centres,
+                      int64_t* info, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t vfn_kmeans_seed_workspace_bytes(int64_t n);
+int vfn_kmeans_seed(const double* points, int64_t n, const int64_t* newest, int32_t first, double* mind2, int64_t* farthest,
+                    int64_t* info, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* =============================================================================================
  * Optimizer side of a training step over ONE flat fp32 buffer (train/vector_field_nerf_train.py:254-260:
  * torch.nn.utils.clip_grad_norm_(model.parameters(), clip); optimizer.step()).  The unique parameters — and their gradients
  * and Adam moments — are laid out contiguously, sorted into up to four REGIONS [start, end) of equal multiplicity `mult` =

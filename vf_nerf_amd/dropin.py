@@ -13,7 +13,7 @@ import importlib
 import sys
 import types
 
-from . import density, evaluator, grid, loss, mesh, nerf, networks, render_output, samplers, supervision, voxel
+from . import bases, density, evaluator, grid, loss, mesh, nerf, networks, render_output, samplers, supervision, voxel
 
 _ALIASES = {
     "models.nerf.vector_field_nerf": nerf,
@@ -38,7 +38,7 @@ def _ensure_package(name: str) -> None:
 
 def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scalars=None, patch_mesh: bool = True,
             patch_metrics: bool = False, patch_tsdf_mesh: bool = False, tsdf_vertex_normals=None, tsdf_sparse=None,
-            tsdf_min_component_faces=None, tsdf_simplify_voxel=None, mesh_orient=None) -> None:
+            tsdf_min_component_faces=None, tsdf_simplify_voxel=None, patch_dominant_bases: bool = False, mesh_orient=None) -> None:
     """``patch_clip=False`` leaves ``torch.nn.utils.clip_grad_norm_`` PyTorch's own function (no process-wide replacement): a step session then
     parks its gradient in the optimizer's flat buffer with every ``param.grad`` None, the trainer's clip call finds nothing to scale, and
     ``optimizer.step()`` all-reduces (more than one rank), clips with the model's ``scheduler_config.clip_norm`` — the value the trainer
@@ -67,6 +67,10 @@ def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scal
     ``tsdf_simplify_voxel`` (None: leave as is) sets ``evaluator.TSDF_SIMPLIFY_VOXEL``: a voxel edge makes ``evaluator.tsdf_mesh`` simplify
     the fused mesh by vertex clustering with quadric placement (``meshops.simplify_vertex_clustering``) after the culling and before
     it writes ``tsdf.ply``, the colours following as cluster means; the module's default is None, the mesh as fused.
+    ``patch_dominant_bases=True`` replaces ``utils.utils.get_dominant_bases`` (trimesh's decimation, scikit-learn's KMeans) with
+    ``bases.get_dominant_bases`` (same signature and return; vertex clustering, vertex normals and k-means on the device — this
+    project's bases, not a recording of the reference's: see ``vf_nerf_amd.bases``) when that module can be imported, and keeps the
+    reference's function as ``utils.utils._reference_get_dominant_bases``; off by default, and ``False`` after ``True`` puts it back.
     ``mesh_orient`` (None: leave as is) sets ``mesh.ORIENT``: "first", "majority" or "volume" makes ``mesh.contrastive_marching_cubes``
     rewind its faces consistently (``meshops.orient``) before it lists them; the module's default is None, every bit of (vs, fs) the
     reference's."""
@@ -139,6 +143,17 @@ def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scal
             mcv.contrastive_marching_cubes = mesh.contrastive_marching_cubes
         elif hasattr(mcv, "_reference_contrastive_marching_cubes"):
             mcv.contrastive_marching_cubes = mcv._reference_contrastive_marching_cubes
+    except Exception:
+        pass
+    # utils/utils.py:216-233 get_dominant_bases (trimesh + scikit-learn on the host) -> the device pipeline, only with the switch
+    try:
+        uu = importlib.import_module("utils.utils")
+        if patch_dominant_bases:
+            if not hasattr(uu, "_reference_get_dominant_bases"):
+                uu._reference_get_dominant_bases = uu.get_dominant_bases
+            uu.get_dominant_bases = bases.get_dominant_bases
+        elif hasattr(uu, "_reference_get_dominant_bases"):
+            uu.get_dominant_bases = uu._reference_get_dominant_bases
     except Exception:
         pass
     # models.helpers.functions stays the reference's module (the trainer uses more of it); only the two host-side numpy

@@ -55,6 +55,7 @@ EXPORTS = (
     "vfn_cc_union_runs", "vfn_cc_flatten", "vfn_cc_segment_sums",
     "vfn_orient_union_runs", "vfn_orient_flatten", "vfn_orient_votes",
     "vfn_face_planes", "vfn_cluster_quadrics",
+    "vfn_kmeans_assign", "vfn_kmeans_update_workspace_bytes", "vfn_kmeans_update", "vfn_kmeans_seed_workspace_bytes", "vfn_kmeans_seed",
 )
 
 
@@ -2298,6 +2299,114 @@ def cluster_quadrics(planes: torch.Tensor, item_face: torch.Tensor, start: torch
     if own:
         simplify_check(int(info.cpu()), "cluster quadrics")
     return position, placed, error
+
+
+# ------------------------------------------------------------------------------------------------
+# k-means (csrc/vfn_kmeans.hip; vf_nerf_amd/cluster.py is the public surface).  Points, centres, sums and distances float64, labels
+# int32, counts and indices int64; contiguous, on one device.
+# ------------------------------------------------------------------------------------------------
+def kmeans_max_k() -> int:
+    return header_constant("VFN_KMEANS_MAX_K")
+
+
+def kmeans_check(status: int, what: str = "k-means") -> None:
+    if status & GEOM_STATUS_NONFINITE:          # (first: a NaN leaves the seeding without a farthest point, which then shows as a bad index)
+        raise VfnError(f"{what}: a non-finite coordinate")
+    if status & GEOM_STATUS_INDEX:
+        raise VfnError(f"{what}: a label or an index lies outside its range")
+
+
+def _kmeans_points(points: torch.Tensor, what: str) -> int:
+    if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+        raise VfnError(f"{what}: points must be [n,3] with n >= 1, got {tuple(points.shape)}")
+    return points.shape[0]
+
+
+def kmeans_assign(points: torch.Tensor, centres: torch.Tensor, previous: Optional[torch.Tensor], label: torch.Tensor, sqdist: torch.Tensor,
+                  changed: torch.Tensor, info: Optional[torch.Tensor] = None) -> None:
+    """points[n,3] and centres[k,3] float64 -> label[n] (int32) = every point's nearest centre, ties to the lowest, sqdist[n] its squared
+    distance; changed (int64 [1]) is INCREASED by the number of labels that differ from ``previous`` (int32 [n]; None: every point; it
+    may be ``label`` itself) — include/vfn.h: vfn_kmeans_assign.  A bad input raises — or, with the caller's zero-filled ``info`` (int64
+    [1]), sets its bits (``kmeans_check``)."""
+    n = _kmeans_points(points, "kmeans_assign")
+    if centres.dim() != 2 or centres.shape[1] != 3 or not 1 <= centres.shape[0] <= kmeans_max_k():
+        raise VfnError(f"kmeans_assign: centres must be [k,3] with 1 <= k <= {kmeans_max_k()}, got {tuple(centres.shape)}")
+    if tuple(label.shape) != (n,) or tuple(sqdist.shape) != (n,) or (previous is not None and tuple(previous.shape) != (n,)) or changed.numel() != 1:
+        raise VfnError(f"kmeans_assign: label, sqdist and previous must have the points' {n} rows and changed one word")
+    dev, rows = points.device, _ptr(points, "points", torch.float64)          # (a host tensor is refused here, before a device is asked for)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_kmeans_assign(rows, C.c_int64(n), _ptr(centres, "centres", torch.float64),
+                                        C.c_int32(centres.shape[0]), _ptr(previous, "previous", torch.int32), _ptr(label, "label", torch.int32),
+                                        _ptr(sqdist, "sqdist", torch.float64), _ptr(changed, "changed", torch.int64), _ptr(info, "info", torch.int64),
+                                        _stream()), "vfn_kmeans_assign")
+    if own:
+        kmeans_check(int(info.cpu()), "k-means (assign)")
+
+
+def _kmeans_ws(fn_name: str, dev, *sizes) -> torch.Tensor:
+    need = getattr(load(), fn_name)(*sizes)
+    if need < 0:
+        raise VfnError(f"{fn_name}{sizes}: {load().vfn_last_error().decode()}")
+    return torch.empty(max(int(need), 8), dtype=torch.uint8, device=dev)
+
+
+def kmeans_update(points: torch.Tensor, label: torch.Tensor, centres: torch.Tensor, info: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None):
+    """points[n,3] float64, label[n] int32 and centres[k,3] float64 (READ AND WRITTEN) -> (sums[k,3] float64, count[k] int64): every
+    cluster's coordinate sums along the fixed tree, lane order "near", its exact count, and centres[j] = sums[j] / count[j] where the
+    count is not 0 — an empty cluster's row keeps its bits (include/vfn.h: vfn_kmeans_update).  ``workspace``: ``kmeans_update_workspace``'s
+    bytes, for a caller that loops.  ``info`` as in ``kmeans_assign``; a label outside [0, k) sets bit 2 and joins no cluster."""
+    n = _kmeans_points(points, "kmeans_update")
+    if centres.dim() != 2 or centres.shape[1] != 3 or not 1 <= centres.shape[0] <= kmeans_max_k():
+        raise VfnError(f"kmeans_update: centres must be [k,3] with 1 <= k <= {kmeans_max_k()}, got {tuple(centres.shape)}")
+    if tuple(label.shape) != (n,):
+        raise VfnError(f"kmeans_update: label must have the points' {n} rows, got {tuple(label.shape)}")
+    k, dev, rows = centres.shape[0], points.device, _ptr(points, "points", torch.float64)
+    sums = torch.empty(k, 3, dtype=torch.float64, device=dev)
+    count = torch.empty(k, dtype=torch.int64, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        ws = workspace if workspace is not None else kmeans_update_workspace(n, k, dev)
+        _check(load().vfn_kmeans_update(rows, C.c_int64(n), _ptr(label, "label", torch.int32), C.c_int32(k),
+                                        _ptr(sums, "sums", torch.float64), _ptr(count, "count", torch.int64), _ptr(centres, "centres", torch.float64),
+                                        _ptr(info, "info", torch.int64), _ptr(ws, "workspace", torch.uint8), C.c_int64(ws.numel()), _stream()),
+               "vfn_kmeans_update")
+    if own:
+        kmeans_check(int(info.cpu()), "k-means (update)")
+    return sums, count
+
+
+def kmeans_update_workspace(n: int, k: int, dev) -> torch.Tensor:
+    with torch.cuda.device(dev):
+        return _kmeans_ws("vfn_kmeans_update_workspace_bytes", dev, C.c_int64(n), C.c_int32(k))
+
+
+def kmeans_seed_workspace(n: int, dev) -> torch.Tensor:
+    with torch.cuda.device(dev):
+        return _kmeans_ws("vfn_kmeans_seed_workspace_bytes", dev, C.c_int64(n))
+
+
+def kmeans_seed(points: torch.Tensor, newest: Optional[torch.Tensor], first: bool, mind2: torch.Tensor, farthest: Optional[torch.Tensor],
+                info: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> None:
+    """One seeding step on the device (include/vfn.h: vfn_kmeans_seed): ``newest`` (int64 [1], DEVICE) names the point that became a
+    centre last; mind2[n] = its squared distance (``first``) or the minimum of that and what mind2 held; ``farthest`` (int64 [1]) gets
+    the index of the greatest mind2, ties to the lowest index.  ``newest`` None: mind2 is only read.  ``farthest`` None: mind2 is only
+    written.  An index outside [0, n) sets bit 2 of ``info`` (as in ``kmeans_assign``), writes -1 and reads nothing through it."""
+    n = _kmeans_points(points, "kmeans_seed")
+    if tuple(mind2.shape) != (n,) or (newest is not None and newest.numel() != 1) or (farthest is not None and farthest.numel() != 1) \
+            or (newest is None and farthest is None):
+        raise VfnError(f"kmeans_seed: mind2 must have the points' {n} rows, newest and farthest one word each (one of them may be None)")
+    dev, rows = points.device, _ptr(points, "points", torch.float64)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        ws = None if farthest is None else workspace if workspace is not None else kmeans_seed_workspace(n, dev)
+        _check(load().vfn_kmeans_seed(rows, C.c_int64(n), _ptr(newest, "newest", torch.int64),
+                                      C.c_int32(int(bool(first))), _ptr(mind2, "mind2", torch.float64), _ptr(farthest, "farthest", torch.int64),
+                                      _ptr(info, "info", torch.int64), _ptr(ws, "workspace", torch.uint8), C.c_int64(0 if ws is None else ws.numel()),
+                                      _stream()), "vfn_kmeans_seed")
+    if own:
+        kmeans_check(int(info.cpu()), "k-means (seed)")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -35,13 +35,19 @@ when it loads a mesh (methods.py:305).
   reference does before it takes ``vertex_normals`` in ``get_dominant_bases`` (utils/utils.py:216-233).  A specification of ours that
   follows Open3D's ``simplify_vertex_clustering`` (Average / Quadric) AS REMEMBERED — not verified against Open3D or trimesh;
   tests/simplify_restatement.py restates it in NumPy twice and the device is held to it bit for bit.
+* ``dominant_bases`` — the reference's ``get_dominant_bases`` (utils/utils.py:216-233) on the device: an optional ``orient``, an optional
+  decimation (``simplify_vertex_clustering`` at a voxel edge, or ``simplify_to_faces``: a fixed bisection of the voxel edge towards a
+  face count, AS SPECIFIED BY US), ``vertex_normals``, then Lloyd's k-means over them (csrc/vfn_kmeans.hip through ``cluster.kmeans``:
+  float64, sums along the fixed tree, bit for bit tests/kmeans_restatement.py), the bases in descending order of their counts.  From
+  the same seeds the iteration agrees with scikit-learn's; the seeding is ours and trimesh's edge-collapse decimation is not imitated.
 
 Inputs are numpy arrays or torch tensors on any device; a mesh is a ``mesh.Mesh`` (its ``vertices_scaled`` are used) or a
 ``(vertices, faces)`` pair.  Outputs are device tensors.  No CPU fallback: ``lib.VfnError`` when no device is visible.  A face index
 outside [0, n) is refused on the host (``ValueError``) before anything is launched.
 
 Out of scope: angle-weighted or uniform vertex normals, signed normal consistency (``vfn_normal_dots`` takes ``fabs`` by contract), filling
-holes, edge-collapse (quadric-error) decimation to a target face count, the k-means step of ``get_dominant_bases``, a scale in ICP.
+holes, edge-collapse (quadric-error) decimation to a target face count, scikit-learn's greedy k-means++ and its random stream, a
+scale in ICP.
 """
 from __future__ import annotations
 
@@ -51,7 +57,7 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from . import geomargs, lib, voxel
+from . import cluster, geomargs, lib, voxel
 
 WELD_DIGITS = 8                    # trimesh's merge_vertices default (digits_vertex), as remembered
 CONNECTIVITIES = ("edge", "vertex")
@@ -681,3 +687,124 @@ def simplify_vertex_clustering(mesh, voxel_size, contraction: str = "average", c
         lib.simplify_check(plane_status, "mesh simplification (planes)")
         lib.simplify_check(quadric_status, "mesh simplification (quadrics)")
     return Simplified(vertices, faces, kept_faces, inverse, out_colours, out_normals, placed[stays], error[stays], k)
+
+
+BISECTION_STEPS = 16               # candidates ``simplify_to_faces`` evaluates
+BISECTION_SPAN_LOG2 = 20           # its finest voxel edge: the largest extent / 2^20 (never evaluated: the first candidate is extent / 2^10)
+
+
+def simplify_to_faces(mesh, target_faces, contraction: str = "quadric", steps: int = BISECTION_STEPS, device=None) -> Tuple[Simplified, float]:
+    """-> (``Simplified``, voxel_size): ``simplify_vertex_clustering`` at a voxel edge chosen so that about ``target_faces`` faces remain.
+    AS SPECIFIED BY US, a deterministic stand-in for the reference's edge-collapse decimation to a face count
+    (``simplify_quadratic_decimation``, utils/utils.py:227), which stays out of scope: a fixed geometric bisection.  With E the largest
+    extent of the bounding box of the vertices some face names, lo = E / 2^20 and hi = E (Python floats); each of the ``steps`` steps
+    evaluates the candidate h = sqrt(lo hi) and goes to the coarser half (lo = h) iff its face count is above the target, to the finer
+    one (hi = h) otherwise.  Returned is the evaluated candidate with the most faces <= ``target_faces`` — of equals the one evaluated
+    first — or, if none qualifies, the coarsest one evaluated.  Every candidate costs the host reads of ``simplify_vertex_clustering``.
+    ValueError on a mesh without faces or without extent."""
+    target = geomargs.positive_int(target_faces, "target_faces")
+    steps = geomargs.positive_int(steps, "steps")
+    if contraction not in CONTRACTIONS:
+        raise ValueError(f"contraction must be one of {CONTRACTIONS}, got {contraction!r}")
+    if geomargs.check_mesh(mesh, "mesh")[1].shape[0] < 1:
+        raise ValueError("simplify_to_faces: the mesh has no faces")
+    v, f = _mesh_on_device(mesh, device, "mesh", "mesh simplification")
+    with torch.cuda.device(v.device):
+        used = torch.zeros(v.shape[0], dtype=torch.bool, device=v.device)
+        used[f.reshape(-1)] = True
+        lower, upper = voxel.bounding_box(v[used])
+    extent = max(hi - lo for lo, hi in zip(lower, upper))
+    if not extent > 0:
+        raise ValueError("simplify_to_faces: the mesh has no extent")
+    lo, hi = extent / 2.0 ** BISECTION_SPAN_LOG2, extent
+    fitting, coarsest = None, None          # (faces, h, Simplified)
+    for _ in range(steps):
+        h = math.sqrt(lo * hi)
+        s = simplify_vertex_clustering((v, f), h, contraction)
+        count = int(s.faces.shape[0])
+        if count > target:
+            lo = h
+        else:
+            hi = h
+            if fitting is None or count > fitting[0]:
+                fitting = (count, h, s)
+        if coarsest is None or h > coarsest[1]:
+            coarsest = (count, h, s)
+    _, h, s = fitting if fitting is not None else coarsest
+    return s, h
+
+
+# ------------------------------------------------------------------------------------------------
+# the dominant directions of a mesh (csrc/vfn_kmeans.hip through vf_nerf_amd/cluster.py)
+# ------------------------------------------------------------------------------------------------
+class DominantBases(NamedTuple):
+    """What ``dominant_bases`` returns: device tensors, except the last six."""
+    bases: torch.Tensor                        # [num_bases,3] float64: the k-means centres of the vertex normals, the dominant one first
+    counts: torch.Tensor                       # [num_bases] int64: the normals of every base, descending
+    labels: torch.Tensor                       # [V] int64: the base of every vertex normal (the vertices some face names, ascending)
+    inertia: torch.Tensor                      # [] float64
+    n_iter: int
+    converged: bool
+    n_vertices: int                            # V: the vertices whose normals were clustered
+    n_faces: int                               # the faces of the mesh they were taken on (after the simplification, if any)
+    voxel_size: Optional[float]                # the voxel edge of the simplification; None without one
+
+
+def _check_decimation(decimation) -> Optional[float]:
+    if decimation is None:
+        return None
+    if isinstance(decimation, bool) or not isinstance(decimation, (int, float, np.integer, np.floating)) or not 0.0 < float(decimation) <= 1.0:
+        raise ValueError(f"decimation must be None or a number in (0, 1], got {decimation!r}")
+    return float(decimation)
+
+
+def dominant_bases(mesh, num_bases, voxel_size=None, decimation=None, orient=None, unit: bool = False, init="farthest", n_init: int = 1,
+                   seed=None, max_iter: int = cluster.MAX_ITER, device=None) -> DominantBases:
+    """-> ``DominantBases`` on the device: the reference's ``get_dominant_bases`` (utils/utils.py:216-233) — decimate the mesh, take its
+    vertex normals, fit k-means to them, return the centres.  The steps: (1) with ``orient`` ("first", "majority" or "volume") the
+    faces are rewound consistently first (``orient``: what a contrastive marching-cubes mesh needs before its vertex normals mean
+    anything); (2) an optional simplification, by ``voxel_size`` (``simplify_vertex_clustering``, "quadric") or by ``decimation``
+    (``simplify_to_faces`` with ``target_faces = floor(decimation * faces)``, at least 1), not both; (3) ``vertex_normals`` of what is left,
+    restricted to the vertices some face names; (4) ``cluster.kmeans`` with ``init`` / ``n_init`` / ``seed`` / ``max_iter``; (5) the bases
+    ordered by descending count with a stable sort, so that the dominant one is first, ``labels`` renumbered with them; (6) with
+    ``unit=True`` each base divided by its length ``sqrt((x x + y y) + z z)``, a base without length left as it is.
+
+    The k-means is ``cluster.kmeans``' (it agrees with scikit-learn's Lloyd iteration from the same seeds; its seeding is ours, NOT
+    scikit-learn's greedy k-means++ nor its random stream), the decimation is vertex clustering AS SPECIFIED BY US, not trimesh's
+    edge collapse: the bases are this project's, not a recording of the reference's.  ValueError before any launch on bad arguments and
+    on a mesh of which nothing is left to cluster; a NaN / inf coordinate raises ``lib.VfnError``."""
+    k, init, n_init, max_iter, seed = cluster.check_arguments(num_bases, init, n_init, max_iter, seed)
+    decimation = _check_decimation(decimation)
+    h = None if voxel_size is None else voxel.check_voxel_size(voxel_size)
+    if h is not None and decimation is not None:
+        raise ValueError("dominant_bases takes voxel_size or decimation, not both")
+    if orient is not None and orient not in REFERENCES[:3]:
+        raise ValueError(f"orient must be None or one of {REFERENCES[:3]}, got {orient!r}")
+    if not isinstance(unit, (bool, np.bool_)):
+        raise ValueError(f"unit must be a bool, got {unit!r}")
+    if geomargs.check_mesh(mesh, "mesh")[1].shape[0] < 1:
+        raise ValueError("dominant_bases: the mesh has no faces")
+    v, f = _mesh_on_device(mesh, device, "mesh", "dominant bases")
+    with torch.cuda.device(v.device):
+        if orient is not None:
+            f = _rewind(f, _orientation(v, f, orient, None).flip)
+        if h is not None:
+            s = simplify_vertex_clustering((v, f), h, "quadric")
+            v, f = s.vertices, s.faces
+        elif decimation is not None:
+            s, h = simplify_to_faces((v, f), max(1, math.floor(decimation * f.shape[0])))
+            v, f = s.vertices, s.faces
+        if f.shape[0] < 1:
+            raise ValueError(f"dominant_bases: the simplification at voxel edge {h!r} leaves no face")
+        used = torch.zeros(v.shape[0], dtype=torch.bool, device=v.device)
+        used[f.reshape(-1)] = True
+        normals = vertex_normals((v, f))[used].contiguous()
+        km = cluster.kmeans(normals, k, init, n_init, max_iter, seed)
+        counts, order = torch.sort(km.counts, descending=True, stable=True)
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(k, dtype=torch.int64, device=v.device)
+        bases = km.centres[order].contiguous()
+        if unit:
+            length = torch.sqrt((bases[:, 0] * bases[:, 0] + bases[:, 1] * bases[:, 1]) + bases[:, 2] * bases[:, 2])[:, None]
+            bases = torch.where(length > 0, bases / length, bases)
+        return DominantBases(bases, counts, rank[km.labels], km.inertia, km.n_iter, km.converged, int(normals.shape[0]), int(f.shape[0]), h)
