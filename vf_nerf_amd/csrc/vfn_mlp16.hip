@@ -727,7 +727,12 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
                     if (ch > 0) epi_pair<EPI, TRAIN, !P1>(cy.pend, gmax, pr, ehi[sblk], elo[sblk], j);
                     else epi_pair<(PEPI >= 0 ? PEPI : 0), TRAIN, !P1>(cy.pend, gmax, pr, ehi[sblk], elo[sblk], j);
                     // the range guard of the pending tile, once its last pair has gone by: one integer compare into the SCALAR mask
-                    if (pr == 7 && (ch > 0 ? EPI : PEPI) == EPI_RELU) cy.sat |= __builtin_amdgcn_ballot_w64(gmax >= VFN16_CLAMP_BITS);
+                    // (the empty asm pins the OR here, into the ONE scalar pair that carries the mask: left to itself hipcc keeps every
+                    //  tile's ballot in a pair of its own — ~100 of them, spilled to VGPR lanes — and ORs them after the last tile)
+                    if (pr == 7 && (ch > 0 ? EPI : PEPI) == EPI_RELU) {
+                        cy.sat |= __builtin_amdgcn_ballot_w64(gmax >= VFN16_CLAMP_BITS);
+                        asm volatile("" : "+s"(cy.sat));
+                    }
                     if ((pr & 3) == 3) {
                         asm volatile("" : "+a"(ehi[sblk]));   // operands live in AGPRs (MFMA reads them there)
                         if constexpr (!P1) asm volatile("" : "+a"(elo[sblk]));
@@ -828,6 +833,23 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
     });
 }
 
+// Encoding geometry of a kernel instantiation: the octave counts (VF multires, rendering multires) are either the shipped pair
+// (settings.py), known at compile time — every column of an aux operand is then a register, a constant zero or nothing — or
+// ENC_RT: read from Mlp16Args at run time, which serves every other geometry the plan admits (VF 5, rendering 0 .. 5) at the
+// price of a compare-and-select chain per column.
+constexpr int ENC_RT = -1;
+constexpr int VFN16_VF_MULTIRES = 6, VFN16_RN_MULTIRES = 4;
+constexpr int enc_multires(int fixed, int run_time) { return fixed >= 0 ? fixed : run_time; }
+
+// The two lanes that share a point (lane halves g = 0, 1) exchange a value: low / high = what the lane of the lower / upper
+// half holds, in both lanes.  One v_permlane32_swap_b32 (lanes 32-63 of its first operand <-> lanes 0-31 of its second), no
+// LDS round trip (__shfl and __shfl_xor compile to ds_bpermute_b32).
+__device__ __forceinline__ void lane_half_pair(float v, float& low, float& high) {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    low = __builtin_bit_cast(float, (unsigned)r[0]); high = __builtin_bit_cast(float, (unsigned)r[1]);
+}
+
 // encoding columns [x(3), sin/cos(2^k x)...] of one 3-vector: column k of the aux operand
 __device__ __forceinline__ float enc_value(const float (&x)[3], const float (&sn)[18], const float (&cs)[18], int multires, int k) {
     if (k < 3) return x[k];
@@ -836,27 +858,35 @@ __device__ __forceinline__ float enc_value(const float (&x)[3], const float (&sn
     return rem < 3 ? sn[3 * oct + rem] : cs[3 * oct + rem - 3];
 }
 
-// aux operand from a column generator: element j of lane half g of K-block s <-> column 16 s + 8 g + j
-template <typename F>
+// aux operand from a column generator: element j of lane half g of K-block s <-> column 16 s + 8 g + j.
+// NDEF: columns >= NDEF are not defined by the encoding (48 when the geometry is a run-time value): a pair of them is a literal
+// zero, without clamp, tracking or split.  NRAW: the first NRAW columns are raw coordinates, the only ones that can leave the
+// range (sines, cosines and the tanh'ed normal are <= 1, i.e. 64 once scaled) — `ain` is folded over them alone; a non-finite
+// coordinate flags through its own column.
+template <int NDEF, int NRAW, typename F>
 __device__ __forceinline__ void build_aux(A16& aux, int g, F col, float& ain) {
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
+    static_for<3>([&](auto is) {
+        constexpr int s = decltype(is)::value;
         half8 hi, lo;
-#pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-            float v0, v1;
-            if (g == 0) { v0 = col(16 * s + j); v1 = col(16 * s + j + 1); }
-            else { v0 = col(16 * s + 8 + j); v1 = col(16 * s + 8 + j + 1); }
-            v0 *= VFN16_XSCALE; v1 *= VFN16_XSCALE;
-            // inputs beyond the f16 range (|coordinate| > ~937): clamp (no inf - inf in the split) and remember
-            v0 = fminf(fmaxf(v0, -VFN16_CLAMP), VFN16_CLAMP); v1 = fminf(fmaxf(v1, -VFN16_CLAMP), VFN16_CLAMP);
-            ain = fmaxf(ain, fmaxf(fabsf(v0), fabsf(v1)));
-            _Float16 h0, h1, l0, l1;
-            split2(v0, v1, h0, h1, l0, l1);
-            hi[j] = h0; hi[j + 1] = h1; lo[j] = l0; lo[j + 1] = l1;
-        }
+        static_for<4>([&](auto ij) {
+            constexpr int j = 2 * decltype(ij)::value;
+            if constexpr (16 * s + j >= NDEF) {      // (the other lane half's columns, 8 further on, are undefined too)
+                hi[j] = (_Float16)0.f; hi[j + 1] = (_Float16)0.f; lo[j] = (_Float16)0.f; lo[j + 1] = (_Float16)0.f;
+            } else {
+                float v0, v1;
+                if (g == 0) { v0 = col(16 * s + j); v1 = col(16 * s + j + 1); }
+                else { v0 = col(16 * s + 8 + j); v1 = col(16 * s + 8 + j + 1); }
+                v0 *= VFN16_XSCALE; v1 *= VFN16_XSCALE;
+                // inputs beyond the f16 range (|coordinate| > ~937): clamp (no inf - inf in the split) and remember
+                v0 = fminf(fmaxf(v0, -VFN16_CLAMP), VFN16_CLAMP); v1 = fminf(fmaxf(v1, -VFN16_CLAMP), VFN16_CLAMP);
+                if constexpr (16 * s + j < NRAW) ain = fmaxf(ain, fmaxf(fabsf(v0), fabsf(v1)));
+                _Float16 h0, h1, l0, l1;
+                split2(v0, v1, h0, h1, l0, l1);
+                hi[j] = h0; hi[j + 1] = h1; lo[j] = l0; lo[j + 1] = l1;
+            }
+        });
         aux.hi[s] = hi; aux.lo[s] = lo;
-    }
+    });
 }
 
 // training: this lane's columns of the encoding tile -> dst[m][40] (column 16 s + 8 g + j; 16-byte groups below 40)
@@ -887,37 +917,43 @@ __device__ __forceinline__ void load_aux(A16& ax, const float* park) {
 // sin / cos of 2^o x for the octaves o < multires of one 3-vector.  The two lanes that share a point (lane halves g = 0, 1)
 // each evaluate ONE octave of every pair (2j + g: same instruction stream, different argument) and swap results, so a lane
 // runs 3 * ceil(multires / 2) sincosf instead of 3 * multires — same inputs to the same function, so the values are
-// bit-identical to evaluating all of them.
-__device__ __forceinline__ void encode_sincos(const float (&x)[3], int multires, int g, float (&sn)[18], float (&cs)[18]) {
+// bit-identical to evaluating all of them.  MR: the octave count at compile time, or ENC_RT (then `multires` is read).
+template <int MR>
+__device__ __forceinline__ void encode_sincos(const float (&x)[3], int multires_rt, int g, float (&sn)[18], float (&cs)[18]) {
+    const int multires = enc_multires(MR, multires_rt);
 #pragma unroll
     for (int j = 0; j < 3; ++j)
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
+            if (MR >= 0 && 2 * j >= MR) {        // a pair of octaves the fixed geometry does not have: nothing to evaluate or exchange
+                sn[6 * j + c] = 0.f; cs[6 * j + c] = 0.f; sn[6 * j + 3 + c] = 0.f; cs[6 * j + 3 + c] = 0.f;
+                continue;
+            }
             float s = 0.f, k = 0.f;
             if (2 * j < multires) {
                 sincosf(x[c] * (g ? (float)(2 << (2 * j)) : (float)(1 << (2 * j))), &s, &k);
-                if (2 * j + g >= multires) { s = 0.f; k = 0.f; }      // odd multires: the pair's upper octave does not exist
+                if (g && 2 * j + 1 >= multires) { s = 0.f; k = 0.f; }      // odd multires: the pair's upper octave does not exist
             }
-            const float so = __shfl_xor(s, 32, 64), ko = __shfl_xor(k, 32, 64);
-            sn[6 * j + c] = g ? so : s;          cs[6 * j + c] = g ? ko : k;              // octave 2j
-            sn[6 * j + 3 + c] = g ? s : so;      cs[6 * j + 3 + c] = g ? k : ko;          // octave 2j + 1
+            // octave 2j is what the lower lane half evaluated, octave 2j + 1 what the upper one did — in both lanes
+            lane_half_pair(s, sn[6 * j + c], sn[6 * j + 3 + c]);
+            lane_half_pair(k, cs[6 * j + c], cs[6 * j + 3 + c]);
         }
 }
 
 // aux operand of the rendering net for one sample: [p(3), d(3), sin/cos(2^k d)(6L), n(3)]
-template <int MODE>
+template <int MODE, int RNM>
 __device__ __forceinline__ void render_aux(const Mlp16Args& a, A16& aux, const float (&xr)[3], const float (&dr)[3], const float (&nrm)[3],
                                            long long m, bool in, int g, float& ain) {
-    const int rn_multires = a.rn_multires;
+    const int rn_multires = enc_multires(RNM, a.rn_multires);
     float sn[18], cs[18];
-    encode_sincos(dr, rn_multires, g, sn, cs);
+    encode_sincos<RNM>(dr, rn_multires, g, sn, cs);
     const int ncol = 6 + 6 * rn_multires;   // first normal column
     auto rn_col = [&](int k) -> float {
         if (k < 3) return xr[k];
         if (k >= ncol) return k < ncol + 3 ? nrm[k - ncol] : 0.f;
         return enc_value(dr, sn, cs, rn_multires, k - 3);
     };
-    build_aux(aux, g, rn_col, ain);
+    build_aux<(RNM >= 0 ? 9 + 6 * RNM : 48), 6>(aux, g, rn_col, ain);      // raw columns: the point and the view direction
     if ((MODE & M16_TRAIN) && in) save_aux(a.save_aux_rn, m, g, rn_col);
 }
 
@@ -949,8 +985,9 @@ __device__ __forceinline__ void report_range(const Mlp16Args& a, unsigned long l
     }
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256, 1) void vfn_mlp16_kernel(const Mlp16Args a) {
+// The whole launch.  (VFM, RNM): the encoding geometry, see ENC_RT.
+template <int MODE, int VFM, int RNM>
+__device__ __forceinline__ void mlp16_body(const Mlp16Args& a) {
     // ONE __shared__ object: a second one beside an LDS-DMA destination makes hipcc drain vmcnt(0) before every
     // first ds_read after a DMA issue (cdna_hip_programming.md, "three .s-level traps")
     __shared__ __attribute__((aligned(16))) uint4 s_ring[3 * VFN16_SLOT + 256 * 8];
@@ -1015,7 +1052,7 @@ __global__ __launch_bounds__(256, 1) void vfn_mlp16_kernel(const Mlp16Args a) {
             for (int i = 0; i < 32; ++i) q[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_blk, goff, i * 1024, 0);
             // the encoding of the view direction (12 sincosf) while the operands are on their way: the three small loads were
             // issued before them, so their wait is a counted one
-            render_aux<MODE>(a, aux, xr, dr, nrm, -1, false, g, ain_blk);
+            render_aux<MODE, RNM>(a, aux, xr, dr, nrm, -1, false, g, ain_blk);
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 half8 h0 = __builtin_bit_cast(half8, q[4 * t + 0]), l0 = __builtin_bit_cast(half8, q[4 * t + 1]);
@@ -1081,13 +1118,13 @@ __global__ __launch_bounds__(256, 1) void vfn_mlp16_kernel(const Mlp16Args a) {
     if constexpr (mode_one(MODE)) static_for<VFN16_P1_RING - 3>([&](auto ic) { dma_chunk<MODE, 2 + decltype(ic)::value>(p, wave, lane); });
 
     // ---- positional encoding of the point -> aux operand (and its parked copy for the skip layer) -----------
-    const int vf_multires = a.vf_multires;
+    const int vf_multires = enc_multires(VFM, a.vf_multires);
     A16 aux;
     float ain = 0.f;
     {
         float sn[18], cs[18];
-        encode_sincos(x, vf_multires, g, sn, cs);
-        build_aux(aux, g, [&](int k) { return enc_value(x, sn, cs, vf_multires, k); }, ain);
+        encode_sincos<VFM>(x, vf_multires, g, sn, cs);
+        build_aux<(VFM >= 0 ? 3 + 6 * VFM : 48), 3>(aux, g, [&](int k) { return enc_value(x, sn, cs, vf_multires, k); }, ain);      // raw columns: the point
         if ((MODE & M16_TRAIN) && in) save_aux(a.save_aux_vf, mw, g, [&](int k) { return enc_value(x, sn, cs, vf_multires, k); });
         half8* pk = reinterpret_cast<half8*>(s_park + 8);
 #pragma unroll
@@ -1131,11 +1168,11 @@ __global__ __launch_bounds__(256, 1) void vfn_mlp16_kernel(const Mlp16Args a) {
     // the head's outputs sit in the lanes < 32; the other lane half of the same point needs them for the aux operand
     float nrm[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) nrm[c] = __shfl(vec[c], lane & 31, 64);
+    for (int c = 0; c < 3; ++c) { float upper; lane_half_pair(vec[c], nrm[c], upper); }
     const float xr[3] = {s_park[0], s_park[1], s_park[2]};
     const float dr[3] = {s_park[4], s_park[5], s_park[6]};
     A16 raux;
-    render_aux<MODE>(a, raux, xr, dr, nrm, (MODE & M16_TRAIN) ? mw : m, in, g, ain);
+    render_aux<MODE, RNM>(a, raux, xr, dr, nrm, (MODE & M16_TRAIN) ? mw : m, in, g, ain);
     render_tail<MODE>(a, p, cy, xa, xb, raux, nrm, a.out_index ? (long long)out_row : m, a.out_index ? out_row >= 0 : in, wave, lane);
     report_range(a, cy.sat, ain);
     if constexpr ((MODE & M16_TRAIN) == 0) {
@@ -1147,6 +1184,32 @@ __global__ __launch_bounds__(256, 1) void vfn_mlp16_kernel(const Mlp16Args a) {
     }   // rendering net
     }   // feature block
     }   // not M16_BLKIN
+}
+
+// Two kernels per mode.  vfn_mlp16_kernel<MODE> is the one the shipped networks run: its inference modes have the shipped encoding
+// geometry compiled in; the training modes read it at run time (their prologue is a smaller share of a launch that also stores its
+// workspace, and the unit's build time stays where it was).  vfn_mlp16_anyenc_kernel<MODE> is the inference launch for every other
+// geometry the plan admits.  The launchers choose (launch16).
+constexpr bool enc_fixed(int mode) { return (mode & M16_TRAIN) == 0; }
+
+template <int MODE>
+__global__ __launch_bounds__(256, 1) void vfn_mlp16_kernel(const Mlp16Args a) {
+    mlp16_body<MODE, (enc_fixed(MODE) ? VFN16_VF_MULTIRES : ENC_RT), (enc_fixed(MODE) ? VFN16_RN_MULTIRES : ENC_RT)>(a);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256, 1) void vfn_mlp16_anyenc_kernel(const Mlp16Args a) {
+    mlp16_body<MODE, ENC_RT, ENC_RT>(a);
+}
+
+// An inference launch: the compiled-in geometry when the nets this mode evaluates have it, the run-time form otherwise.
+template <int MODE>
+void launch16(const Mlp16Args& a, long long blocks, void* stream) {
+    static_assert(enc_fixed(MODE), "training modes have one kernel");
+    const bool vf_ok = (MODE & M16_BLKIN) != 0 || a.vf_multires == VFN16_VF_MULTIRES;        // (M16_BLKIN: no vector-field net in the launch)
+    const bool rn_ok = (MODE & M16_RENDER) == 0 || a.rn_multires == VFN16_RN_MULTIRES;
+    if (vf_ok && rn_ok) hipLaunchKernelGGL(vfn_mlp16_kernel<MODE>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(vfn_mlp16_anyenc_kernel<MODE>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
 }
 
 // a network's plan against the compile-time tables
@@ -1215,7 +1278,7 @@ extern "C" int vfn_vf_mlp16_fwd(const vfn_net_geom* geom, const void* packed16, 
     a.status = t_status_word;
     a.clock = t_clock_probe; a.clock_slots = t_clock_slots;
     const long long blocks = (n_points + VFN16_PTS - 1) / VFN16_PTS;
-    hipLaunchKernelGGL(vfn_mlp16_kernel<M16_VF_VEC>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    launch16<M16_VF_VEC>(a, blocks, stream);
     return vfn_check_launch("vfn_vf_mlp16_fwd");
 }
 
@@ -1247,8 +1310,8 @@ static int launch_fused16(const char* what, const vfn_net_geom* vf_geom, const v
     a.status = t_status_word;
     a.clock = t_clock_probe; a.clock_slots = t_clock_slots;
     const long long blocks = (n_points + VFN16_PTS - 1) / VFN16_PTS;
-    if (colour_products == 2) hipLaunchKernelGGL(vfn_mlp16_kernel<M16_FUSED | M16_C2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(vfn_mlp16_kernel<M16_FUSED>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    if (colour_products == 2) launch16<M16_FUSED | M16_C2>(a, blocks, stream);
+    else launch16<M16_FUSED>(a, blocks, stream);
     return vfn_check_launch(what);
 }
 
@@ -1302,7 +1365,7 @@ extern "C" int vfn_vf_feat16_fwd(const vfn_net_geom* geom, const void* packed16,
     a.status = t_status_word;
     a.clock = t_clock_probe; a.clock_slots = t_clock_slots;
     const long long blocks = (n_points + VFN16_PTS - 1) / VFN16_PTS;
-    hipLaunchKernelGGL(vfn_mlp16_kernel<M16_VF_BLK>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    launch16<M16_VF_BLK>(a, blocks, stream);
     return vfn_check_launch("vfn_vf_feat16_fwd");
 }
 
@@ -1325,7 +1388,7 @@ extern "C" int vfn_render16_from_blocks(const vfn_net_geom* rn_geom, const void*
     a.status = t_status_word;
     a.clock = t_clock_probe; a.clock_slots = t_clock_slots;
     const long long nblocks = (n_points + VFN16_PTS - 1) / VFN16_PTS;
-    hipLaunchKernelGGL(vfn_mlp16_kernel<M16_RN_BLK>, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, a);
+    launch16<M16_RN_BLK>(a, nblocks, stream);
     return vfn_check_launch("vfn_render16_from_blocks");
 }
 
