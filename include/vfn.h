@@ -1328,6 +1328,86 @@ int vfn_cluster_quadrics(const double* planes, int64_t m, const int64_t* item_fa
                          double* position, uint8_t* placed, double* error, int64_t* info, void* stream);
 
 /* =============================================================================================
+ * Decimating a triangle mesh to a face count by quadric edge collapse (csrc/vfn_collapse.hip, csrc/vfn_collapse_core.h;
+ * vf_nerf_amd/decimate.py: collapse_round, simplify_edge_collapse) — what the reference asks of trimesh's simplify_quadratic_decimation
+ * in get_dominant_bases (utils/utils.py:227).  A SPECIFICATION of ours: a ROUND-BASED, MEMORYLESS quadric-error decimation, AS SPECIFIED
+ * BY US, not verified against trimesh / Open3D and NOT their serial priority-queue order; the link condition is not tested (a known limit:
+ * a collapse may make two faces name one vertex set, of which the later is dropped by the duplicate rule).  Everything is float64,
+ * evaluated without contraction in the association written here, with no floating-point atomics: no output bit depends on the schedule.
+ * Indices, keys and tables are int64.
+ *   The call (the caller's, torch plumbing) first drops the faces that name a vertex twice and the later ones of a sorted triple, and
+ *   fixes the frame's origin o as the lower corner of the bounding box of the vertices some face names.  It then repeats a ROUND, a pure
+ *   function of (positions P[n, 3], faces F[m, 3] with m >= 1, the remaining budget):
+ *   1 Planes.         Rows 0 .. m-1 are vfn_face_planes(P, F, o).  The 3m corner pairs — all (0,1), then all (1,2), then all (2,0) — with
+ *                     key = min n + max are sorted stably; a run of equal keys is one undirected EDGE (a < b) = (key / n, key % n), edges
+ *                     numbered 0 .. E-1 in ascending key, run[e] = the length of its run.  An edge with run 1 is a BOUNDARY edge: its one
+ *                     pair names face f and the corners `from` then `to` in f's order.  The boundary edges, in ascending key, give the rows
+ *                     m .. m+B-1 (vfn_boundary_planes, one lane each), with (nf, area) = planes[f, 0..2], planes[f, 4]:
+ *                       d = P_to - P_from;   c = (d.y nf.z - d.z nf.y,  d.z nf.x - d.x nf.z,  d.x nf.y - d.y nf.x)
+ *                       s = c.x c.x;  s = s + c.y c.y;  s = s + c.z c.z;  r = sqrt(s)
+ *                     r > 0 and finite:  nrm = c / r (three divisions);  e = nrm.x (P_from.x - o.x);  e = e + nrm.y (..y);  e = e + nrm.z (..z);
+ *                       row = (nrm.x, nrm.y, nrm.z, e, boundary_weight area)
+ *                     otherwise five +0.0.  info bit 1 = a non-finite input, bit 2 = an index outside its range (nothing is read through
+ *                     it; five +0.0), bit 4 = r not finite.
+ *   2 Quadrics.       The ITEMS of a vertex are the rows it belongs to — the faces that name it, then the boundary rows of which it is an
+ *                     end — in ascending row: item_row[n_items] with start[n + 1].  vfn_vertex_quadrics, ONE LANE per vertex: for a row
+ *                     (nrm, e, w):  wn_i = w nrm_i;  we = w e;  its ten numbers
+ *                       wn_0 nrm_0, wn_0 nrm_1, wn_0 nrm_2, wn_1 nrm_1, wn_1 nrm_2, wn_2 nrm_2,  -(we nrm_0), -(we nrm_1), -(we nrm_2),  we e
+ *                     added channel by channel serially in item order STARTING from the first item (vfn_voxel_means' rule); a vertex
+ *                     without items holds ten +0.0.  Q_v(z) = z^T A z + 2 b^T z + c is the weighted sum of the squared distances of o + z
+ *                     from the vertex's planes.  A segment that is decreasing or outside [0, n_items], or a row outside [0, rows): ten
+ *                     NaN and info bit 2.
+ *   3 Candidates.     vfn_edge_collapse_candidates, one lane per edge (a, b) (csrc/vfn_collapse_core.h):
+ *                       S = Q_a + Q_b channel by channel;  d = P_b - P_a;  l2 = (d.x d.x + d.y d.y) + d.z d.z;  mid_k = 0.5 (P_a,k + P_b,k)
+ *                       m00 .. m22, det, y, x_k = -(y_k / det), t  exactly as in vfn_cluster_quadrics above
+ *                       r_k = x_k - (mid_k - o_k);   r2 = (r.x r.x + r.y r.y) + r.z r.z
+ *                     ACCEPTED iff  det > rcond ((t t) t)  and  r2 <= (reach reach) l2  (false on a NaN).  With value(z) = vfn_cluster_quadrics'
+ *                     error at z over S:
+ *                       accepted:   point_k = o_k + x_k,  value = value(x)
+ *                       otherwise:  of (mid, P_a, P_b) in this order the one with the lowest value(point - o), replaced only by a
+ *                                   strictly lower one; point = its bits
+ *                       cost = value > 0 ? value : +0.0              so a cost's bit pattern orders like its value; -0.0 never appears
+ *                       g = point - P_a;  s = ((g.x d.x + g.y d.y) + g.z d.z) / l2;  s = +0.0 unless s >= 0;  s = 1 where s > 1
+ *                     flags[e] (uint8): 2 = accepted; 4 = run > 2 (a non-manifold edge); 8 = value or point not finite (and info bit 1);
+ *                     16 = cost > max_error (max_error = +inf: no bound); and, only where none of 4, 8, 16 is set, the FLIP TEST: every
+ *                     face in the items of a, then of b, that does not name the other end, with corners (p0, p1, p2):
+ *                       c_old = (p1 - p0) x (p2 - p0) as in vfn_face_planes;  c_new = the same with the end replaced by point
+ *                       the face passes iff  (c_old.x c_new.x + c_old.y c_new.y) + c_old.z c_new.z > 0;  c_old == (0, 0, 0) imposes nothing
+ *                     32 = some face failed.  1 = the edge is a CANDIDATE: none of 4, 8, 16, 32.  An edge end, a segment, a row or a face
+ *                     corner outside its range, or an item that does not name its vertex: info bit 2, no candidate, nothing is read
+ *                     through it (ends outside [0, n) or a == b: point, cost and s are NaN).
+ *   4 Selection.      vfn_collapse_select; its result is a function of the costs alone.  Every vertex CHOOSES among the candidates it is
+ *                     an end of the lowest (cost, edge index): best_edge[n] (2^63 - 1: none; best_cost[n] is the workspace of the first
+ *                     pass).  An edge is PROPOSED iff both its ends chose it.  Then every face takes the proposed edges its three
+ *                     corners chose; if they are not all one edge, all but the lowest (cost, edge index) among them are WITHDRAWN.  Only
+ *                     the proposals are used: the rule is not recursive.  What stays (proposed and not withdrawn) is a set of edges none
+ *                     of whose 1-rings share a moving vertex, so the flip test of step 3 is exact when the collapse is applied; and the
+ *                     globally lowest candidate always stays.
+ *   5 Budget (the caller's).  The edges that stay, sorted ascending by (cost, edge index) (a stable sort of the costs over the index
+ *                     order); with a target the shortest prefix whose summed run is >= m - target_faces is TAKEN, all of them if it
+ *                     never gets there; without one, all.
+ *   6 Apply (the caller's).  For a taken edge: b -> a, P[a] = point, attr[a] = (1 - s) attr[a] + s attr[b] (two products, one sum),
+ *                     cost[a] = max(cost[a], cost[b], the edge's cost).  The faces are remapped, those that name a vertex twice and the
+ *                     later ones of a sorted triple are dropped.
+ *   7 Stop (the caller's).  m <= target_faces, a round without a taken edge, or max_rounds rounds.
+ * info[0] (int64, zero-filled by the caller, only OR-ed into).  Limits: 1 <= n, m < 2^31, 1 <= count <= 3m, m <= rows <= 4m,
+ * 1 <= E <= 3m, rcond in [0, 1], reach and boundary_weight finite and >= 0, max_error >= 0.  Every argument check answers before any
+ * launch.
+ * ============================================================================================= */
+int vfn_boundary_planes(const double* vertices, int64_t n, const double* planes, int64_t m, const int64_t* face, const int64_t* from,
+                        const int64_t* to, int64_t count, const double* origin, double boundary_weight, double* out, int64_t* info,
+                        void* stream);
+int vfn_vertex_quadrics(const double* planes, int64_t rows, const int64_t* item_row, int64_t n_items, const int64_t* start, int64_t n,
+                        double* quadrics, int64_t* info, void* stream);
+int vfn_edge_collapse_candidates(const double* vertices, int64_t n, const int64_t* faces, int64_t m, const double* quadrics,
+                                 const int64_t* item_row, int64_t n_items, const int64_t* start, int64_t rows, const int64_t* edge_a,
+                                 const int64_t* edge_b, const int64_t* run, int64_t n_edges, const double* origin, double rcond, double reach,
+                                 double max_error, double* point, double* cost, double* s, uint8_t* flags, int64_t* info, void* stream);
+int vfn_collapse_select(const double* cost, const uint8_t* flags, const int64_t* edge_a, const int64_t* edge_b, int64_t n_edges,
+                        const int64_t* faces, int64_t m, int64_t n, int64_t* best_cost, int64_t* best_edge, uint8_t* proposed,
+                        uint8_t* withdrawn, int64_t* info, void* stream);
+
+/* =============================================================================================
  * Clustering points in space (csrc/vfn_kmeans.hip; vf_nerf_amd/cluster.py: kmeans; meshops.py: dominant_bases): Lloyd's k-means, the
  * step of get_dominant_bases (utils/utils.py:216-233) that the reference leaves to sklearn.cluster.KMeans after it has decimated a mesh
  * and taken its vertex_normals.  A SPECIFICATION of ours: the plain float64 Lloyd iteration from given seeds.  Held against

@@ -13,7 +13,7 @@ import importlib
 import sys
 import types
 
-from . import bases, density, evaluator, grid, loss, mesh, nerf, networks, render_output, samplers, supervision, voxel
+from . import bases, density, evaluator, grid, loss, mesh, meshops, nerf, networks, render_output, samplers, supervision, voxel
 
 _ALIASES = {
     "models.nerf.vector_field_nerf": nerf,
@@ -38,7 +38,8 @@ def _ensure_package(name: str) -> None:
 
 def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scalars=None, patch_mesh: bool = True,
             patch_metrics: bool = False, patch_tsdf_mesh: bool = False, tsdf_vertex_normals=None, tsdf_sparse=None,
-            tsdf_min_component_faces=None, tsdf_simplify_voxel=None, patch_dominant_bases: bool = False, mesh_orient=None) -> None:
+            tsdf_min_component_faces=None, tsdf_simplify_voxel=None, dominant_bases_decimation=None, tsdf_simplify_faces=None,
+            patch_dominant_bases: bool = False, mesh_orient=None) -> None:
     """``patch_clip=False`` leaves ``torch.nn.utils.clip_grad_norm_`` PyTorch's own function (no process-wide replacement): a step session then
     parks its gradient in the optimizer's flat buffer with every ``param.grad`` None, the trainer's clip call finds nothing to scale, and
     ``optimizer.step()`` all-reduces (more than one rank), clips with the model's ``scheduler_config.clip_norm`` — the value the trainer
@@ -67,6 +68,12 @@ def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scal
     ``tsdf_simplify_voxel`` (None: leave as is) sets ``evaluator.TSDF_SIMPLIFY_VOXEL``: a voxel edge makes ``evaluator.tsdf_mesh`` simplify
     the fused mesh by vertex clustering with quadric placement (``meshops.simplify_vertex_clustering``) after the culling and before
     it writes ``tsdf.ply``, the colours following as cluster means; the module's default is None, the mesh as fused.
+    ``dominant_bases_decimation`` (None: leave as is) sets ``meshops.DECIMATION``: "collapse" makes ``meshops.dominant_bases(decimation=)``
+    reach its face count by quadric edge collapse (``meshops.simplify_edge_collapse``) instead of the bisection over vertex clusterings;
+    the module's default is "clustering".
+    ``tsdf_simplify_faces`` (None: leave as is) sets ``evaluator.TSDF_SIMPLIFY_FACES``: an integer makes ``evaluator.tsdf_mesh`` decimate
+    the fused mesh to at most about that many faces by edge collapse after the culling, the colours interpolated along the collapsed
+    edges; it cannot be combined with ``tsdf_simplify_voxel`` (ValueError); the module's default is None.
     ``patch_dominant_bases=True`` replaces ``utils.utils.get_dominant_bases`` (trimesh's decimation, scikit-learn's KMeans) with
     ``bases.get_dominant_bases`` (same signature and return; vertex clustering, vertex normals and k-means on the device — this
     project's bases, not a recording of the reference's: see ``vf_nerf_amd.bases``) when that module can be imported, and keeps the
@@ -79,12 +86,25 @@ def install(patch_evaluator: bool = True, patch_clip: bool = True, deferred_scal
         raise ValueError(f"mesh_orient must be None or one of {mesh.ORIENT_REFERENCES}, got {mesh_orient!r}")
     if tsdf_simplify_voxel is not None:
         tsdf_simplify_voxel = voxel.check_voxel_size(tsdf_simplify_voxel, "tsdf_simplify_voxel")
+    if dominant_bases_decimation is not None and dominant_bases_decimation not in meshops.DECIMATIONS:
+        raise ValueError(f"dominant_bases_decimation must be None or one of {meshops.DECIMATIONS}, got {dominant_bases_decimation!r}")
+    if tsdf_simplify_faces is not None:
+        if isinstance(tsdf_simplify_faces, bool) or not isinstance(tsdf_simplify_faces, int) or tsdf_simplify_faces < 1:
+            raise ValueError(f"tsdf_simplify_faces must be None or an integer >= 1, got {tsdf_simplify_faces!r}")
+        if (tsdf_simplify_voxel if tsdf_simplify_voxel is not None else evaluator.TSDF_SIMPLIFY_VOXEL) is not None:
+            raise ValueError("tsdf_simplify_faces cannot be combined with tsdf_simplify_voxel")
+    elif tsdf_simplify_voxel is not None and evaluator.TSDF_SIMPLIFY_FACES is not None:
+        raise ValueError("tsdf_simplify_voxel cannot be combined with tsdf_simplify_faces")
     if tsdf_min_component_faces is not None:
         if isinstance(tsdf_min_component_faces, bool) or not isinstance(tsdf_min_component_faces, int) or tsdf_min_component_faces < 0:
             raise ValueError(f"tsdf_min_component_faces must be None or an integer >= 0, got {tsdf_min_component_faces!r}")
         evaluator.TSDF_MIN_COMPONENT_FACES = tsdf_min_component_faces
     if tsdf_simplify_voxel is not None:
         evaluator.TSDF_SIMPLIFY_VOXEL = tsdf_simplify_voxel
+    if tsdf_simplify_faces is not None:
+        evaluator.TSDF_SIMPLIFY_FACES = tsdf_simplify_faces
+    if dominant_bases_decimation is not None:
+        meshops.DECIMATION = dominant_bases_decimation
     if mesh_orient is not None:
         mesh.ORIENT = mesh_orient
     if tsdf_vertex_normals is not None:

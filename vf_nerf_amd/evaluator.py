@@ -43,6 +43,9 @@ TSDF_MIN_COMPONENT_FACES = None
 # tsdf_mesh simplifies the fused mesh by vertex clustering at this voxel edge (meshops.simplify_vertex_clustering, "quadric") after the
 # component culling and before it writes tsdf.ply; None: the mesh as fused.  dropin.install(tsdf_simplify_voxel=...) sets it.
 TSDF_SIMPLIFY_VOXEL = None
+# tsdf_mesh decimates the fused mesh to at most this many faces by quadric edge collapse (meshops.simplify_edge_collapse) after the
+# component culling; None: the mesh as fused.  Not together with TSDF_SIMPLIFY_VOXEL.  dropin.install(tsdf_simplify_faces=...) sets it.
+TSDF_SIMPLIFY_FACES = None
 
 
 @torch.no_grad()
@@ -211,9 +214,13 @@ def tsdf_mesh(eval_path: str, dataset_config) -> None:
     of the fused mesh with fewer faces are culled (``meshops.filter_components``) before the file is written; colours, and the normals
     of the fused mesh if asked for, follow the vertices that stay.  With ``TSDF_SIMPLIFY_VOXEL`` set the mesh — after that culling — is
     simplified by vertex clustering at that voxel edge (``meshops.simplify_vertex_clustering``, ``"quadric"``); the colours follow as
-    cluster means and the normals, if asked for, are those of the simplified mesh.  Installed by ``dropin.install(patch_tsdf_mesh=True)``."""
+    cluster means and the normals, if asked for, are those of the simplified mesh.  With ``TSDF_SIMPLIFY_FACES`` set it is instead decimated
+    to that face count by edge collapse (``meshops.simplify_edge_collapse``), the colours interpolated along the collapsed edges and the
+    normals taken afterwards; both switches set raises ValueError.  Installed by ``dropin.install(patch_tsdf_mesh=True)``."""
     from PIL import Image
     from . import meshops, ply, tsdf
+    if TSDF_SIMPLIFY_VOXEL is not None and TSDF_SIMPLIFY_FACES is not None:
+        raise ValueError("evaluator.TSDF_SIMPLIFY_VOXEL and evaluator.TSDF_SIMPLIFY_FACES cannot both be set")
     dataset_dict = importlib.import_module("datasets.normal_datasets").dataset_dict
     dataset = dataset_dict[dataset_config.dataset_name](dataset_config)
     images_path = os.path.join(eval_path, "rendered_images")
@@ -234,11 +241,14 @@ def tsdf_mesh(eval_path: str, dataset_config) -> None:
                                                    **({"sparse": True} if TSDF_SPARSE else {}))
     mesh_path = os.path.join(eval_path, "tsdf-mesh")
     os.makedirs(mesh_path, exist_ok=True)
-    if TSDF_SIMPLIFY_VOXEL is not None:
+    if TSDF_SIMPLIFY_VOXEL is not None or TSDF_SIMPLIFY_FACES is not None:
         if TSDF_MIN_COMPONENT_FACES is not None:
             vertices, faces, _, inverse = meshops.filter_components((vertices, faces), min_faces=TSDF_MIN_COMPONENT_FACES)
             colours = colours[(inverse >= 0).to(colours.device)]
-        simple = meshops.simplify_vertex_clustering((vertices, faces), TSDF_SIMPLIFY_VOXEL, contraction="quadric", colours=colours)
+        if TSDF_SIMPLIFY_FACES is not None:
+            simple = meshops.simplify_edge_collapse((vertices, faces), target_faces=TSDF_SIMPLIFY_FACES, colours=colours)
+        else:
+            simple = meshops.simplify_vertex_clustering((vertices, faces), TSDF_SIMPLIFY_VOXEL, contraction="quadric", colours=colours)
         ply.write_ply(os.path.join(mesh_path, "tsdf.ply"), simple.vertices, simple.faces, simple.colours,
                       **({"normals": meshops.vertex_normals((simple.vertices, simple.faces))} if TSDF_VERTEX_NORMALS else {}))
     elif TSDF_MIN_COMPONENT_FACES is not None:

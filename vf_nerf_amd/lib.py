@@ -55,6 +55,7 @@ EXPORTS = (
     "vfn_cc_union_runs", "vfn_cc_flatten", "vfn_cc_segment_sums",
     "vfn_orient_union_runs", "vfn_orient_flatten", "vfn_orient_votes",
     "vfn_face_planes", "vfn_cluster_quadrics",
+    "vfn_boundary_planes", "vfn_vertex_quadrics", "vfn_edge_collapse_candidates", "vfn_collapse_select",
     "vfn_kmeans_assign", "vfn_kmeans_update_workspace_bytes", "vfn_kmeans_update", "vfn_kmeans_seed_workspace_bytes", "vfn_kmeans_seed",
 )
 
@@ -2299,6 +2300,126 @@ def cluster_quadrics(planes: torch.Tensor, item_face: torch.Tensor, start: torch
     if own:
         simplify_check(int(info.cpu()), "cluster quadrics")
     return position, placed, error
+
+
+# ------------------------------------------------------------------------------------------------
+# quadric edge-collapse decimation (csrc/vfn_collapse.hip; vf_nerf_amd/decimate.py is the public surface).  Planes, quadrics, points
+# and costs float64, indices and tables int64, the flags uint8; contiguous, on one device.
+# ------------------------------------------------------------------------------------------------
+COLLAPSE_CANDIDATE, COLLAPSE_ACCEPTED, COLLAPSE_NONMANIFOLD, COLLAPSE_NONFINITE, COLLAPSE_OVER, COLLAPSE_FLIP = 1, 2, 4, 8, 16, 32
+COLLAPSE_NO_EDGE = (1 << 63) - 1          # best_edge of a vertex without a candidate
+
+
+def collapse_check(status: int, what: str = "edge collapse") -> None:
+    if status & GEOM_STATUS_INDEX:
+        raise VfnError(f"{what}: an index, a row or a segment lies outside its range")
+    if status & GEOM_STATUS_NONFINITE:
+        raise VfnError(f"{what}: a non-finite coordinate or quadric")
+    if status & GEOM_STATUS_OVERFLOW:
+        raise VfnError(f"{what}: a normal's length overflowed")
+
+
+def boundary_planes(vertices: torch.Tensor, planes: torch.Tensor, face: torch.Tensor, start: torch.Tensor, end: torch.Tensor, origin,
+                    boundary_weight: float, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vertices[n,3], the face planes[m,5], and per boundary edge its face and its two corners in the face's order (int64 [B], B >= 1)
+    -> rows[B,5]: the plane through the edge perpendicular to its face, weighted ``boundary_weight`` times the face's area; five +0.0
+    for an edge or a face without length (include/vfn.h: vfn_boundary_planes).  ``info`` as in ``face_planes``."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or planes.dim() != 2 or planes.shape[1] != 5 or face.dim() != 1 or face.shape[0] < 1 \
+            or start.shape != face.shape or end.shape != face.shape or len(origin) != 3:
+        raise VfnError(f"boundary_planes: vertices must be [n,3], planes [m,5], face / start / end [B] with B >= 1 and origin three values, got "
+                       f"{tuple(vertices.shape)}, {tuple(planes.shape)}, {tuple(face.shape)}, {tuple(start.shape)}, {tuple(end.shape)} and {len(origin)}")
+    count, dev = face.shape[0], planes.device
+    args = (_ptr(vertices, "vertices", torch.float64), C.c_int64(vertices.shape[0]), _ptr(planes, "planes", torch.float64), C.c_int64(planes.shape[0]),
+            _ptr(face, "face", torch.int64), _ptr(start, "start", torch.int64), _ptr(end, "end", torch.int64), C.c_int64(count),
+            (C.c_double * 3)(*(float(o) for o in origin)), C.c_double(boundary_weight))
+    out = torch.empty(count, 5, dtype=torch.float64, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_boundary_planes(*args, _ptr(out, "out", torch.float64), _ptr(info, "info", torch.int64), _stream()), "vfn_boundary_planes")
+    if own:
+        collapse_check(int(info.cpu()), "boundary planes")
+    return out
+
+
+def vertex_quadrics(planes: torch.Tensor, item_row: torch.Tensor, start: torch.Tensor, info: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """planes[R,5], item_row[k] and start[n+1] (int64) -> quadrics[n,10]: every vertex's ten sums over its rows, one lane a vertex, added
+    serially from the first row (include/vfn.h: vfn_vertex_quadrics); ten +0.0 for a vertex without rows."""
+    if planes.dim() != 2 or planes.shape[1] != 5 or planes.shape[0] < 1 or item_row.dim() != 1 or item_row.shape[0] < 1 or start.dim() != 1 \
+            or start.shape[0] < 2:
+        raise VfnError(f"vertex_quadrics: planes must be [R,5] with R >= 1, item_row [k] with k >= 1 and start [n+1] with n >= 1, got "
+                       f"{tuple(planes.shape)}, {tuple(item_row.shape)} and {tuple(start.shape)}")
+    n, dev = start.shape[0] - 1, planes.device
+    args = (_ptr(planes, "planes", torch.float64), C.c_int64(planes.shape[0]), _ptr(item_row, "item_row", torch.int64), C.c_int64(item_row.shape[0]),
+            _ptr(start, "start", torch.int64), C.c_int64(n))
+    quadrics = torch.empty(n, 10, dtype=torch.float64, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_vertex_quadrics(*args, _ptr(quadrics, "quadrics", torch.float64), _ptr(info, "info", torch.int64), _stream()),
+               "vfn_vertex_quadrics")
+    if own:
+        collapse_check(int(info.cpu()), "vertex quadrics")
+    return quadrics
+
+
+def edge_collapse_candidates(vertices: torch.Tensor, faces: torch.Tensor, quadrics: torch.Tensor, item_row: torch.Tensor, start: torch.Tensor,
+                             rows: int, edge_a: torch.Tensor, edge_b: torch.Tensor, run: torch.Tensor, origin, rcond: float, reach: float,
+                             max_error: float, info: Optional[torch.Tensor] = None):
+    """-> (point[E,3], cost[E], s[E] float64, flags[E] uint8): what the collapse of every edge would do, one lane an edge — the minimiser
+    of the two ends' quadrics or the best of (midpoint, a, b), its cost, the attribute parameter, and whether the edge is a candidate
+    (``COLLAPSE_*`` bits; include/vfn.h: vfn_edge_collapse_candidates).  ``max_error`` = inf: no bound."""
+    n, m, count = vertices.shape[0], faces.shape[0], edge_a.shape[0]
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or tuple(quadrics.shape) != (n, 10) \
+            or item_row.dim() != 1 or tuple(start.shape) != (n + 1,) or edge_a.dim() != 1 or edge_b.shape != edge_a.shape or run.shape != edge_a.shape \
+            or len(origin) != 3:
+        raise VfnError(f"edge_collapse_candidates: vertices must be [n,3], faces [m,3], quadrics [n,10], item_row [k], start [n+1], edge_a / edge_b / "
+                       f"run [E] and origin three values, got {tuple(vertices.shape)}, {tuple(faces.shape)}, {tuple(quadrics.shape)}, "
+                       f"{tuple(item_row.shape)}, {tuple(start.shape)}, {tuple(edge_a.shape)}, {tuple(edge_b.shape)}, {tuple(run.shape)} and {len(origin)}")
+    if n < 1 or m < 1 or count < 1 or item_row.shape[0] < 1:
+        raise VfnError("edge_collapse_candidates: at least one vertex, face, item and edge")
+    dev = vertices.device
+    args = (_ptr(vertices, "vertices", torch.float64), C.c_int64(n), _ptr(faces, "faces", torch.int64), C.c_int64(m),
+            _ptr(quadrics, "quadrics", torch.float64), _ptr(item_row, "item_row", torch.int64), C.c_int64(item_row.shape[0]),
+            _ptr(start, "start", torch.int64), C.c_int64(rows), _ptr(edge_a, "edge_a", torch.int64), _ptr(edge_b, "edge_b", torch.int64),
+            _ptr(run, "run", torch.int64), C.c_int64(count), (C.c_double * 3)(*(float(o) for o in origin)), C.c_double(rcond), C.c_double(reach),
+            C.c_double(max_error))
+    point = torch.empty(count, 3, dtype=torch.float64, device=dev)
+    cost = torch.empty(count, dtype=torch.float64, device=dev)
+    s = torch.empty(count, dtype=torch.float64, device=dev)
+    flags = torch.empty(count, dtype=torch.uint8, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_edge_collapse_candidates(*args, _ptr(point, "point", torch.float64), _ptr(cost, "cost", torch.float64),
+                                                   _ptr(s, "s", torch.float64), _ptr(flags, "flags", torch.uint8), _ptr(info, "info", torch.int64),
+                                                   _stream()), "vfn_edge_collapse_candidates")
+    if own:
+        collapse_check(int(info.cpu()), "edge collapse candidates")
+    return point, cost, s, flags
+
+
+def collapse_select(cost: torch.Tensor, flags: torch.Tensor, edge_a: torch.Tensor, edge_b: torch.Tensor, faces: torch.Tensor, n: int,
+                    info: Optional[torch.Tensor] = None):
+    """-> (best_edge[n] int64, proposed[E], withdrawn[E] uint8): every vertex's lowest (cost, edge) among its candidates
+    (``COLLAPSE_NO_EDGE``: none), the edges both of whose ends chose them, and of those the ones some face withdrew in favour of a lower
+    one (include/vfn.h: vfn_collapse_select).  A function of the costs alone."""
+    count = cost.shape[0]
+    if cost.dim() != 1 or count < 1 or flags.shape != cost.shape or edge_a.shape != cost.shape or edge_b.shape != cost.shape or faces.dim() != 2 \
+            or faces.shape[1] != 3 or faces.shape[0] < 1 or n < 1:
+        raise VfnError(f"collapse_select: cost / flags / edge_a / edge_b must be [E] with E >= 1, faces [m,3] with m >= 1 and n >= 1, got "
+                       f"{tuple(cost.shape)}, {tuple(flags.shape)}, {tuple(edge_a.shape)}, {tuple(edge_b.shape)}, {tuple(faces.shape)} and {n}")
+    dev = cost.device
+    args = (_ptr(cost, "cost", torch.float64), _ptr(flags, "flags", torch.uint8), _ptr(edge_a, "edge_a", torch.int64), _ptr(edge_b, "edge_b", torch.int64),
+            C.c_int64(count), _ptr(faces, "faces", torch.int64), C.c_int64(faces.shape[0]), C.c_int64(n))
+    best_cost = torch.empty(n, dtype=torch.int64, device=dev)
+    best_edge = torch.empty(n, dtype=torch.int64, device=dev)
+    proposed = torch.empty(count, dtype=torch.uint8, device=dev)
+    withdrawn = torch.empty(count, dtype=torch.uint8, device=dev)
+    info, own = _own_info(info, dev)
+    with torch.cuda.device(dev):
+        _check(load().vfn_collapse_select(*args, _ptr(best_cost, "best_cost", torch.int64), _ptr(best_edge, "best_edge", torch.int64), _ptr(proposed, "proposed", torch.uint8),
+                                          _ptr(withdrawn, "withdrawn", torch.uint8), _ptr(info, "info", torch.int64), _stream()), "vfn_collapse_select")
+    if own:
+        collapse_check(int(info.cpu()), "collapse selection")
+    return best_edge, proposed, withdrawn
 
 
 # ------------------------------------------------------------------------------------------------

@@ -40,14 +40,21 @@ when it loads a mesh (methods.py:305).
   face count, AS SPECIFIED BY US), ``vertex_normals``, then Lloyd's k-means over them (csrc/vfn_kmeans.hip through ``cluster.kmeans``:
   float64, sums along the fixed tree, bit for bit tests/kmeans_restatement.py), the bases in descending order of their counts.  From
   the same seeds the iteration agrees with scikit-learn's; the seeding is ours and trimesh's edge-collapse decimation is not imitated.
+  With the module switch ``DECIMATION = "collapse"`` the decimation is ``simplify_edge_collapse`` instead.
+* ``simplify_edge_collapse`` — decimation to a face count by quadric edge collapse (``vf_nerf_amd/decimate.py``, csrc/vfn_collapse.hip,
+  include/vfn.h), re-exported here: rounds of plane quadrics per vertex (the faces' and, weighted by ``boundary_weight``, the boundary
+  edges'), per edge the minimiser of the two ends' quadrics with a flip test over both 1-rings, a selection of edges whose 1-rings
+  share no moving vertex, and of those the cheapest the remaining budget needs.  A round-based, memoryless quadric-error decimation
+  AS SPECIFIED BY US, not verified against trimesh / Open3D; tests/collapse_restatement.py restates it in NumPy twice and the device
+  is held to it bit for bit.
 
 Inputs are numpy arrays or torch tensors on any device; a mesh is a ``mesh.Mesh`` (its ``vertices_scaled`` are used) or a
 ``(vertices, faces)`` pair.  Outputs are device tensors.  No CPU fallback: ``lib.VfnError`` when no device is visible.  A face index
 outside [0, n) is refused on the host (``ValueError``) before anything is launched.
 
 Out of scope: angle-weighted or uniform vertex normals, signed normal consistency (``vfn_normal_dots`` takes ``fabs`` by contract), filling
-holes, edge-collapse (quadric-error) decimation to a target face count, scikit-learn's greedy k-means++ and its random stream, a
-scale in ICP.
+holes, trimesh's / Open3D's serial priority-queue edge-collapse order and the link condition, scikit-learn's greedy k-means++ and its
+random stream, a scale in ICP.
 """
 from __future__ import annotations
 
@@ -64,6 +71,10 @@ CONNECTIVITIES = ("edge", "vertex")
 SIZES = ("faces", "area")          # what ``keep_largest`` ranks by
 REFERENCES = ("first", "majority", "volume", "viewpoints")          # what fixes the sign of an orientation component
 CONTRACTIONS = ("average", "quadric")          # where ``simplify_vertex_clustering`` puts a cluster's vertex
+DECIMATIONS = ("clustering", "collapse")
+# how ``dominant_bases(decimation=)`` reaches its face count: "clustering" (``simplify_to_faces``) or "collapse"
+# (``simplify_edge_collapse``).  dropin.install(dominant_bases_decimation=...) sets it.
+DECIMATION = "clustering"
 
 
 def _check_indices(f: torch.Tensor, n: int, name: str) -> None:
@@ -764,7 +775,8 @@ def dominant_bases(mesh, num_bases, voxel_size=None, decimation=None, orient=Non
     vertex normals, fit k-means to them, return the centres.  The steps: (1) with ``orient`` ("first", "majority" or "volume") the
     faces are rewound consistently first (``orient``: what a contrastive marching-cubes mesh needs before its vertex normals mean
     anything); (2) an optional simplification, by ``voxel_size`` (``simplify_vertex_clustering``, "quadric") or by ``decimation``
-    (``simplify_to_faces`` with ``target_faces = floor(decimation * faces)``, at least 1), not both; (3) ``vertex_normals`` of what is left,
+    (``simplify_to_faces`` with ``target_faces = floor(decimation * faces)``, at least 1 — or, with the module switch
+    ``DECIMATION = "collapse"``, ``simplify_edge_collapse`` at that target, and ``voxel_size`` is then None), not both; (3) ``vertex_normals`` of what is left,
     restricted to the vertices some face names; (4) ``cluster.kmeans`` with ``init`` / ``n_init`` / ``seed`` / ``max_iter``; (5) the bases
     ordered by descending count with a stable sort, so that the dominant one is first, ``labels`` renumbered with them; (6) with
     ``unit=True`` each base divided by its length ``sqrt((x x + y y) + z z)``, a base without length left as it is.
@@ -782,6 +794,8 @@ def dominant_bases(mesh, num_bases, voxel_size=None, decimation=None, orient=Non
         raise ValueError(f"orient must be None or one of {REFERENCES[:3]}, got {orient!r}")
     if not isinstance(unit, (bool, np.bool_)):
         raise ValueError(f"unit must be a bool, got {unit!r}")
+    if DECIMATION not in DECIMATIONS:
+        raise ValueError(f"meshops.DECIMATION must be one of {DECIMATIONS}, got {DECIMATION!r}")
     if geomargs.check_mesh(mesh, "mesh")[1].shape[0] < 1:
         raise ValueError("dominant_bases: the mesh has no faces")
     v, f = _mesh_on_device(mesh, device, "mesh", "dominant bases")
@@ -791,11 +805,14 @@ def dominant_bases(mesh, num_bases, voxel_size=None, decimation=None, orient=Non
         if h is not None:
             s = simplify_vertex_clustering((v, f), h, "quadric")
             v, f = s.vertices, s.faces
+        elif decimation is not None and DECIMATION == "collapse":
+            s = simplify_edge_collapse((v, f), target_faces=max(1, math.floor(decimation * f.shape[0])))
+            v, f = s.vertices, s.faces
         elif decimation is not None:
             s, h = simplify_to_faces((v, f), max(1, math.floor(decimation * f.shape[0])))
             v, f = s.vertices, s.faces
         if f.shape[0] < 1:
-            raise ValueError(f"dominant_bases: the simplification at voxel edge {h!r} leaves no face")
+            raise ValueError(f"dominant_bases: the simplification at voxel edge {h!r} leaves no face")          # (None: by edge collapse)
         used = torch.zeros(v.shape[0], dtype=torch.bool, device=v.device)
         used[f.reshape(-1)] = True
         normals = vertex_normals((v, f))[used].contiguous()
@@ -808,3 +825,7 @@ def dominant_bases(mesh, num_bases, voxel_size=None, decimation=None, orient=Non
             length = torch.sqrt((bases[:, 0] * bases[:, 0] + bases[:, 1] * bases[:, 1]) + bases[:, 2] * bases[:, 2])[:, None]
             bases = torch.where(length > 0, bases / length, bases)
         return DominantBases(bases, counts, rank[km.labels], km.inertia, km.n_iter, km.converged, int(normals.shape[0]), int(f.shape[0]), h)
+
+
+# decimation to a face count by quadric edge collapse: vf_nerf_amd/decimate.py (which takes its helpers from this module at call time)
+from .decimate import Collapsed, collapse_round, simplify_edge_collapse  # noqa: E402,F401
