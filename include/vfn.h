@@ -1142,7 +1142,7 @@ int vfn_voxel_means(const double* sorted_values, int64_t n, int32_t channels, co
                     int64_t* info, void* stream);
 
 /* =============================================================================================
- * Connected components of a triangle mesh (csrc/vfn_cc.hip, csrc/vfn_cc_core.h; vf_nerf_amd/meshops.py: connected_components,
+ * Connected components of a triangle mesh (csrc/vfn_cc.hip, csrc/vfn_forest_core.h; vf_nerf_amd/meshops.py: connected_components,
  * filter_components): what a fused mesh consists of, so that its small detached pieces can be culled before it is scored.  A
  * SPECIFICATION of ours that follows Open3D's cluster_connected_triangles and trimesh's split AS REMEMBERED: neither is available to
  * compare against, and neither fixes a numbering of the components or an order of summation; ours does.  Labels, counts and tables
@@ -1166,7 +1166,7 @@ int vfn_voxel_means(const double* sorted_values, int64_t n, int32_t channels, co
  *                     vertex, node = the face.  Faces that hold one key stand next to each other: uniting neighbours unites them all.
  *   vfn_cc_union_runs reads keys[n_items] (sorted), nodes[n_items]; updates parent[n_nodes] (int32), which the CALLER fills with the
  *                     identity.  One lane per item i >= 1: where keys[i] == keys[i-1] >= 0, the trees of nodes[i-1] and nodes[i] are
- *                     united — a concurrent union-find (csrc/vfn_cc_core.h): parent[x] <= x at all times; only a root is ever hooked,
+ *                     united — a concurrent union-find (csrc/vfn_forest_core.h): parent[x] <= x at all times; only a root is ever hooked,
  *                     by a compare-and-swap parent[a]: a -> b with b < a both found as roots, the finds repeated when it fails; path
  *                     halving by compare-and-swap.  After the launch two nodes are in one tree exactly when a chain of united pairs
  *                     joins them, and every tree's root is its lowest node — whatever the schedule.  A node outside [0, n_nodes):
@@ -1190,7 +1190,7 @@ int vfn_cc_segment_sums(const double* sorted_values, int64_t n, const int64_t* s
                         void* stream);
 
 /* =============================================================================================
- * Orientation of a triangle mesh (csrc/vfn_orient.hip, csrc/vfn_orient_core.h; vf_nerf_amd/meshops.py: orientation, orient,
+ * Orientation of a triangle mesh (csrc/vfn_orient.hip, csrc/vfn_forest_core.h; vf_nerf_amd/meshops.py: orientation, orient,
  * inconsistent_edges): the faces rewound so that two faces that share a manifold edge traverse it in opposite directions — what the
  * contrastive marching-cubes mesh, whose cells choose their sides locally, does not give.  A SPECIFICATION of ours, not verified against
  * trimesh's fix_normals or Open3D's orient_triangles: neither is available to compare against, and neither fixes which face of a piece
@@ -1227,7 +1227,7 @@ int vfn_cc_segment_sums(const double* sorted_values, int64_t n, const int64_t* s
  *                     compare-and-swap sees a consistent pair — hence n_nodes < 2^30.  One lane per item i >= 1: where
  *                     keys[i-1] == keys[i] >= 0, keys[i-2] and keys[i+1] (where they exist) differ from it and nodes[i-1] != nodes[i],
  *                     the trees of the two faces are united with the parity want = (dirs[i-1] != 0) == (dirs[i] != 0) between them — a
- *                     concurrent parity union-find (csrc/vfn_orient_core.h): only a root is ever hooked, by a compare-and-swap
+ *                     concurrent parity union-find (csrc/vfn_forest_core.h): only a root is ever hooked, by a compare-and-swap
  *                     (a, 0) -> (b, q) with b < a both found as roots; path halving by compare-and-swap composes the parities of the
  *                     skipped link.  A unite whose two finds end at one root writes nothing: conflicts are not judged here.  After the
  *                     launch the trees are the components, every root is its tree's lowest node, and in an orientable component the

@@ -1,7 +1,7 @@
 """Connected components, host side: the C-ABI surface, the build recipe, the two CPU restatements of the partition
 (tests/cc_restatement.py) held against each other — and against scipy where it imports — on every shape, the union-find of
-csrc/vfn_cc_core.h run on 16 host threads by the stand-alone program tests/c_abi/cc_core_host.cpp, the argument checks that run before
-any device is asked for, and the unchanged call path of ``score_mesh`` / ``metrics_3d`` without the culling keywords."""
+csrc/vfn_forest_core.h run on 16 host threads by the stand-alone program tests/c_abi/forest_core_host.cpp (under the sanitizers where
+their runtimes exist), the argument checks that run before any device is asked for, and the unchanged call path of ``score_mesh`` / ``metrics_3d`` without the culling keywords."""
 import inspect
 import os
 import re
@@ -64,12 +64,15 @@ def test_build_recipe_lists_the_unit_in_both_places():
     build = open(os.path.join(REPO, "vf_nerf_amd", "csrc", "build.sh")).read()
     assert re.search(r'^UNITS=".*\bvfn_cc\b.*"', build, flags=re.M)
     assert re.search(r"\|vfn_cc[|)].*-ffp-contract=off", build)
-    for name in ("vfn_cc.hip", "vfn_cc_core.h"):
-        assert os.path.exists(os.path.join(REPO, "vf_nerf_amd", "csrc", name))
-    # the forest is re-read through the atomic load only, and the device and the host program compile ONE text of the loops
-    unit = open(os.path.join(REPO, "vf_nerf_amd", "csrc", "vfn_cc.hip")).read()
-    assert "__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)" in unit and '#include "vfn_cc_core.h"' in unit
-    assert "vfn_cc_core.h" in open(os.path.join(REPO, "tests", "c_abi", "cc_core_host.cpp")).read()
+    csrc = os.path.join(REPO, "vf_nerf_amd", "csrc")
+    for name in ("vfn_cc.hip", "vfn_forest_core.h", "vfn_geom.h"):
+        assert os.path.exists(os.path.join(csrc, name))
+    # the forest is re-read through the atomic load only (the shared header's, which the core includes), and the device and the host
+    # program compile ONE text of the loops
+    unit, core, geom = (open(os.path.join(csrc, name)).read() for name in ("vfn_cc.hip", "vfn_forest_core.h", "vfn_geom.h"))
+    assert "__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)" in geom and "__hip_atomic_load" not in unit + core
+    assert '#include "vfn_forest_core.h"' in unit and '#include "vfn_geom.h"' in core and "DeviceMem" in unit
+    assert "vfn_forest_core.h" in open(os.path.join(REPO, "tests", "c_abi", "forest_core_host.cpp")).read()
 
 
 def test_signatures_and_defaults():
@@ -174,23 +177,25 @@ def test_restated_properties():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# the loops of csrc/vfn_cc_core.h on 16 host threads, before any card sees them
+# the loops of csrc/vfn_forest_core.h (the plain forest) on 16 host threads, before any card sees them
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _build_host_program(tmp_path):
+def _build_host_program(tmp_path, sanitizer):
     compiler = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     assert compiler, "no host C++ compiler"
-    source = os.path.join(REPO, "tests", "c_abi", "cc_core_host.cpp")
-    exe = str(tmp_path / "cc_core_host")
+    source = os.path.join(REPO, "tests", "c_abi", "forest_core_host.cpp")
+    exe = str(tmp_path / "forest_core_host")
     base = [compiler, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-pthread", source, "-o", exe]
-    build = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True)
-    if build.returncode != 0:          # a machine without the sanitizers' runtime: the plain program (an error in the text fails it too)
+    build = subprocess.run(base + sanitizer, capture_output=True, text=True)
+    if build.returncode != 0:          # a machine without the sanitizer's runtime: the plain program (an error in the text fails it too)
         build = subprocess.run(base, capture_output=True, text=True)
     assert build.returncode == 0, build.stderr
     return exe
 
 
-def test_union_find_core_on_sixteen_host_threads(tmp_path):
-    exe = _build_host_program(tmp_path)
+@pytest.mark.parametrize("sanitizer", [["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], ["-fsanitize=thread"]],
+                         ids=["address_undefined", "thread"])
+def test_union_find_core_on_sixteen_host_threads(tmp_path, sanitizer):
+    exe = _build_host_program(tmp_path, sanitizer)
     text, want = [], []
     for name, connectivity in CASES:
         v, f = SHAPES[name]
@@ -202,7 +207,8 @@ def test_union_find_core_on_sixteen_host_threads(tmp_path):
     # negative keys unite nothing; a node outside [0, n) is not followed (neither of the two pairs it stands in) and the status says so
     text.append("4 5\n-1 0\n-1 1\n7 2\n7 9\n7 3\n")
     want.append(("bad node", None, None))
-    run = subprocess.run([exe, "16"], input="".join(text) + "0 0\n", capture_output=True, text=True, timeout=120)
+    # (the program holds its four 16-thread runs of every case to its own serial run, and exits with 4 where one differs)
+    run = subprocess.run([exe, "plain", "16"], input="".join(text) + "0 0\n", capture_output=True, text=True, timeout=120)
     assert run.returncode == 0 and run.stderr == "", (run.returncode, run.stderr[-2000:])
     lines = run.stdout.strip().split("\n")
     assert len(lines) == len(want)

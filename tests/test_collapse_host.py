@@ -218,7 +218,9 @@ def test_new_exports_are_declared_bound_and_linked():
 def test_build_recipe_lists_the_unit_in_both_places():
     build = open(os.path.join(REPO, "vf_nerf_amd", "csrc", "build.sh")).read()
     assert re.search(r'^UNITS=".*\bvfn_collapse\b.*"', build, flags=re.M)
-    assert re.search(r"\|vfn_collapse[|)].*-ffp-contract=off", build) and "-nt vfn_collapse_core.h" in build
+    assert re.search(r"\|vfn_collapse[|)].*-ffp-contract=off", build)
+    # the VFN_ONLY shortcut refuses objects older than the core: than every header beside the units, the core among them
+    assert re.search(r'for src in "\$u\.hip" \*\.h \.\./\.\./include/vfn\.h; do\n +\[ "\$OBJDIR/\$u\.o" -nt "\$src" \] \|\| fresh=0\n', build)
     for name in ("vfn_collapse.hip", "vfn_collapse_core.h"):
         assert os.path.exists(os.path.join(REPO, "vf_nerf_amd", "csrc", name))
     # the device and the host program compile ONE text of the per-edge routine; the unit has no floating-point atomic

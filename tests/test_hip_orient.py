@@ -243,7 +243,7 @@ def test_a_node_outside_its_range_sets_the_status(bad):
 @pytest.mark.parametrize("words", [[0, 0, 3 << 1, 4], [0, 0, 9 << 1, 4], [0, 0, -2, 4], [0, 0, -(1 << 31), 4], [0, 0, (1 << 31) - 1, 4],
                                    [0, 0, (2 << 1) | 1, 4], [1, 0, 0, 4], [0x55555555, 0x2AAAAAAA, -1, 0x7FFFFFFE]])
 def test_a_forest_that_is_not_ours_is_reported(words):
-    """Words whose parent leaves [0, its node], or a root word with its parity bit set: the range guard of csrc/vfn_orient_core.h ends the
+    """Words whose parent leaves [0, its node], or a root word with its parity bit set: the range guard of csrc/vfn_forest_core.h ends the
     walk before the word indexes anything.  Neither the flatten nor the unions follow it."""
     forest = dev(words, torch.int32)
     with pytest.raises(lib.VfnError, match="outside its range"):

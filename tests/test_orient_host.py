@@ -1,6 +1,6 @@
 """Orientation, host side: the C-ABI surface, the build recipe, the two CPU restatements of the parities (tests/orient_restatement.py)
 held against each other on every shape and every reference, the properties an oriented mesh must have, the parity union-find of
-csrc/vfn_orient_core.h run on 16 host threads by the stand-alone program tests/c_abi/orient_core_host.cpp (under the sanitizers where
+csrc/vfn_forest_core.h run on 16 host threads by the stand-alone program tests/c_abi/forest_core_host.cpp (under the sanitizers where
 their runtimes exist), the argument checks that run before any device is asked for, and the unchanged call path of the drop-in's
 ``contrastive_marching_cubes`` without the switch."""
 import inspect
@@ -82,13 +82,17 @@ def test_build_recipe_lists_the_unit_in_both_places():
     build = open(os.path.join(REPO, "vf_nerf_amd", "csrc", "build.sh")).read()
     assert re.search(r'^UNITS=".*\bvfn_orient\b.*"', build, flags=re.M)
     assert re.search(r"\|vfn_orient[|)].*-ffp-contract=off", build)
-    assert "-nt vfn_orient_core.h" in build                                   # the VFN_ONLY shortcut refuses objects older than the core
-    for name in ("vfn_orient.hip", "vfn_orient_core.h"):
-        assert os.path.exists(os.path.join(REPO, "vf_nerf_amd", "csrc", name))
-    # the forest is re-read through the atomic load only, and the device and the host program compile ONE text of the loops
-    unit = open(os.path.join(REPO, "vf_nerf_amd", "csrc", "vfn_orient.hip")).read()
-    assert "__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)" in unit and '#include "vfn_orient_core.h"' in unit
-    assert "vfn_orient_core.h" in open(os.path.join(REPO, "tests", "c_abi", "orient_core_host.cpp")).read()
+    # the VFN_ONLY shortcut refuses objects older than the core: than every header beside the units, the core among them
+    assert re.search(r'for src in "\$u\.hip" \*\.h \.\./\.\./include/vfn\.h; do\n +\[ "\$OBJDIR/\$u\.o" -nt "\$src" \] \|\| fresh=0\n', build)
+    csrc = os.path.join(REPO, "vf_nerf_amd", "csrc")
+    for name in ("vfn_orient.hip", "vfn_forest_core.h", "vfn_geom.h"):
+        assert os.path.exists(os.path.join(csrc, name))
+    # the forest is re-read through the atomic load only (the shared header's, which the core includes), and the device and the host
+    # program compile ONE text of the loops
+    unit, core, geom = (open(os.path.join(csrc, name)).read() for name in ("vfn_orient.hip", "vfn_forest_core.h", "vfn_geom.h"))
+    assert "__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)" in geom and "__hip_atomic_load" not in unit + core
+    assert '#include "vfn_forest_core.h"' in unit and '#include "vfn_geom.h"' in core and "DeviceMem" in unit
+    assert "vfn_forest_core.h" in open(os.path.join(REPO, "tests", "c_abi", "forest_core_host.cpp")).read()
 
 
 def test_signatures_and_defaults():
@@ -233,12 +237,12 @@ def test_golden_meshes_are_orientable_and_how_inconsistent_they_are():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# the loops of csrc/vfn_orient_core.h on 16 host threads, before any card sees them
+# the loops of csrc/vfn_forest_core.h (the parity forest) on 16 host threads, before any card sees them
 # ---------------------------------------------------------------------------------------------------------------------------------
 def _build_host_program(tmp_path, sanitizer, name):
     compiler = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     assert compiler, "no host C++ compiler"
-    source = os.path.join(REPO, "tests", "c_abi", "orient_core_host.cpp")
+    source = os.path.join(REPO, "tests", "c_abi", "forest_core_host.cpp")
     exe = str(tmp_path / name)
     base = [compiler, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-pthread", source, "-o", exe]
     build = subprocess.run(base + sanitizer, capture_output=True, text=True)
@@ -254,7 +258,7 @@ HOST_SHAPES = ("sheet_64", "strip_4096", "moebius_4097", "two_sheets", "fin", "d
 @pytest.mark.parametrize("sanitizer", [["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], ["-fsanitize=thread"]],
                          ids=["address_undefined", "thread"])
 def test_parity_union_find_core_on_sixteen_host_threads(tmp_path, sanitizer):
-    exe = _build_host_program(tmp_path, sanitizer, "orient_core_host")
+    exe = _build_host_program(tmp_path, sanitizer, "forest_core_host")
     text = []
     for name in HOST_SHAPES:
         v, f = SHAPES[name]
@@ -262,7 +266,7 @@ def test_parity_union_find_core_on_sixteen_host_threads(tmp_path, sanitizer):
         text.append(f"{len(f)} {len(keys)}\n" + "".join(f"{k} {n} {d}\n" for k, n, d in zip(keys.tolist(), nodes.tolist(), dirs.tolist())))
     # negative keys unite nothing; a node outside [0, n) is not followed and the status says so; {5: 0, 1} is a good pair wound the same way
     text.append("4 7\n-1 0 1\n-1 1 1\n5 0 1\n5 1 1\n7 2 0\n7 9 1\n8 3 0\n")
-    run = subprocess.run([exe, "16"], input="".join(text) + "0 0\n", capture_output=True, text=True, timeout=120)
+    run = subprocess.run([exe, "parity", "16"], input="".join(text) + "0 0\n", capture_output=True, text=True, timeout=120)
     assert run.returncode == 0 and run.stderr == "", (run.returncode, run.stderr[-2000:])
     lines = run.stdout.strip().split("\n")
     assert len(lines) == 3 * (len(HOST_SHAPES) + 1)

@@ -6,7 +6,8 @@ before / after them.  Round 5 found its four largest kernel gains this way (DESI
 branch per stored register quad, scalar offsets hipcc could not prove uniform compiled to a waterfall loop per store, compare + select
 masks through SGPR pairs, divergent blocks in the middle of a pipelined K loop.
 
-    python tools/isa_stats.py vfn_bwd16 [kernel-name substring] [--dump]        (needs hipcc; no GPU)"""
+    python tools/isa_stats.py vfn_bwd16 [kernel-name substring] [--dump] [--table] [--csrc DIR]        (needs hipcc; no GPU)"""
+import hashlib
 import os
 import re
 import subprocess
@@ -16,13 +17,15 @@ from collections import Counter
 unit = sys.argv[1] if len(sys.argv) > 1 else "vfn_mlp16"
 needle = sys.argv[2] if len(sys.argv) > 2 and not sys.argv[2].startswith("--") else ""
 dump = "--dump" in sys.argv
+table = "--table" in sys.argv          # one markdown row per kernel instead: instructions, branches, VGPRs, SGPRs, scratch, histogram digest
 root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vf_nerf_amd", "csrc")
-flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function"]
-if unit in ("vfn_mlp16", "vfn_bwd16"):
-    flags += ["-mllvm", "-amdgpu-mfma-vgpr-form", "-mllvm", "-pragma-unroll-threshold=10000000"]
-if unit in ("vfn_rays", "vfn_grid", "vfn_mesh", "vfn_metrics", "vfn_tsdf", "vfn_raster", "vfn_icp"):
-    flags += ["-ffp-contract=off"]
-flags += os.environ.get("VFN_%s_EXTRA" % unit[4:].upper(), "").split()
+if "--csrc" in sys.argv:               # another checkout's csrc/ (to compare two commits)
+    root = sys.argv[sys.argv.index("--csrc") + 1]
+# the unit's own flags are build.sh's: its extra_flags function (and the MFMA16 it names) is run, not restated here
+recipe = open(os.path.join(root, "build.sh")).read()
+pieces = [re.search(r"^MFMA16=.*$", recipe, re.M).group(0), re.search(r"^extra_flags\(\) \{.*?^\}", recipe, re.M | re.S).group(0)]
+extra = subprocess.run(["bash", "-c", "\n".join(pieces) + '\nextra_flags "$1"', "bash", unit], check=True, capture_output=True, text=True).stdout
+flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function"] + extra.split()
 asm = f"/tmp/{unit}.isa.s"
 subprocess.run(["hipcc", *flags, "--cuda-device-only", "-S", os.path.join(root, unit + ".hip"), "-o", asm], check=True, stderr=subprocess.DEVNULL)
 lines = open(asm).read().split("\n")
@@ -37,6 +40,11 @@ for k, (i, l) in enumerate(starts):
     mfma = sum(v for kk, v in c.items() if kk.startswith("v_mfma"))
     branches = sum(v for kk, v in c.items() if kk.startswith("s_cbranch"))
     scratch = sum(v for kk, v in c.items() if kk.startswith("scratch_"))
+    if table:
+        used = {key: int(n) for key, n in re.findall(r"^; (NumVgprs|TotalNumSgprs|ScratchSize): (\d+)", "\n".join(lines[i:end]), re.M)}
+        digest = hashlib.sha1(repr(sorted(c.items())).encode()).hexdigest()[:10]
+        print(f"| `{name}` | {len(body)} | {branches} | {used['NumVgprs']} | {used['TotalNumSgprs']} | {used['ScratchSize']} | `{digest}` |")
+        continue
     print(f"{name}\n    {len(body)} instructions, {mfma} matrix, {branches} branches ({c['s_cbranch_execnz']} execnz = waterfall / divergent loops), "
           f"{c['s_and_saveexec_b64']} saveexec, {c['v_readfirstlane_b32']} readfirstlane, {scratch} scratch accesses")
     waits = Counter(x for x in body if x.startswith("s_waitcnt"))

@@ -33,7 +33,12 @@ ONLY=${VFN_ONLY:-}
 for u in $UNITS; do
   [ -f "$u.hip" ] || { echo "build.sh: missing source $u.hip" >&2; exit 1; }
   if [ -n "$ONLY" ] && ! echo " $ONLY " | grep -q " $u "; then
-    if [ -s "$OBJDIR/$u.o" ] && [ "$OBJDIR/$u.o" -nt "$u.hip" ] && [ "$OBJDIR/$u.o" -nt vfn_common.h ] && [ "$OBJDIR/$u.o" -nt vfn_mc_tables.h ] && [ "$OBJDIR/$u.o" -nt vfn_mc_extract.h ] && [ "$OBJDIR/$u.o" -nt vfn_tree.h ] && [ "$OBJDIR/$u.o" -nt vfn_cc_core.h ] && [ "$OBJDIR/$u.o" -nt vfn_orient_core.h ] && [ "$OBJDIR/$u.o" -nt vfn_collapse_core.h ] && [ "$OBJDIR/$u.o" -nt ../../include/vfn.h ]; then
+    fresh=1          # an existing object must be newer than its source and than EVERY header here: a new header cannot be forgotten
+    [ -s "$OBJDIR/$u.o" ] || fresh=0
+    for src in "$u.hip" *.h ../../include/vfn.h; do
+      [ "$OBJDIR/$u.o" -nt "$src" ] || fresh=0
+    done
+    if [ "$fresh" = 1 ]; then
       OBJS="$OBJS $OBJDIR/$u.o"; touch "$OBJDIR/$u.remarks"; continue
     fi
     echo "build.sh: VFN_ONLY given but $u.o is missing or older than its sources" >&2; exit 1

@@ -2,55 +2,33 @@
 // mesh consists of, so that its floaters can be culled before it is scored.  A specification of ours that follows Open3D's
 // cluster_connected_triangles and trimesh's split as remembered (include/vfn.h).
 //   cc_union_runs    one lane per item of a sorted key list: equal neighbouring keys unite their two nodes in an int32 forest — a
-//                    concurrent union-find (csrc/vfn_cc_core.h has the loops, the invariant, the termination argument and why the
+//                    concurrent union-find (csrc/vfn_forest_core.h has the loops, the invariant, the termination argument and why the
 //                    result does not depend on the schedule).  Bound by the latency of dependent loads and compare-and-swaps on the
 //                    forest, not by bandwidth: 16 bytes per item are streamed, the forest words are gathered.
 //   cc_flatten       one lane per node, after the unions: where its parent chain ends.  Reads the forest, writes another array: no races.
 //   cc_segment_sums  one WAVE per segment: lane t adds elements t, t + 64, ... serially from its first one, the 64 partial sums fold as
 //                    s[t] += s[t + 32], then 16, 8, 4, 2, 1.  A wave reads 512 contiguous bytes per step.
-// The forest is re-read only through __hip_atomic_load(..., __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT): never through a plain load that
-// the compiler may keep in a register across a loop.  The orders are relaxed because the forest words are the only data: nothing else
-// is published through them.  All arithmetic of the sums is fp64 with -ffp-contract=off (build.sh).  No floating-point atomics.  No
+// The forest is re-read only through DeviceMem's relaxed agent-scope atomic load (csrc/vfn_geom.h has the load and why relaxed is enough).
+// All arithmetic of the sums is fp64 with -ffp-contract=off (build.sh).  No floating-point atomics.  No
 // node, parent or segment bound indexes memory before it has been compared with its range; no kernel returns before its wave's status
-// report, and a wave ORs its status bits into info[0] with at most one atomic (the pattern of vfn_voxel.hip).
+// report, and a wave ORs its status bits into info[0] with at most one atomic (report() of csrc/vfn_geom.h).
 #include "vfn_common.h"
-#include "vfn_cc_core.h"
+#include "vfn_forest_core.h"
 
 namespace {
+
+using namespace vfn_geom;
 
 constexpr int CC_BLOCK = 256;
 constexpr int WAVE = 64;
 constexpr int SUM_AHEAD = 16;            // loads in flight per lane of cc_segment_sums (speed only: the order of the additions is the header's)
-constexpr unsigned ST_RANGE = vfn_cc::ST_RANGE;
-
-struct DeviceMem {
-    using word = int;
-    static __device__ __forceinline__ int load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    // -> the value found: `expected` exactly when the swap happened
-    static __device__ __forceinline__ int cas(int* p, int expected, int desired) {
-        __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return expected;
-    }
-};
-
-inline unsigned blocks_for(long long n) { return (unsigned)((n + CC_BLOCK - 1) / CC_BLOCK); }
-
-// every lane of the wave arrives here (no early return in the kernels)
-__device__ __forceinline__ void report(unsigned status, unsigned long long* __restrict__ info) {
-    const unsigned long long any = __ballot(status != 0u);
-    if (any) {
-        unsigned all = status;
-        for (int o = 32; o > 0; o >>= 1) all |= (unsigned)__shfl_xor((int)all, o, 64);
-        if ((threadIdx.x & 63) == (unsigned)__builtin_ctzll(any)) atomicOr(info, (unsigned long long)all);
-    }
-}
 
 __global__ __launch_bounds__(256) void vfn_cc_union_runs_kernel(const long long* __restrict__ keys, const long long* __restrict__ nodes,
                                                                 long long n_items, int* parent, long long n_nodes,
                                                                 unsigned long long* __restrict__ info) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned status = 0;
-    if (i >= 1 && i < n_items) status = vfn_cc::union_item<DeviceMem>(keys, nodes, i, parent, n_nodes);
+    if (i >= 1 && i < n_items) status = vfn_forest::union_item<DeviceMem>(keys, nodes, i, parent, n_nodes);
     report(status, info);
 }
 
@@ -58,7 +36,7 @@ __global__ __launch_bounds__(256) void vfn_cc_flatten_kernel(const int* parent, 
                                                              unsigned long long* __restrict__ info) {
     const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned status = 0;
-    if (v < n_nodes) root[v] = (long long)vfn_cc::chain_end<DeviceMem>(parent, (int)v, &status);
+    if (v < n_nodes) root[v] = (long long)vfn_forest::chain_end<DeviceMem, 0>(parent, (int)v, &status).root;
     report(status, info);
 }
 

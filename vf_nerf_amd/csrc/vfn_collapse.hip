@@ -15,31 +15,18 @@
 //                     1 (idempotent: no atomic).
 // All arithmetic fp64 with -ffp-contract=off (build.sh).  No floating-point atomics, no LDS, no bit depends on the schedule.  Nothing is
 // read through a segment bound, a row or an index before it has been compared with its range; no kernel returns before its wave's status
-// report, and a wave ORs its status bits into info[0] with at most one atomic (the pattern of vfn_simplify.hip).
+// report, and a wave ORs its status bits into info[0] with at most one atomic (report() of csrc/vfn_geom.h).
 #include "vfn_common.h"
 #include "vfn_collapse_core.h"
-#include <math.h>
 
 namespace {
 
+using namespace vfn_geom;
 using namespace vfn_collapse;
 
 constexpr int COL_BLOCK = 256;
-constexpr unsigned ST_OVERFLOW = 4u;
 constexpr unsigned long long NO_COST = ~0ull;
 constexpr long long NO_EDGE = 0x7fffffffffffffffll;
-
-inline unsigned blocks_for(long long n) { return (unsigned)((n + COL_BLOCK - 1) / COL_BLOCK); }
-
-// every lane of the wave arrives here (no early return in the kernels)
-__device__ __forceinline__ void report(unsigned status, unsigned long long* __restrict__ info) {
-    const unsigned long long any = __ballot(status != 0u);
-    if (any) {
-        unsigned all = status;
-        for (int o = 32; o > 0; o >>= 1) all |= (unsigned)__shfl_xor((int)all, o, 64);
-        if ((threadIdx.x & 63) == (unsigned)__builtin_ctzll(any)) atomicOr(info, (unsigned long long)all);
-    }
-}
 
 __global__ __launch_bounds__(256) void vfn_boundary_planes_kernel(const double* __restrict__ v, long long n, const double* __restrict__ planes, long long m,
                                                                   const long long* __restrict__ face, const long long* __restrict__ from,
@@ -63,19 +50,10 @@ __global__ __launch_bounds__(256) void vfn_boundary_planes_kernel(const double* 
             if (!fin || !isfinite(area)) status |= ST_NONFINITE;
             const double d[3] = {pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2]};
             const double c[3] = {d[1] * nf[2] - d[2] * nf[1], d[2] * nf[0] - d[0] * nf[2], d[0] * nf[1] - d[1] * nf[0]};
-            double s = c[0] * c[0];
-            s = s + c[1] * c[1];
-            s = s + c[2] * c[2];
-            const double r = sqrt(s);
-            if (r > 0.0 && isfinite(r)) {
-                o[0] = c[0] / r; o[1] = c[1] / r; o[2] = c[2] / r;
-                double e = o[0] * (pa[0] - ox);
-                e = e + o[1] * (pa[1] - oy);
-                e = e + o[2] * (pa[2] - oz);
-                o[3] = e;
+            double r;
+            if (unit_vector(c, o, &r, status)) {
+                o[3] = plane_offset(o, pa, ox, oy, oz);
                 o[4] = weight * area;
-            } else if (!isfinite(r)) {
-                status |= ST_OVERFLOW;
             }
         }
 #pragma unroll

@@ -1,5 +1,5 @@
 // vfn_collapse_core.h — what one edge of csrc/vfn_collapse.hip (include/vfn.h: vfn_edge_collapse_candidates) computes, as ONE text that
-// compiles for the device and for the host: the sum of the two end quadrics, the adjugate solve of vfn_cluster_quadrics, the fallback to
+// compiles for the device and for the host: the sum of the two end quadrics, the solve of csrc/vfn_quadric.h, the fallback to
 // the midpoint or an end, the attribute parameter and the flip test over both 1-rings through the vertices' item table.
 // tests/c_abi/collapse_core_host.cpp runs it over small meshes under a sanitizer before it ever runs on a card.  fp64 throughout, built
 // without contraction on both sides (-ffp-contract=off): the expressions of include/vfn.h, operation for operation.  Nothing is read
@@ -7,6 +7,8 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include "vfn_geom.h"
+#include "vfn_quadric.h"
 
 #if defined(__HIPCC__)
 #define VFN_COLLAPSE_FN __host__ __device__ __forceinline__
@@ -16,8 +18,10 @@
 
 namespace vfn_collapse {
 
-constexpr int CHANNELS = 10;
-constexpr unsigned ST_NONFINITE = 1u, ST_INDEX = 2u;                               // the status bits of include/vfn.h
+using vfn_geom::ST_INDEX;
+using vfn_geom::ST_NONFINITE;
+using vfn_quadric::CHANNELS;
+using vfn_quadric::value_at;
 // the flag byte of an edge
 constexpr unsigned char F_CANDIDATE = 1, F_ACCEPTED = 2, F_NONMANIFOLD = 4, F_NONFINITE = 8, F_OVER = 16, F_FLIP = 32;
 
@@ -39,13 +43,6 @@ struct Edge {
     double point[3], cost, s;
     unsigned char flags;
 };
-
-// the quadric (ten sums) at the offset z from the origin, in the association of vfn_cluster_quadrics' error
-VFN_COLLAPSE_FN double value_at(const double* s, const double* z) {
-    const double p0 = (s[0] * z[0] + s[1] * z[1]) + s[2] * z[2], p1 = (s[1] * z[0] + s[3] * z[1]) + s[4] * z[2],
-                 p2 = (s[2] * z[0] + s[4] * z[1]) + s[5] * z[2];
-    return (((z[0] * p0 + z[1] * p1) + z[2] * p2) + 2.0 * ((s[6] * z[0] + s[7] * z[1]) + s[8] * z[2])) + s[9];
-}
 
 // the faces of vertex `moving` that do not name `other`, with `moving` at `point`: false as soon as one of them turns over.
 // -> status bits; *ok is cleared on a flip
@@ -94,17 +91,12 @@ VFN_COLLAPSE_FN unsigned edge(const Mesh& g, long long a, long long b, long long
         mid[k] = 0.5 * (pa[k] + pb[k]);
     }
     const double l2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
-    const double a00 = s[0], a01 = s[1], a02 = s[2], a11 = s[3], a12 = s[4], a22 = s[5], b0 = s[6], b1 = s[7], b2 = s[8];
-    const double m00 = a11 * a22 - a12 * a12, m01 = a02 * a12 - a01 * a22, m02 = a01 * a12 - a02 * a11;
-    const double m11 = a00 * a22 - a02 * a02, m12 = a01 * a02 - a00 * a12, m22 = a00 * a11 - a01 * a01;
-    const double det = (a00 * m00 + a01 * m01) + a02 * m02;
-    const double y0 = (m00 * b0 + m01 * b1) + m02 * b2, y1 = (m01 * b0 + m11 * b1) + m12 * b2, y2 = (m02 * b0 + m12 * b1) + m22 * b2;
-    const double x[3] = {-(y0 / det), -(y1 / det), -(y2 / det)};
-    const double t = ((a00 + a11) + a22) / 3.0;
+    const vfn_quadric::Minimiser mn = vfn_quadric::minimiser(s);
+    const double* x = mn.x;
     const double r[3] = {x[0] - (mid[0] - g.o[0]), x[1] - (mid[1] - g.o[1]), x[2] - (mid[2] - g.o[2])};
     const double r2 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
     // (every comparison is false on a NaN)
-    const bool accepted = det > g.rcond * ((t * t) * t) && r2 <= (g.reach * g.reach) * l2;
+    const bool accepted = mn.det > g.rcond * ((mn.t * mn.t) * mn.t) && r2 <= (g.reach * g.reach) * l2;
     double point[3], value;
     if (accepted) {
         for (int k = 0; k < 3; ++k) point[k] = g.o[k] + x[k];

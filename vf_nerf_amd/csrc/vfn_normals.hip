@@ -9,39 +9,20 @@
 // atomics, no LDS, no bit depends on the schedule.  These are gather kernels: every lane reads rows of 24 bytes (three doubles or three
 // int64) at scattered addresses, as three 8-byte loads — a row is 8-byte aligned, not 16.  Nothing is read through an index before the
 // index has been compared with its range.  The status bits of a wave are ORed into info[0] with at most one atomic per wave that saw
-// a bad input (the pattern of vfn_mc_count_kernel).
+// a bad input (report() of csrc/vfn_geom.h).
 #include "vfn_common.h"
-#include <math.h>
+#include "vfn_geom.h"
 
 namespace {
 
+using namespace vfn_geom;
+
 constexpr int NRM_BLOCK = 256;
-constexpr unsigned ST_NONFINITE = 1u, ST_INDEX = 2u, ST_OVERFLOW = 4u;
-
-inline unsigned blocks_for(long long n) { return (unsigned)((n + NRM_BLOCK - 1) / NRM_BLOCK); }
-
-// every lane of the wave arrives here (no early return in the kernels)
-__device__ __forceinline__ void report(unsigned status, unsigned long long* __restrict__ info) {
-    const unsigned long long any = __ballot(status != 0u);
-    if (any) {
-        unsigned all = status;
-        for (int o = 32; o > 0; o >>= 1) all |= (unsigned)__shfl_xor((int)all, o, 64);
-        if ((threadIdx.x & 63) == (unsigned)__builtin_ctzll(any)) atomicOr(info, (unsigned long long)all);
-    }
-}
 
 // unit(c, fallback) of include/vfn.h
 __device__ __forceinline__ void unit(const double c[3], double fx, double fy, double fz, double out[3], unsigned& status) {
-    double s = c[0] * c[0];
-    s = s + c[1] * c[1];
-    s = s + c[2] * c[2];
-    const double r = sqrt(s);
-    if (r > 0.0 && isfinite(r)) {
-        out[0] = c[0] / r; out[1] = c[1] / r; out[2] = c[2] / r;
-    } else {
-        out[0] = fx; out[1] = fy; out[2] = fz;
-        if (!isfinite(r)) status |= ST_OVERFLOW;
-    }
+    double r;
+    if (!unit_vector(c, out, &r, status)) { out[0] = fx; out[1] = fy; out[2] = fz; }
 }
 
 __global__ __launch_bounds__(256) void vfn_face_normals_kernel(const double* __restrict__ v, long long n, const long long* __restrict__ f, long long m,

@@ -2,7 +2,7 @@
 // mesh chooses every cell's sides locally, so neighbouring faces often traverse their shared edge the same way.  A specification of ours
 // (include/vfn.h), not verified against trimesh's fix_normals or Open3D's orient_triangles.
 //   orient_union_runs  one lane per item of the sorted half-edge list: a run of exactly two equal keys from two faces unites them in an
-//                      int32 forest whose words hold (parent << 1) | parity — a concurrent PARITY union-find (csrc/vfn_orient_core.h has
+//                      int32 forest whose words hold (parent << 1) | parity — a concurrent PARITY union-find (csrc/vfn_forest_core.h has
 //                      the loops, the invariant, the termination argument and why neither the partition nor an orientable component's
 //                      parities depend on the schedule).  Bound by the latency of dependent loads and compare-and-swaps on the forest,
 //                      not by bandwidth: 17 bytes per item are streamed (and its two neighbours' keys re-read from cache), the forest
@@ -11,48 +11,26 @@
 //                      writes two other arrays: no races.
 //   orient_votes       one lane per face: its vote for the sign of its component (six times its signed volume against the origin, or
 //                      its normal against the direction to the nearest viewpoint).  The sums are vfn_cc_segment_sums'.
-// The forest is re-read only through __hip_atomic_load(..., __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT): never through a plain load that
-// the compiler may keep in a register across a loop.  The orders are relaxed because the forest words are the only data — parent and
-// parity travel in one word — and nothing else is published through them (the reason at the top of vfn_cc.hip).  All arithmetic of
+// The forest is re-read only through DeviceMem's relaxed agent-scope atomic load (csrc/vfn_geom.h has the load and why relaxed is
+// enough: parent and parity travel in one word, and nothing else is published through it).  All arithmetic of
 // the votes is fp64 with -ffp-contract=off (build.sh).  No floating-point atomics.  No node, parent or vertex index reaches memory
 // before it has been compared with its range; no kernel returns before its wave's status report, and a wave ORs its status bits into
-// info[0] with at most one atomic (the pattern of vfn_voxel.hip).
+// info[0] with at most one atomic (report() of csrc/vfn_geom.h).
 #include "vfn_common.h"
-#include "vfn_orient_core.h"
+#include "vfn_forest_core.h"
 
 namespace {
 
+using namespace vfn_geom;
+
 constexpr int OR_BLOCK = 256;
-constexpr unsigned ST_NONFINITE = 1u, ST_RANGE = vfn_orient::ST_RANGE;
-
-struct DeviceMem {
-    using word = int;
-    static __device__ __forceinline__ int load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    // -> the value found: `expected` exactly when the swap happened
-    static __device__ __forceinline__ int cas(int* p, int expected, int desired) {
-        __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return expected;
-    }
-};
-
-inline unsigned blocks_for(long long n) { return (unsigned)((n + OR_BLOCK - 1) / OR_BLOCK); }
-
-// every lane of the wave arrives here (no early return in the kernels)
-__device__ __forceinline__ void report(unsigned status, unsigned long long* __restrict__ info) {
-    const unsigned long long any = __ballot(status != 0u);
-    if (any) {
-        unsigned all = status;
-        for (int o = 32; o > 0; o >>= 1) all |= (unsigned)__shfl_xor((int)all, o, 64);
-        if ((threadIdx.x & 63) == (unsigned)__builtin_ctzll(any)) atomicOr(info, (unsigned long long)all);
-    }
-}
 
 __global__ __launch_bounds__(256) void vfn_orient_union_runs_kernel(const long long* __restrict__ keys, const long long* __restrict__ nodes,
                                                                     const unsigned char* __restrict__ dirs, long long n_items, int* forest,
                                                                     long long n_nodes, unsigned long long* __restrict__ info) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned status = 0;
-    if (i >= 1 && i < n_items) status = vfn_orient::union_item<DeviceMem>(keys, nodes, dirs, i, n_items, forest, n_nodes);
+    if (i >= 1 && i < n_items) status = vfn_forest::union_item<DeviceMem>(keys, nodes, dirs, i, n_items, forest, n_nodes);
     report(status, info);
 }
 
@@ -61,7 +39,7 @@ __global__ __launch_bounds__(256) void vfn_orient_flatten_kernel(const int* fore
     const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned status = 0;
     if (v < n_nodes) {
-        const vfn_orient::Found e = vfn_orient::chain_end<DeviceMem>(forest, (int)v, &status);
+        const vfn_forest::Found e = vfn_forest::chain_end<DeviceMem, 1>(forest, (int)v, &status);
         root[v] = (long long)e.root;
         parity[v] = (unsigned char)e.parity;
     }

@@ -6,35 +6,25 @@
 //                     like vfn_face_normals: three rows of 24 bytes read at scattered addresses, 40 contiguous bytes written per face.
 //   cluster_quadrics  one WAVE per cluster: lane t turns the items t, t + 64, ... of the cluster's segment into their ten numbers and
 //                     adds them serially from its first item; the 64 partial sums of every channel fold as s[t] += s[t + 32], then 16,
-//                     8, 4, 2, 1 (vfn_cc_segment_sums' rule); lane 0 solves the 3 x 3 system by the adjugate, tests the minimiser and
-//                     writes.  Per item 8 bytes of the table and a gathered row of 40 bytes; a cluster of a marching-cubes mesh holds
+//                     8, 4, 2, 1 (vfn_cc_segment_sums' rule); lane 0 solves the 3 x 3 system by the adjugate (csrc/vfn_quadric.h), tests
+//                     the minimiser and writes.  Per item 8 bytes of the table and a gathered row of 40 bytes; a cluster of a marching-cubes mesh holds
 //                     a few dozen items, so most lanes of a wave idle and the kernel is bound by the latency of the two dependent
 //                     loads (the face index, then its plane), not by bandwidth.
 // All arithmetic fp64 with -ffp-contract=off (build.sh): the expressions of include/vfn.h, operation for operation.  No floating-point
 // atomics, no LDS, no bit depends on the schedule.  Nothing is read through a segment bound or a face index before it has been compared
 // with its range; no kernel returns before its wave's status report, and a wave ORs its status bits into info[0] with at most one
-// atomic (the pattern of vfn_voxel.hip).
+// atomic (report() of csrc/vfn_geom.h).
 #include "vfn_common.h"
-#include <math.h>
+#include "vfn_geom.h"
+#include "vfn_quadric.h"
 
 namespace {
 
+using namespace vfn_geom;
+using vfn_quadric::CHANNELS;
+
 constexpr int SIM_BLOCK = 256;
 constexpr int WAVE = 64;
-constexpr int CHANNELS = 10;
-constexpr unsigned ST_NONFINITE = 1u, ST_INDEX = 2u, ST_OVERFLOW = 4u;
-
-inline unsigned blocks_for(long long n) { return (unsigned)((n + SIM_BLOCK - 1) / SIM_BLOCK); }
-
-// every lane of the wave arrives here (no early return in the kernels)
-__device__ __forceinline__ void report(unsigned status, unsigned long long* __restrict__ info) {
-    const unsigned long long any = __ballot(status != 0u);
-    if (any) {
-        unsigned all = status;
-        for (int o = 32; o > 0; o >>= 1) all |= (unsigned)__shfl_xor((int)all, o, 64);
-        if ((threadIdx.x & 63) == (unsigned)__builtin_ctzll(any)) atomicOr(info, (unsigned long long)all);
-    }
-}
 
 __global__ __launch_bounds__(256) void vfn_face_planes_kernel(const double* __restrict__ v, long long n, const long long* __restrict__ f, long long m,
                                                               double ox, double oy, double oz, double* __restrict__ planes,
@@ -57,19 +47,10 @@ __global__ __launch_bounds__(256) void vfn_face_planes_kernel(const double* __re
             const double a[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
             const double b[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
             const double c[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
-            double s = c[0] * c[0];
-            s = s + c[1] * c[1];
-            s = s + c[2] * c[2];
-            const double r = sqrt(s);
-            if (r > 0.0 && isfinite(r)) {
-                o[0] = c[0] / r; o[1] = c[1] / r; o[2] = c[2] / r;
-                double e = o[0] * (p0[0] - ox);
-                e = e + o[1] * (p0[1] - oy);
-                e = e + o[2] * (p0[2] - oz);
-                o[3] = e;
+            double r;
+            if (unit_vector(c, o, &r, status)) {
+                o[3] = plane_offset(o, p0, ox, oy, oz);
                 o[4] = 0.5 * r;
-            } else if (!isfinite(r)) {
-                status |= ST_OVERFLOW;
             }
         }
 #pragma unroll
@@ -134,16 +115,11 @@ __global__ __launch_bounds__(256) void vfn_cluster_quadrics_kernel(const double*
                 status |= ST_INDEX;
                 out[0] = out[1] = out[2] = err = __builtin_nan("");
             } else {
-                const double a00 = s[0], a01 = s[1], a02 = s[2], a11 = s[3], a12 = s[4], a22 = s[5], b0 = s[6], b1 = s[7], b2 = s[8];
-                const double m00 = a11 * a22 - a12 * a12, m01 = a02 * a12 - a01 * a22, m02 = a01 * a12 - a02 * a11;
-                const double m11 = a00 * a22 - a02 * a02, m12 = a01 * a02 - a00 * a12, m22 = a00 * a11 - a01 * a01;
-                const double det = (a00 * m00 + a01 * m01) + a02 * m02;
-                const double y0 = (m00 * b0 + m01 * b1) + m02 * b2, y1 = (m01 * b0 + m11 * b1) + m12 * b2, y2 = (m02 * b0 + m12 * b1) + m22 * b2;
-                const double x[3] = {-(y0 / det), -(y1 / det), -(y2 / det)};
-                const double t = ((a00 + a11) + a22) / 3.0;
+                const vfn_quadric::Minimiser mn = vfn_quadric::minimiser(s);
+                const double* x = mn.x;
                 const double half = 0.5 * h;
                 // (every comparison is false on a NaN)
-                const bool accepted = det > rcond * ((t * t) * t) && fabs(x[0]) <= half && fabs(x[1]) <= half && fabs(x[2]) <= half;
+                const bool accepted = mn.det > rcond * ((mn.t * mn.t) * mn.t) && fabs(x[0]) <= half && fabs(x[1]) <= half && fabs(x[2]) <= half;
                 double z[3];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
@@ -151,9 +127,7 @@ __global__ __launch_bounds__(256) void vfn_cluster_quadrics_kernel(const double*
                     out[k] = accepted ? g[k] + x[k] : mean;
                     z[k] = accepted ? x[k] : mean - g[k];
                 }
-                const double p0 = (a00 * z[0] + a01 * z[1]) + a02 * z[2], p1 = (a01 * z[0] + a11 * z[1]) + a12 * z[2],
-                             p2 = (a02 * z[0] + a12 * z[1]) + a22 * z[2];
-                err = (((z[0] * p0 + z[1] * p1) + z[2] * p2) + 2.0 * ((b0 * z[0] + b1 * z[1]) + b2 * z[2])) + s[9];
+                err = vfn_quadric::value_at(s, z);
                 ok = accepted ? 1 : 0;
             }
             position[3 * q] = out[0]; position[3 * q + 1] = out[1]; position[3 * q + 2] = out[2];

@@ -8,29 +8,18 @@
 //                on the running sum.  A voxel holding every point is walked by one lane: slow, and correct.
 // All arithmetic fp64 with -ffp-contract=off (build.sh): the expressions of include/vfn.h, operation for operation.  No floating-point
 // atomics, no LDS, no bit depends on the schedule.  No key indexes memory; a segment is followed only after both its bounds have been
-// compared with [0, n].  The status bits of a wave are ORed into info[0] with at most one atomic per wave that saw a bad input (the
-// pattern of vfn_normals.hip).
+// compared with [0, n].  The status bits of a wave are ORed into info[0] with at most one atomic per wave that saw a bad input
+// (report() of csrc/vfn_geom.h).
 #include "vfn_common.h"
-#include <math.h>
+#include "vfn_geom.h"
 
 namespace {
 
+using namespace vfn_geom;
+
 constexpr int VOX_BLOCK = 256;
-constexpr unsigned ST_NONFINITE = 1u, ST_RANGE = 2u;
 constexpr int AXIS_BITS = VFN_VOXEL_AXIS_BITS;
 constexpr double AXIS_CELLS = (double)(1ll << AXIS_BITS);
-
-inline unsigned blocks_for(long long n) { return (unsigned)((n + VOX_BLOCK - 1) / VOX_BLOCK); }
-
-// every lane of the wave arrives here (no early return in the kernels)
-__device__ __forceinline__ void report(unsigned status, unsigned long long* __restrict__ info) {
-    const unsigned long long any = __ballot(status != 0u);
-    if (any) {
-        unsigned all = status;
-        for (int o = 32; o > 0; o >>= 1) all |= (unsigned)__shfl_xor((int)all, o, 64);
-        if ((threadIdx.x & 63) == (unsigned)__builtin_ctzll(any)) atomicOr(info, (unsigned long long)all);
-    }
-}
 
 __global__ __launch_bounds__(256) void vfn_voxel_keys_kernel(const double* __restrict__ p, long long n, double ox, double oy, double oz, double h,
                                                              long long* __restrict__ keys, unsigned long long* __restrict__ info) {

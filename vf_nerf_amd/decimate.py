@@ -191,9 +191,7 @@ def simplify_edge_collapse(mesh, target_faces=None, max_error=None, boundary_wei
         absorbed = torch.zeros(n, dtype=torch.float64, device=dev)
         rounds = collapsed = 0
         if f.shape[0]:
-            used = torch.zeros(n, dtype=torch.bool, device=dev)
-            used[f.reshape(-1)] = True
-            origin = voxel.bounding_box(v[used])[0]                   # (a non-finite coordinate raises here)
+            origin = voxel.bounding_box(v[meshops._referenced(f, n)])[0]          # (a non-finite coordinate raises here)
         while f.shape[0] and (target is None or f.shape[0] > target) and rounds < max_rounds:
             r = collapse_round(position, f, origin, target, max_error, boundary_weight, rcond, reach)
             rounds += 1
@@ -214,8 +212,7 @@ def simplify_edge_collapse(mesh, target_faces=None, max_error=None, boundary_wei
             f, sub = meshops._without_duplicates(f)
             kept = kept[sub]
             collapsed += r.n_taken
-        used = torch.zeros(n, dtype=torch.bool, device=dev)
-        used[f.reshape(-1)] = True
+        used = meshops._referenced(f, n)
         number = torch.where(used, torch.cumsum(used, dim=0) - 1, torch.full((n,), -1, dtype=torch.int64, device=dev))
         out_colours, out_normals = (None if x is None else x[used].contiguous() for x in extras)
         return Collapsed(position[used].contiguous(), number[f].reshape(-1, 3).contiguous(), kept.contiguous(), number[owner].contiguous(),

@@ -108,6 +108,13 @@ def face_normals(mesh, normalise: bool = True, device=None) -> torch.Tensor:
     return lib.face_normals(v, f, bool(normalise))
 
 
+def _referenced(faces: torch.Tensor, n_vertices: int) -> torch.Tensor:
+    """Device faces (any shape, checked) -> used[n] bool: the vertices some face names."""
+    used = torch.zeros(n_vertices, dtype=torch.bool, device=faces.device)
+    used[faces.reshape(-1)] = True
+    return used
+
+
 def _incidences(faces: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """faces[m,3], m >= 1 -> (vertex, face) of every incidence, each once, ascending by vertex then by face."""
     m = faces.shape[0]
@@ -169,9 +176,7 @@ def weld(mesh, digits: Optional[int] = WELD_DIGITS, device=None) -> Tuple[torch.
         inverse = torch.full((n,), -1, dtype=torch.int64, device=dev)
         if f.shape[0] == 0 or n == 0:
             return torch.empty(0, 3, dtype=torch.float64, device=dev), f, inverse
-        used = torch.zeros(n, dtype=torch.bool, device=dev)
-        used[f.reshape(-1)] = True
-        referenced = torch.nonzero(used).reshape(-1)                      # ascending vertex index
+        referenced = torch.nonzero(_referenced(f, n)).reshape(-1)          # ascending vertex index
         vr = v[referenced].contiguous()
         keys = vr if digits is None else torch.round(vr * 10.0 ** digits)
         if not bool(torch.isfinite(keys).all()):
@@ -228,16 +233,18 @@ def _check_filter(min_faces, min_area, keep_largest, by, connectivity):
 
 def component_items(faces: torch.Tensor, n_vertices: int, connectivity: str) -> Tuple[torch.Tensor, torch.Tensor]:
     """Device faces[m,3] (m >= 1, checked) -> (keys, nodes) as ``lib.cc_union_runs`` takes them, int64: the faces that hold one key stand
-    next to each other.  "edge": the 3m corner pairs — all (0,1), then all (1,2), then all (2,0) — with key = min * n + max (-1 where
-    both ends are one vertex: no edge), sorted stably by torch.  "vertex": the rows of ``_vertex_faces``, key = the vertex."""
+    next to each other.  "edge": the first two of ``orient_items`` (its direction bytes are not made).  "vertex": the rows of ``_vertex_faces``, key = the vertex."""
     if connectivity == "vertex":
         return _incidences(faces)
-    m = faces.shape[0]
-    a = torch.cat((faces[:, 0], faces[:, 1], faces[:, 2]))
-    b = torch.cat((faces[:, 1], faces[:, 2], faces[:, 0]))
-    keys = torch.where(a == b, torch.full_like(a, -1), torch.minimum(a, b) * n_vertices + torch.maximum(a, b))
-    keys, order = torch.sort(keys, stable=True)
-    return keys, torch.arange(m, dtype=torch.int64, device=faces.device).repeat(3)[order].contiguous()
+    return _edge_items(faces, n_vertices, False)[:2]
+
+
+def _label_segments(face_label: torch.Tensor, face_count: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (order[m], start[K+1]) as ``lib.cc_segment_sums`` takes them: the faces sorted stably by label — a component's faces in
+    ascending face index — and where every component's segment starts, the last one's end behind them."""
+    order = torch.sort(face_label, stable=True)[1]
+    start = torch.cat((torch.zeros(1, dtype=torch.int64, device=face_label.device), torch.cumsum(face_count, dim=0))).contiguous()
+    return order, start
 
 
 def _components(v: torch.Tensor, f: torch.Tensor, connectivity: str, areas: bool) -> Components:
@@ -263,8 +270,7 @@ def _components(v: torch.Tensor, f: torch.Tensor, connectivity: str, areas: bool
         area = None
         if areas:
             per_face = lib.tri_areas(v, f, info=info[2:3])
-            order = torch.sort(face_label, stable=True)[1]          # a component's faces in ascending face index
-            start = torch.cat((torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(face_count, dim=0))).contiguous()
+            order, start = _label_segments(face_label, face_count)
             area = lib.cc_segment_sums(per_face[order].contiguous(), start, info=info[3:4])
         unions, chains, triangles, sums = (int(x) for x in info.cpu())          # the one read of the status words
         lib.cc_check(unions, "connected components (unions)")
@@ -310,8 +316,7 @@ def _select_faces(v: torch.Tensor, f: torch.Tensor, face_keep: torch.Tensor):
     """The faces of the mask in their order, the vertices they name in their order and bits -> (vertices, faces, kept_faces, inverse)."""
     kept_faces = torch.nonzero(face_keep).reshape(-1)
     kept = f[kept_faces]
-    used = torch.zeros(v.shape[0], dtype=torch.bool, device=v.device)
-    used[kept.reshape(-1)] = True
+    used = _referenced(kept, v.shape[0])
     inverse = torch.where(used, torch.cumsum(used, dim=0) - 1, torch.full((v.shape[0],), -1, dtype=torch.int64, device=v.device))
     return v[used].contiguous(), inverse[kept].reshape(-1, 3).contiguous(), kept_faces, inverse
 
@@ -372,14 +377,21 @@ def _check_reference(reference, viewpoints):
 
 
 def orient_items(faces: torch.Tensor, n_vertices: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """Device faces[m,3] (m >= 1, checked) -> (keys, nodes, dirs) as ``lib.orient_union_runs`` takes them: the "edge" items of
-    ``component_items`` — the same keys in the same stable order — each with the direction byte (a < b) of its half-edge a -> b."""
+    """Device faces[m,3] (m >= 1, checked) -> (keys, nodes, dirs) as ``lib.orient_union_runs`` takes them: the 3m half-edges a -> b —
+    all (0,1), then all (1,2), then all (2,0) — with key = min * n + max (-1 where both ends are one vertex: no edge), sorted stably
+    by torch, each with its face and the direction byte (a < b).  The first two are ``component_items``' "edge" items."""
+    return _edge_items(faces, n_vertices, True)
+
+
+def _edge_items(faces: torch.Tensor, n_vertices: int, dirs: bool):
+    """``orient_items``; without ``dirs`` the direction bytes are not made (None)."""
     m = faces.shape[0]
     a = torch.cat((faces[:, 0], faces[:, 1], faces[:, 2]))
     b = torch.cat((faces[:, 1], faces[:, 2], faces[:, 0]))
     keys = torch.where(a == b, torch.full_like(a, -1), torch.minimum(a, b) * n_vertices + torch.maximum(a, b))
     keys, order = torch.sort(keys, stable=True)
-    return keys, torch.arange(m, dtype=torch.int64, device=faces.device).repeat(3)[order].contiguous(), (a < b)[order].to(torch.uint8).contiguous()
+    nodes = torch.arange(m, dtype=torch.int64, device=faces.device).repeat(3)[order].contiguous()
+    return keys, nodes, (a < b)[order].to(torch.uint8).contiguous() if dirs else None
 
 
 def manifold_mask(keys: torch.Tensor, nodes: torch.Tensor, dirs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -438,8 +450,7 @@ def _orientation(v: torch.Tensor, f: torch.Tensor, reference: str, viewpoints: O
         elif reference in ("volume", "viewpoints"):
             per_face = lib.orient_votes(v, f, parity, lib.ORIENT_VOLUME if reference == "volume" else lib.ORIENT_VIEWPOINTS, viewpoints,
                                         info=info[2:3])
-            order = torch.sort(face_label, stable=True)[1]          # a component's faces in ascending face index
-            start = torch.cat((torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(face_count, dim=0))).contiguous()
+            order, start = _label_segments(face_label, face_count)
             votes = lib.cc_segment_sums(per_face[order].contiguous(), start, info=info[3:4])
             sign = (votes < 0) & orientable
         flip = (parity != 0) ^ sign[face_label]
@@ -653,9 +664,7 @@ def simplify_vertex_clustering(mesh, voxel_size, contraction: str = "average", c
             return Simplified(none(0, 3), none(0, 3, dtype=torch.int64), none(0, dtype=torch.int64),
                               torch.full((n,), -1, dtype=torch.int64, device=dev), *(None if x is None else none(0, 3) for x in extras),
                               none(0, dtype=torch.bool), none(0), 0)
-        used = torch.zeros(n, dtype=torch.bool, device=dev)
-        used[f.reshape(-1)] = True
-        referenced = torch.nonzero(used).reshape(-1)                      # ascending vertex index
+        referenced = torch.nonzero(_referenced(f, n)).reshape(-1)          # ascending vertex index
         vr = v[referenced].contiguous()
         origin, _ = voxel.frame(*voxel.bounding_box(vr), h)               # read 1 (a non-finite coordinate raises here)
         info = torch.zeros(4, dtype=torch.int64, device=dev)              # a word per stage: keys, means, planes, quadrics
@@ -721,8 +730,7 @@ def simplify_to_faces(mesh, target_faces, contraction: str = "quadric", steps: i
         raise ValueError("simplify_to_faces: the mesh has no faces")
     v, f = _mesh_on_device(mesh, device, "mesh", "mesh simplification")
     with torch.cuda.device(v.device):
-        used = torch.zeros(v.shape[0], dtype=torch.bool, device=v.device)
-        used[f.reshape(-1)] = True
+        used = _referenced(f, v.shape[0])
         lower, upper = voxel.bounding_box(v[used])
     extent = max(hi - lo for lo, hi in zip(lower, upper))
     if not extent > 0:
@@ -813,8 +821,7 @@ def dominant_bases(mesh, num_bases, voxel_size=None, decimation=None, orient=Non
             v, f = s.vertices, s.faces
         if f.shape[0] < 1:
             raise ValueError(f"dominant_bases: the simplification at voxel edge {h!r} leaves no face")          # (None: by edge collapse)
-        used = torch.zeros(v.shape[0], dtype=torch.bool, device=v.device)
-        used[f.reshape(-1)] = True
+        used = _referenced(f, v.shape[0])
         normals = vertex_normals((v, f))[used].contiguous()
         km = cluster.kmeans(normals, k, init, n_init, max_iter, seed)
         counts, order = torch.sort(km.counts, descending=True, stable=True)
