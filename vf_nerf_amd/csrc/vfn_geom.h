@@ -1,7 +1,8 @@
-// vfn_geom.h — what the fp64 mesh units (vfn_normals, vfn_voxel, vfn_cc, vfn_orient, vfn_simplify, vfn_collapse) share: the status bits
-// of include/vfn.h, the launch size, a wave's status report, the forest's memory accesses, and the unit vector of a cross product with
-// a plane's offset.  The status bits also compile for the host (csrc/vfn_forest_core.h, csrc/vfn_collapse_core.h); the rest is device
-// code, for units built with -ffp-contract=off (build.sh).
+// vfn_geom.h — what the fp64 mesh units (vfn_normals, vfn_voxel, vfn_cc, vfn_orient, vfn_simplify, vfn_collapse) and, through
+// csrc/vfn_mc_extract.h, the lattice units (vfn_mesh, vfn_tsdf) share: the status bits of include/vfn.h, the launch size and a wave's
+// status report — those for every unit —, the forest's memory accesses, and the unit vector of a cross product with a plane's offset.
+// The status bits also compile for the host (csrc/vfn_forest_core.h, csrc/vfn_collapse_core.h); the rest is device code, for units built
+// with -ffp-contract=off (build.sh).
 #pragma once
 #include <math.h>
 

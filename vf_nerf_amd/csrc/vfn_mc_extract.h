@@ -12,6 +12,7 @@
 // Everything here has internal linkage: each including unit gets its own tables and its own instantiations.
 #pragma once
 #include "vfn_common.h"
+#include "vfn_geom.h"         // the launch size, a wave's status report
 #include "vfn_mc_tables.h"
 #include <hipcub/hipcub.hpp>
 
@@ -29,7 +30,7 @@ __device__ __forceinline__ int tri_count(int top) {
     return n;
 }
 
-inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
+using vfn_geom::blocks_for;
 
 // The ordered inclusive scan over n int32 values (rocPRIM through hipCUB) that gives every triangle / vertex its output slot.
 inline int vfn_mc_scan_bytes(long long n, size_t* bytes) {
@@ -66,13 +67,7 @@ __global__ __launch_bounds__(256) void vfn_mc_count_kernel(Source a, int* __rest
         typename Source::Value v[8];
         counts[p] = a.eval(p, c, v, top, status) ? tri_count(top) : 0;
     }
-    // (one atomic per wave that saw a bad input)
-    const unsigned long long any = __ballot(status != 0u);
-    if (any) {
-        unsigned all = status;
-        for (int o = 32; o > 0; o >>= 1) all |= (unsigned)__shfl_xor((int)all, o, 64);
-        if ((threadIdx.x & 63) == (unsigned)__builtin_ctzll(any)) atomicOr((unsigned long long*)&info[1], (unsigned long long)all);
-    }
+    vfn_geom::report(status, (unsigned long long*)&info[1]);
 }
 
 // the same lanes again: every triangle's three float64 vertices at their slots (slot = 3 x triangle + corner)

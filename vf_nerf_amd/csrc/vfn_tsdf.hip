@@ -6,7 +6,10 @@
 //              single-view calls.  A workgroup covers a brick of 4 x 8 x 32 voxels; its 256 lanes first test one view each against the
 //              brick (below), the ballots go to LDS, and every wave then walks the set bits in ascending order — the view index is
 //              wave-uniform, so the 16 per-view parameters are scalar loads, not per-lane ones.  The depth reads are gathers:
-//              neighbouring lanes project to neighbouring pixels and the caches serve them.
+//              neighbouring lanes project to neighbouring pixels and the caches serve them.  The dense and the block-sparse kernel are
+//              ONE code path around their own index derivation: load_vec / store_vec (a run and its 12 colour floats, 16 B at a time),
+//              apply_views<lanes> (brick test, ballots, the walk) and integrate_view (the arithmetic).  Only the dense kernel has a
+//              scalar form, for rows that are no multiple of four voxels or arrays off the 16-B boundary; it is written there.
 //   brick test A view is skipped for a brick only when NO voxel centre of the brick can pass the per-voxel tests.  The test uses the
 //              voxel's own fp32 expressions at the brick's extreme centres: every operation of x -> xc -> (xc fx) / zc + cx + 0.5 is
 //              monotone in each operand once the signs of the coefficients are fixed, and rounding keeps order (a <= b gives
@@ -19,7 +22,8 @@
 //   colour     the COLOUR instantiation of the integration kernel carries a lane's 4 x 3 colour floats next to tsdf and weight (three
 //              16-B accesses in the vector form) and reads the pixel's three bytes with byte loads, issued with the depth load; the
 //              colourless instantiation is the code it was (the colour arguments are an empty record at the END of its arguments).
-//              emit_colours is a second source over the same skeleton whose vertex() is a colour; vertex_colours picks, per vertex,
+//              emit_colours is a second source over the same skeleton whose vertex() is a colour (colour_at, for both volumes, from the
+//              two voxel indices a source computes); vertex_colours picks, per vertex,
 //              the colour of the lowest slot that carries its id (an integer atomicMin per slot, then a gather).
 // No floating-point atomics.  fp32 (integration) and fp64 (vertices, colours) without contraction: -ffp-contract=off (build.sh),
 // correctly rounded / and sqrtf.
@@ -98,6 +102,38 @@ __device__ bool brick_may_see(const float* __restrict__ e, const float* __restri
     return true;
 }
 
+// A lane's run of RUN consecutive k voxels lives in registers as ts / wt / col, arrays of the KERNEL: both integrating kernels load them
+// here, update them view by view and store them here.  `off` is the run's first voxel in the arrays; a lane's 12 colour floats are
+// contiguous there, three 16-B accesses.  (The arrays are not members of one record: hipcc then allocates all six kernels differently
+// and gives the scalar colour form 100 B of scratch per lane, see profiles/r24.)
+template <bool COLOUR>
+__device__ __forceinline__ void load_vec(float ts[RUN], float wt[RUN], float (*col)[3], const float* tsdf, const float* weight,
+                                         const Colour<COLOUR>& cl, long long off) {
+    const float4 a = *reinterpret_cast<const float4*>(tsdf + off), c = *reinterpret_cast<const float4*>(weight + off);
+    ts[0] = a.x; ts[1] = a.y; ts[2] = a.z; ts[3] = a.w;
+    wt[0] = c.x; wt[1] = c.y; wt[2] = c.z; wt[3] = c.w;
+    if constexpr (COLOUR) {
+        const float4* __restrict__ q = reinterpret_cast<const float4*>(cl.colour + off * 3);
+        const float4 p = q[0], b4 = q[1], d = q[2];
+        col[0][0] = p.x; col[0][1] = p.y; col[0][2] = p.z; col[1][0] = p.w;
+        col[1][1] = b4.x; col[1][2] = b4.y; col[2][0] = b4.z; col[2][1] = b4.w;
+        col[2][2] = d.x; col[3][0] = d.y; col[3][1] = d.z; col[3][2] = d.w;
+    }
+}
+
+template <bool COLOUR>
+__device__ __forceinline__ void store_vec(const float ts[RUN], const float wt[RUN], const float (*col)[3], float* tsdf, float* weight,
+                                          const Colour<COLOUR>& cl, long long off) {
+    *reinterpret_cast<float4*>(tsdf + off) = make_float4(ts[0], ts[1], ts[2], ts[3]);
+    *reinterpret_cast<float4*>(weight + off) = make_float4(wt[0], wt[1], wt[2], wt[3]);
+    if constexpr (COLOUR) {
+        float4* __restrict__ q = reinterpret_cast<float4*>(cl.colour + off * 3);
+        q[0] = make_float4(col[0][0], col[0][1], col[0][2], col[1][0]);
+        q[1] = make_float4(col[1][1], col[1][2], col[2][0], col[2][1]);
+        q[2] = make_float4(col[2][2], col[3][0], col[3][1], col[3][2]);
+    }
+}
+
 // one view into the RUN voxels of a lane (include/vfn.h: the association is the contract)
 template <bool COLOUR>
 __device__ __forceinline__ void integrate_view(const Views& vs, const Colour<COLOUR>& cl, int view, float x, float y, const float z[RUN], int cnt,
@@ -138,6 +174,41 @@ __device__ __forceinline__ void integrate_view(const Views& vs, const Colour<COL
     }
 }
 
+// All views of a call into a lane's run, by a workgroup of N lanes whose voxel centres lie in the box [lo, hi]: every lane tests one view
+// per round against the box, the ballots go to the N / 64 words of `seen` in LDS, and each wave walks the set bits in ascending order
+// (the view index is wave-uniform).  Every lane of the workgroup arrives here, one without voxels with cnt == 0.  (`seen` is the
+// kernel's own __shared__ array: with a function-scope one hipcc generates other code for the dense kernels, see profiles/r24.)
+template <int N, bool COLOUR>
+__device__ __forceinline__ void apply_views(const Views& vs, const Colour<COLOUR>& cl, const float lo[3], const float hi[3], float x, float y,
+                                            const float z[RUN], int cnt, float trunc, float ts[RUN], float wt[RUN], float (*col)[3],
+                                            unsigned long long* seen) {
+    static_assert(N % 64 == 0, "whole waves: one ballot word each");
+    const int t = threadIdx.x;
+    const float wf = (float)vs.w, hf = (float)vs.h;
+    for (int base = 0; base < vs.n; base += N) {
+        const int mine = base + t;
+        const bool may = mine < vs.n && brick_may_see(vs.extr + (long long)mine * 12, vs.intr + (long long)mine * 4, lo, hi, wf, hf);
+        const unsigned long long ballot = __ballot(may);
+        if ((t & 63) == 0) seen[t >> 6] = ballot;
+        __syncthreads();
+        for (int g = 0; g < N / 64; ++g) {
+            const unsigned long long m64 = seen[g];
+            unsigned m_lo = __builtin_amdgcn_readfirstlane((unsigned)m64), m_hi = __builtin_amdgcn_readfirstlane((unsigned)(m64 >> 32));
+            while (m_lo) {                                    // ascending view order
+                const int bit = __builtin_ctz(m_lo);
+                m_lo &= m_lo - 1;
+                integrate_view<COLOUR>(vs, cl, base + g * 64 + bit, x, y, z, cnt, trunc, ts, wt, col);
+            }
+            while (m_hi) {
+                const int bit = __builtin_ctz(m_hi);
+                m_hi &= m_hi - 1;
+                integrate_view<COLOUR>(vs, cl, base + g * 64 + 32 + bit, x, y, z, cnt, trunc, ts, wt, col);
+            }
+        }
+        __syncthreads();
+    }
+}
+
 template <bool VEC, bool COLOUR>
 __global__ __launch_bounds__(THREADS) void vfn_tsdf_integrate_kernel(Volume vol, Views vs, int nbj, int nbk, Colour<COLOUR> cl) {
     __shared__ unsigned long long seen[THREADS / 64];
@@ -153,20 +224,10 @@ __global__ __launch_bounds__(THREADS) void vfn_tsdf_integrate_kernel(Volume vol,
     float col[COLOUR ? RUN : 1][3] = {};                     // a lane's 12 contiguous colour floats
     if (live) {
         if (VEC) {
-            const float4 a = *reinterpret_cast<const float4*>(vol.tsdf + off), c = *reinterpret_cast<const float4*>(vol.weight + off);
-            ts[0] = a.x; ts[1] = a.y; ts[2] = a.z; ts[3] = a.w;
-            wt[0] = c.x; wt[1] = c.y; wt[2] = c.z; wt[3] = c.w;
-        } else {
+            load_vec<COLOUR>(ts, wt, col, vol.tsdf, vol.weight, cl, off);
+        } else {                                              // rows that are no multiple of four voxels, arrays off the 16-B boundary
             for (int r = 0; r < cnt; ++r) { ts[r] = vol.tsdf[off + r]; wt[r] = vol.weight[off + r]; }
-        }
-        if constexpr (COLOUR) {
-            if (VEC) {
-                const float4* __restrict__ q = reinterpret_cast<const float4*>(cl.colour + off * 3);
-                const float4 a = q[0], b4 = q[1], c = q[2];
-                col[0][0] = a.x; col[0][1] = a.y; col[0][2] = a.z; col[1][0] = a.w;
-                col[1][1] = b4.x; col[1][2] = b4.y; col[2][0] = b4.z; col[2][1] = b4.w;
-                col[2][2] = c.x; col[3][0] = c.y; col[3][1] = c.z; col[3][2] = c.w;
-            } else {
+            if constexpr (COLOUR) {
                 for (int r = 0; r < cnt; ++r)
                     for (int c = 0; c < 3; ++c) col[r][c] = cl.colour[(off + r) * 3 + c];
             }
@@ -180,45 +241,14 @@ __global__ __launch_bounds__(THREADS) void vfn_tsdf_integrate_kernel(Volume vol,
     const float lo[3] = {centre(vol.ox, bi * BI, vol.vl), centre(vol.oy, bj * BJ, vol.vl), centre(vol.oz, bk * BK, vol.vl)};
     const float hi[3] = {centre(vol.ox, min(bi * BI + BI, vol.nx) - 1, vol.vl), centre(vol.oy, min(bj * BJ + BJ, vol.ny) - 1, vol.vl),
                          centre(vol.oz, min(bk * BK + BK, vol.nz) - 1, vol.vl)};
-    const float wf = (float)vs.w, hf = (float)vs.h;
-
-    for (int base = 0; base < vs.n; base += THREADS) {
-        const int mine = base + t;
-        const bool may = mine < vs.n && brick_may_see(vs.extr + (long long)mine * 12, vs.intr + (long long)mine * 4, lo, hi, wf, hf);
-        const unsigned long long ballot = __ballot(may);
-        if ((t & 63) == 0) seen[t >> 6] = ballot;
-        __syncthreads();
-        for (int g = 0; g < THREADS / 64; ++g) {
-            const unsigned long long m64 = seen[g];
-            unsigned m_lo = __builtin_amdgcn_readfirstlane((unsigned)m64), m_hi = __builtin_amdgcn_readfirstlane((unsigned)(m64 >> 32));
-            while (m_lo) {                                    // ascending view order
-                const int bit = __builtin_ctz(m_lo);
-                m_lo &= m_lo - 1;
-                integrate_view<COLOUR>(vs, cl, base + g * 64 + bit, x, y, z, cnt, vol.trunc, ts, wt, col);
-            }
-            while (m_hi) {
-                const int bit = __builtin_ctz(m_hi);
-                m_hi &= m_hi - 1;
-                integrate_view<COLOUR>(vs, cl, base + g * 64 + 32 + bit, x, y, z, cnt, vol.trunc, ts, wt, col);
-            }
-        }
-        __syncthreads();
-    }
+    apply_views<THREADS>(vs, cl, lo, hi, x, y, z, cnt, vol.trunc, ts, wt, col, seen);
 
     if (live) {
         if (VEC) {
-            *reinterpret_cast<float4*>(vol.tsdf + off) = make_float4(ts[0], ts[1], ts[2], ts[3]);
-            *reinterpret_cast<float4*>(vol.weight + off) = make_float4(wt[0], wt[1], wt[2], wt[3]);
+            store_vec<COLOUR>(ts, wt, col, vol.tsdf, vol.weight, cl, off);
         } else {
             for (int r = 0; r < cnt; ++r) { vol.tsdf[off + r] = ts[r]; vol.weight[off + r] = wt[r]; }
-        }
-        if constexpr (COLOUR) {
-            if (VEC) {
-                float4* __restrict__ q = reinterpret_cast<float4*>(cl.colour + off * 3);
-                q[0] = make_float4(col[0][0], col[0][1], col[0][2], col[1][0]);
-                q[1] = make_float4(col[1][1], col[1][2], col[2][0], col[2][1]);
-                q[2] = make_float4(col[2][2], col[3][0], col[3][1], col[3][2]);
-            } else {
+            if constexpr (COLOUR) {
                 for (int r = 0; r < cnt; ++r)
                     for (int c = 0; c < 3; ++c) cl.colour[(off + r) * 3 + c] = col[r][c];
             }
@@ -236,6 +266,15 @@ __device__ __forceinline__ void edge_ends(int e, int& ql, int& qu, int& axis) {
     const bool a_low = INC[qa][axis] < INC[qb][axis];
     ql = a_low ? qa : qb;
     qu = a_low ? qb : qa;
+}
+
+// the colour on a cut edge with endpoints ql / qu: the colours of their voxels il / iu of `colour`, mixed as the position is, in [0, 1]
+__device__ __forceinline__ void colour_at(const float v[8], int ql, int qu, long long il, long long iu, const float* colour, double out[3]) {
+    const double fl = fabs((double)v[ql]), fu = fabs((double)v[qu]);
+    const double r = fl / (fl + fu);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+        out[ch] = ((1.0 - r) * (double)colour[il * 3 + ch] + r * (double)colour[iu * 3 + ch]) / 255.0;
 }
 
 // the TSDF source of vfn_mc_extract.h: it never sets a status
@@ -299,11 +338,7 @@ struct LatticeColours {
         edge_ends(e, ql, qu, axis);
         const long long il = ((long long)(c[0] + INC[ql][0]) * at.ny + (c[1] + INC[ql][1])) * at.nz + (c[2] + INC[ql][2]);
         const long long iu = ((long long)(c[0] + INC[qu][0]) * at.ny + (c[1] + INC[qu][1])) * at.nz + (c[2] + INC[qu][2]);
-        const double fl = fabs((double)v[ql]), fu = fabs((double)v[qu]);
-        const double r = fl / (fl + fu);
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch)
-            out[ch] = ((1.0 - r) * (double)colour[il * 3 + ch] + r * (double)colour[iu * 3 + ch]) / 255.0;
+        colour_at(v, ql, qu, il, iu, colour, out);
     }
 };
 
@@ -342,17 +377,35 @@ int make_lattice(Lattice& a, const float* tsdf, const float* weight, int32_t nx,
     return VFN_OK;
 }
 
-// the checks and the launch of both integrating entry points; `colour` / `rgb` are read only by the COLOUR instantiation
+// what every entry point that takes views checks before it looks at a pointer
+int check_views(const char* what, float sdf_trunc, int32_t n_views, int32_t height, int32_t width) {
+    VFN_REQUIRE(sdf_trunc > 0.f && sdf_trunc - sdf_trunc == 0.f, "%s: sdf_trunc must be positive and finite", what);
+    VFN_REQUIRE(n_views >= 0 && height >= 1 && width >= 1 && (long long)height * width < (1ll << 31),
+                "%s: bad views (%d of %d x %d)", what, n_views, height, width);
+    return VFN_OK;
+}
+
+// `colour` / `rgb` are read only by the COLOUR instantiation
+template <bool COLOUR>
+Colour<COLOUR> make_colour(float* colour, const unsigned char* rgb) {
+    Colour<COLOUR> cl;
+    if constexpr (COLOUR) {
+        cl.colour = colour;
+        cl.rgb = rgb;
+    }
+    return cl;
+}
+
+// the checks and the launch of both dense integrating entry points
 template <bool COLOUR>
 int integrate(const char* what, float* tsdf, float* weight, float* colour, int32_t nx, int32_t ny, int32_t nz, float ox, float oy, float oz,
               float voxel_length, float sdf_trunc, const float* depth, const unsigned char* rgb, int32_t height, int32_t width,
               const float* intrinsics, const float* extrinsics, int32_t n_views, void* stream) {
-    const int rc = check_dims(nx, ny, nz, voxel_length, what);
+    int rc = check_dims(nx, ny, nz, voxel_length, what);
     if (rc != VFN_OK) return rc;
     VFN_REQUIRE(tsdf && weight && (!COLOUR || colour), "%s: NULL volume", what);
-    VFN_REQUIRE(sdf_trunc > 0.f && sdf_trunc - sdf_trunc == 0.f, "%s: sdf_trunc must be positive and finite", what);
-    VFN_REQUIRE(n_views >= 0 && height >= 1 && width >= 1 && (long long)height * width < (1ll << 31),
-                "%s: bad views (%d of %d x %d)", what, n_views, height, width);
+    rc = check_views(what, sdf_trunc, n_views, height, width);
+    if (rc != VFN_OK) return rc;
     if (n_views == 0) return VFN_OK;
     VFN_REQUIRE(depth && intrinsics && extrinsics && (!COLOUR || rgb), "%s: NULL view argument", what);
     const long long nbi = (nx + BI - 1) / BI, nbj = (ny + BJ - 1) / BJ, nbk = (nz + BK - 1) / BK;
@@ -360,15 +413,10 @@ int integrate(const char* what, float* tsdf, float* weight, float* colour, int32
     VFN_REQUIRE(bricks < (1ll << 31), "%s: %lld bricks exceed one launch", what, bricks);
     Volume vol{tsdf, weight, nx, ny, nz, ox, oy, oz, voxel_length, sdf_trunc};
     Views vs{depth, intrinsics, extrinsics, n_views, height, width};
-    Colour<COLOUR> cl;
+    const Colour<COLOUR> cl = make_colour<COLOUR>(colour, rgb);
     // 16-B accesses need rows of a multiple of four voxels and 16-B aligned arrays (a lane's 12 colour floats then start on a multiple
-    // of 48 B); anything else takes the scalar form
-    bool vec = nz % RUN == 0 && ((uintptr_t)tsdf & 15) == 0 && ((uintptr_t)weight & 15) == 0;
-    if constexpr (COLOUR) {
-        cl.colour = colour;
-        cl.rgb = rgb;
-        vec = vec && ((uintptr_t)colour & 15) == 0;
-    }
+    // of 48 B); anything else takes the scalar form.  (`colour` is NULL without COLOUR.)
+    const bool vec = nz % RUN == 0 && ((uintptr_t)tsdf & 15) == 0 && ((uintptr_t)weight & 15) == 0 && ((uintptr_t)colour & 15) == 0;
     hipStream_t s = (hipStream_t)stream;
     if (vec) hipLaunchKernelGGL((vfn_tsdf_integrate_kernel<true, COLOUR>), dim3((unsigned)bricks), dim3(THREADS), 0, s, vol, vs, (int)nbj, (int)nbk, cl);
     else hipLaunchKernelGGL((vfn_tsdf_integrate_kernel<false, COLOUR>), dim3((unsigned)bricks), dim3(THREADS), 0, s, vol, vs, (int)nbj, (int)nbk, cl);
@@ -441,9 +489,9 @@ extern "C" int vfn_tsdf_vertex_colours(const int64_t* ids, int64_t n_slots, cons
 //   mark       one lane per pixel of every view, float64: the blocks its point's ball touches get a byte 1 (a plain store of a constant;
 //              lanes that race store the same value).  Numbering the new blocks is torch plumbing on the marks.
 //   integrate  one workgroup of 128 lanes per block, a lane owns RUN consecutive k voxels (always 16-B aligned inside a block: only the
-//              vector form).  x, y, z come from the GLOBAL index through centre(), the views are tested with brick_may_see at the block's
-//              extreme in-lattice centres and applied by integrate_view<COLOUR> — the dense kernel's own code, so a voxel holds the dense
-//              volume's bits.  Voxels of an edge block beyond dims are never updated.
+//              vector form).  x, y, z come from the GLOBAL index through centre(); the kernel derives the indices, the offset and the
+//              block's extreme in-lattice centres, everything else is the dense kernel's own code — load_vec, apply_views<128>, store_vec
+//              — so a voxel holds the dense volume's bits.  Voxels of an edge block beyond dims are never updated.
 //   count/emit a third source of vfn_mc_extract.h: position p is block p >> 9, local cell (p >> 6) & 7, (p >> 3) & 7, p & 7; corners
 //              come from this block or from the neighbour block_of names; an absent neighbour voids the cell.  vertex() is Lattice's with
 //              the global index: the dense mesh's position bits.
@@ -517,18 +565,7 @@ __global__ __launch_bounds__(SP_THREADS) void vfn_tsdf_sparse_integrate_kernel(S
 
     float ts[RUN], wt[RUN], z[RUN];
     float col[COLOUR ? RUN : 1][3] = {};
-    {
-        const float4 a = *reinterpret_cast<const float4*>(vol.tsdf + off), c = *reinterpret_cast<const float4*>(vol.weight + off);
-        ts[0] = a.x; ts[1] = a.y; ts[2] = a.z; ts[3] = a.w;
-        wt[0] = c.x; wt[1] = c.y; wt[2] = c.z; wt[3] = c.w;
-    }
-    if constexpr (COLOUR) {
-        const float4* __restrict__ q = reinterpret_cast<const float4*>(cl.colour + off * 3);
-        const float4 a = q[0], b4 = q[1], c = q[2];
-        col[0][0] = a.x; col[0][1] = a.y; col[0][2] = a.z; col[1][0] = a.w;
-        col[1][1] = b4.x; col[1][2] = b4.y; col[2][0] = b4.z; col[2][1] = b4.w;
-        col[2][2] = c.x; col[3][0] = c.y; col[3][1] = c.z; col[3][2] = c.w;
-    }
+    load_vec<COLOUR>(ts, wt, col, vol.tsdf, vol.weight, cl, off);
     const float x = centre(vol.ox, i, vol.vl), y = centre(vol.oy, j, vol.vl);
 #pragma unroll
     for (int r = 0; r < RUN; ++r) z[r] = centre(vol.oz, k0 + r, vol.vl);
@@ -537,39 +574,9 @@ __global__ __launch_bounds__(SP_THREADS) void vfn_tsdf_sparse_integrate_kernel(S
     const float lo[3] = {centre(vol.ox, b0, vol.vl), centre(vol.oy, b1, vol.vl), centre(vol.oz, b2, vol.vl)};
     const float hi[3] = {centre(vol.ox, min(b0 + BLOCK, vol.nx) - 1, vol.vl), centre(vol.oy, min(b1 + BLOCK, vol.ny) - 1, vol.vl),
                          centre(vol.oz, min(b2 + BLOCK, vol.nz) - 1, vol.vl)};
-    const float wf = (float)vs.w, hf = (float)vs.h;
+    apply_views<SP_THREADS>(vs, cl, lo, hi, x, y, z, cnt, vol.trunc, ts, wt, col, seen);
 
-    for (int base = 0; base < vs.n; base += SP_THREADS) {
-        const int mine = base + t;
-        const bool may = mine < vs.n && brick_may_see(vs.extr + (long long)mine * 12, vs.intr + (long long)mine * 4, lo, hi, wf, hf);
-        const unsigned long long ballot = __ballot(may);
-        if ((t & 63) == 0) seen[t >> 6] = ballot;
-        __syncthreads();
-        for (int g = 0; g < SP_THREADS / 64; ++g) {
-            const unsigned long long m64 = seen[g];
-            unsigned m_lo = __builtin_amdgcn_readfirstlane((unsigned)m64), m_hi = __builtin_amdgcn_readfirstlane((unsigned)(m64 >> 32));
-            while (m_lo) {                                    // ascending view order
-                const int bit = __builtin_ctz(m_lo);
-                m_lo &= m_lo - 1;
-                integrate_view<COLOUR>(vs, cl, base + g * 64 + bit, x, y, z, cnt, vol.trunc, ts, wt, col);
-            }
-            while (m_hi) {
-                const int bit = __builtin_ctz(m_hi);
-                m_hi &= m_hi - 1;
-                integrate_view<COLOUR>(vs, cl, base + g * 64 + 32 + bit, x, y, z, cnt, vol.trunc, ts, wt, col);
-            }
-        }
-        __syncthreads();
-    }
-
-    *reinterpret_cast<float4*>(vol.tsdf + off) = make_float4(ts[0], ts[1], ts[2], ts[3]);
-    *reinterpret_cast<float4*>(vol.weight + off) = make_float4(wt[0], wt[1], wt[2], wt[3]);
-    if constexpr (COLOUR) {
-        float4* __restrict__ q = reinterpret_cast<float4*>(cl.colour + off * 3);
-        q[0] = make_float4(col[0][0], col[0][1], col[0][2], col[1][0]);
-        q[1] = make_float4(col[1][1], col[1][2], col[2][0], col[2][1]);
-        q[2] = make_float4(col[2][2], col[3][0], col[3][1], col[3][2]);
-    }
+    store_vec<COLOUR>(ts, wt, col, vol.tsdf, vol.weight, cl, off);
 }
 
 // the sparse source of vfn_mc_extract.h; c[] is the GLOBAL cell index, so Lattice::vertex gives the dense mesh's bits
@@ -634,12 +641,7 @@ struct SparseLatticeColours {
         const long long b = sp.block_of[((long long)home[0] * sp.nby + home[1]) * sp.nbz + home[2]];
         const int gl[3] = {c[0] + INC[ql][0], c[1] + INC[ql][1], c[2] + INC[ql][2]};
         const int gu[3] = {c[0] + INC[qu][0], c[1] + INC[qu][1], c[2] + INC[qu][2]};
-        const long long il = sp.voxel(gl, home, b), iu = sp.voxel(gu, home, b);      // (both present: eval passed)
-        const double fl = fabs((double)v[ql]), fu = fabs((double)v[qu]);
-        const double r = fl / (fl + fu);
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch)
-            out[ch] = ((1.0 - r) * (double)colour[il * 3 + ch] + r * (double)colour[iu * 3 + ch]) / 255.0;
+        colour_at(v, ql, qu, sp.voxel(gl, home, b), sp.voxel(gu, home, b), colour, out);      // (both present: eval passed)
     }
 };
 
@@ -673,11 +675,10 @@ template <bool COLOUR>
 int sparse_integrate(const char* what, float* tsdf, float* weight, float* colour, const int32_t* coords, int32_t n_blocks, int32_t nx, int32_t ny,
                      int32_t nz, float ox, float oy, float oz, float voxel_length, float sdf_trunc, const float* depth, const unsigned char* rgb,
                      int32_t height, int32_t width, const float* intrinsics, const float* extrinsics, int32_t n_views, void* stream) {
-    const int rc = check_sparse_dims(nx, ny, nz, n_blocks, voxel_length, what);
+    int rc = check_sparse_dims(nx, ny, nz, n_blocks, voxel_length, what);
     if (rc != VFN_OK) return rc;
-    VFN_REQUIRE(sdf_trunc > 0.f && sdf_trunc - sdf_trunc == 0.f, "%s: sdf_trunc must be positive and finite", what);
-    VFN_REQUIRE(n_views >= 0 && height >= 1 && width >= 1 && (long long)height * width < (1ll << 31),
-                "%s: bad views (%d of %d x %d)", what, n_views, height, width);
+    rc = check_views(what, sdf_trunc, n_views, height, width);
+    if (rc != VFN_OK) return rc;
     if (n_views == 0 || n_blocks == 0) return VFN_OK;
     VFN_REQUIRE(tsdf && weight && coords && (!COLOUR || colour), "%s: NULL volume", what);
     VFN_REQUIRE(depth && intrinsics && extrinsics && (!COLOUR || rgb), "%s: NULL view argument", what);
@@ -685,12 +686,8 @@ int sparse_integrate(const char* what, float* tsdf, float* weight, float* colour
                 what);
     SparseVolume vol{tsdf, weight, (const int*)coords, nx, ny, nz, ox, oy, oz, voxel_length, sdf_trunc};
     Views vs{depth, intrinsics, extrinsics, n_views, height, width};
-    Colour<COLOUR> cl;
-    if constexpr (COLOUR) {
-        cl.colour = colour;
-        cl.rgb = rgb;
-    }
-    hipLaunchKernelGGL((vfn_tsdf_sparse_integrate_kernel<COLOUR>), dim3((unsigned)n_blocks), dim3(SP_THREADS), 0, (hipStream_t)stream, vol, vs, cl);
+    hipLaunchKernelGGL((vfn_tsdf_sparse_integrate_kernel<COLOUR>), dim3((unsigned)n_blocks), dim3(SP_THREADS), 0, (hipStream_t)stream, vol, vs,
+                       make_colour<COLOUR>(colour, rgb));
     return vfn_check_launch(what);
 }
 
@@ -704,8 +701,8 @@ extern "C" int vfn_tsdf_sparse_mark(uint8_t* marks, int32_t nbx, int32_t nby, in
                 "%s: the block lattice (%d, %d, %d) must be positive with fewer than 2^31 blocks", what, nbx, nby, nbz);
     VFN_REQUIRE(voxel_length > 0.f && voxel_length - voxel_length == 0.f && sdf_trunc > 0.f && sdf_trunc - sdf_trunc == 0.f,
                 "%s: voxel_length and sdf_trunc must be positive and finite", what);
-    VFN_REQUIRE(n_views >= 0 && height >= 1 && width >= 1 && (long long)height * width < (1ll << 31),
-                "%s: bad views (%d of %d x %d)", what, n_views, height, width);
+    const int rc = check_views(what, sdf_trunc, n_views, height, width);      // (sdf_trunc has passed: this is the view part)
+    if (rc != VFN_OK) return rc;
     if (n_views == 0) return VFN_OK;
     VFN_REQUIRE(marks && depth && cameras, "%s: NULL argument", what);
     const long long lanes = (long long)height * width * n_views;

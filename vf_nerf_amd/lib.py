@@ -1705,16 +1705,9 @@ def _tsdf_volume_args(tsdf: torch.Tensor, weight: torch.Tensor):
     return (_ptr(tsdf, "tsdf"), _ptr(weight, "weight"), C.c_int32(nx), C.c_int32(ny), C.c_int32(nz))
 
 
-def tsdf_integrate(tsdf: torch.Tensor, weight: torch.Tensor, origin: Sequence[float], voxel_length: float, sdf_trunc: float,
-                   depth: torch.Tensor, intrinsics: torch.Tensor, extrinsics: torch.Tensor) -> None:
-    """All views of depth[V,H,W] (intrinsics[V,4] = fx fy cx cy, extrinsics[V,12] = world -> camera rows) into the volume, in place, in one
-    pass over it; origin / voxel_length / sdf_trunc are taken as float32.  See include/vfn.h for the arithmetic."""
-    vol = _tsdf_volume_args(tsdf, weight)
-    v, h, w = _tsdf_view_args(tsdf, depth, intrinsics, extrinsics)
-    with torch.cuda.device(tsdf.device):
-        _check(load().vfn_tsdf_integrate(*vol, *(C.c_float(float(o)) for o in origin), C.c_float(float(voxel_length)), C.c_float(float(sdf_trunc)),
-                                         _ptr(depth, "depth"), C.c_int32(h), C.c_int32(w), _ptr(intrinsics, "intrinsics"),
-                                         _ptr(extrinsics, "extrinsics"), C.c_int32(v), _stream()), "vfn_tsdf_integrate")
+def _f32s(*values):
+    """The values as the ``float`` arguments of an entry point."""
+    return tuple(C.c_float(float(x)) for x in values)
 
 
 def _tsdf_view_args(tsdf: torch.Tensor, depth: torch.Tensor, intrinsics: torch.Tensor, extrinsics: torch.Tensor, rgb=None):
@@ -1739,55 +1732,77 @@ def _tsdf_colour_arg(tsdf: torch.Tensor, colour: torch.Tensor):
     return _ptr(colour, "colour")
 
 
+def _tsdf_integrate(tsdf, weight, colour, origin, voxel_length, sdf_trunc, depth, rgb, intrinsics, extrinsics) -> None:
+    """Both dense integrations: ``colour`` / ``rgb`` are tensors for vfn_tsdf_integrate_rgb, both None for vfn_tsdf_integrate."""
+    vol = _tsdf_volume_args(tsdf, weight)
+    col = () if colour is None else (_tsdf_colour_arg(tsdf, colour),)
+    v, h, w = _tsdf_view_args(tsdf, depth, intrinsics, extrinsics, rgb)
+    name = "vfn_tsdf_integrate" if colour is None else "vfn_tsdf_integrate_rgb"
+    with torch.cuda.device(tsdf.device):
+        _check(getattr(load(), name)(*vol[:2], *col, *vol[2:], *_f32s(*origin, voxel_length, sdf_trunc), _ptr(depth, "depth"),
+                                     *(() if rgb is None else (_ptr(rgb, "rgb", torch.uint8),)), C.c_int32(h), C.c_int32(w),
+                                     _ptr(intrinsics, "intrinsics"), _ptr(extrinsics, "extrinsics"), C.c_int32(v), _stream()), name)
+
+
+def tsdf_integrate(tsdf: torch.Tensor, weight: torch.Tensor, origin: Sequence[float], voxel_length: float, sdf_trunc: float,
+                   depth: torch.Tensor, intrinsics: torch.Tensor, extrinsics: torch.Tensor) -> None:
+    """All views of depth[V,H,W] (intrinsics[V,4] = fx fy cx cy, extrinsics[V,12] = world -> camera rows) into the volume, in place, in one
+    pass over it; origin / voxel_length / sdf_trunc are taken as float32.  See include/vfn.h for the arithmetic."""
+    _tsdf_integrate(tsdf, weight, None, origin, voxel_length, sdf_trunc, depth, None, intrinsics, extrinsics)
+
+
 def tsdf_integrate_rgb(tsdf: torch.Tensor, weight: torch.Tensor, colour: torch.Tensor, origin: Sequence[float], voxel_length: float,
                        sdf_trunc: float, depth: torch.Tensor, rgb: torch.Tensor, intrinsics: torch.Tensor, extrinsics: torch.Tensor) -> None:
     """``tsdf_integrate`` with the views' images: rgb[V,H,W,3] uint8 into colour[nx,ny,nz,3] float32 (byte units), the running mean of the
     pixels whose depth updated the voxel.  tsdf / weight come out as ``tsdf_integrate`` leaves them.  See include/vfn.h."""
+    _tsdf_integrate(tsdf, weight, colour, origin, voxel_length, sdf_trunc, depth, rgb, intrinsics, extrinsics)
+
+
+def _tsdf_slot_colours(emit_colours, dev):
+    """The ``per_slot`` of a coloured extraction: ``emit_colours`` launches the volume's ``*_emit_colours``, then every vertex takes its first slot's."""
+    def colours_of(scanned, ids, n_vert):
+        n_slots = ids.shape[0]
+        tri_cols = torch.empty(n_slots, 3, dtype=torch.float64, device=dev)
+        emit_colours(*scanned, _ptr(tri_cols, "tri_cols", torch.float64), _stream())
+        first = torch.empty(max(n_vert, 1), dtype=torch.int32, device=dev)
+        out = torch.empty(n_vert, 3, dtype=torch.float64, device=dev)
+        _check(load().vfn_tsdf_vertex_colours(_ptr(ids, "ids", torch.int64), C.c_int64(n_slots), _ptr(tri_cols, "tri_cols", torch.float64),
+                                              _ptr(first, "first", torch.int32), C.c_int64(n_vert),
+                                              _ptr(out, "colours", torch.float64) if n_vert else None, _stream()), "vfn_tsdf_vertex_colours")
+        return out
+
+    return colours_of
+
+
+def _tsdf_extract(count, emit, positions: int, dev, what: str, per_slot=None):
+    """``_extract_slots`` for both volumes -> (vertices, faces) or, with ``per_slot``, (vertices, faces, colours [0,3] when empty)."""
+    vertices, faces, colours = _extract_slots(count, emit, positions, dev, what, per_slot=per_slot)
+    if per_slot is None:
+        return vertices, faces
+    return vertices, faces, colours if colours is not None else torch.empty(0, 3, dtype=torch.float64, device=dev)
+
+
+def _tsdf_dense_extract(tsdf, weight, colour, origin, voxel_length):
     vol = _tsdf_volume_args(tsdf, weight)
-    col = _tsdf_colour_arg(tsdf, colour)
-    v, h, w = _tsdf_view_args(tsdf, depth, intrinsics, extrinsics, rgb)
-    with torch.cuda.device(tsdf.device):
-        _check(load().vfn_tsdf_integrate_rgb(vol[0], vol[1], col, *vol[2:], *(C.c_float(float(o)) for o in origin), C.c_float(float(voxel_length)),
-                                             C.c_float(float(sdf_trunc)), _ptr(depth, "depth"), _ptr(rgb, "rgb", torch.uint8), C.c_int32(h),
-                                             C.c_int32(w), _ptr(intrinsics, "intrinsics"), _ptr(extrinsics, "extrinsics"), C.c_int32(v),
-                                             _stream()), "vfn_tsdf_integrate_rgb")
+    col = None if colour is None else _tsdf_colour_arg(tsdf, colour)
+    per_slot = None if colour is None else _tsdf_slot_colours(
+        lambda *out: _check(load().vfn_tsdf_emit_colours(*vol[:2], col, *vol[2:], *out), "vfn_tsdf_emit_colours"), tsdf.device)
+    nx, ny, nz = tsdf.shape
+    box = _f32s(*origin, voxel_length)
+    return _tsdf_extract(lambda *out: _check(load().vfn_tsdf_count(*vol, *out), "vfn_tsdf_count"),
+                         lambda *out: _check(load().vfn_tsdf_emit(*vol, *box, *out), "vfn_tsdf_emit"),
+                         (nx - 1) * (ny - 1) * (nz - 1), tsdf.device, "TSDF extraction", per_slot)
 
 
 def tsdf_extract(tsdf: torch.Tensor, weight: torch.Tensor, origin: Sequence[float], voxel_length: float):
-    """The zero level set of the volume (csrc/vfn_tsdf.hip) through ``_extract`` -> (vertices[n,3] float64, faces[m,3] int64, 0-based)."""
-    vol = _tsdf_volume_args(tsdf, weight)
-    nx, ny, nz = tsdf.shape
-    box = tuple(C.c_float(float(o)) for o in origin) + (C.c_float(float(voxel_length)),)
-    return _extract(lambda *out: _check(load().vfn_tsdf_count(*vol, *out), "vfn_tsdf_count"),
-                    lambda *out: _check(load().vfn_tsdf_emit(*vol, *box, *out), "vfn_tsdf_emit"),
-                    (nx - 1) * (ny - 1) * (nz - 1), tsdf.device, "TSDF extraction")
+    """The zero level set of the volume (csrc/vfn_tsdf.hip) through ``_tsdf_extract`` -> (vertices[n,3] float64, faces[m,3] int64, 0-based)."""
+    return _tsdf_dense_extract(tsdf, weight, None, origin, voxel_length)
 
 
 def tsdf_extract_coloured(tsdf: torch.Tensor, weight: torch.Tensor, colour: torch.Tensor, origin: Sequence[float], voxel_length: float):
     """``tsdf_extract`` with vertex colours -> (vertices, faces, colours[n,3] float64 in [0,1]): the vertices and faces are those of
     ``tsdf_extract``; a vertex takes the colour of the slot at which it first appears (include/vfn.h)."""
-    vol = _tsdf_volume_args(tsdf, weight)
-    col = _tsdf_colour_arg(tsdf, colour)
-    nx, ny, nz = tsdf.shape
-    dev = tsdf.device
-    box = tuple(C.c_float(float(o)) for o in origin) + (C.c_float(float(voxel_length)),)
-
-    def colours_of(scanned, ids, n):
-        n_slots = ids.shape[0]
-        tri_cols = torch.empty(n_slots, 3, dtype=torch.float64, device=dev)
-        _check(load().vfn_tsdf_emit_colours(vol[0], vol[1], col, *vol[2:], *scanned, _ptr(tri_cols, "tri_cols", torch.float64), _stream()),
-               "vfn_tsdf_emit_colours")
-        first = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        out = torch.empty(n, 3, dtype=torch.float64, device=dev)
-        _check(load().vfn_tsdf_vertex_colours(_ptr(ids, "ids", torch.int64), C.c_int64(n_slots), _ptr(tri_cols, "tri_cols", torch.float64),
-                                              _ptr(first, "first", torch.int32), C.c_int64(n), _ptr(out, "colours", torch.float64) if n else None,
-                                              _stream()), "vfn_tsdf_vertex_colours")
-        return out
-
-    vertices, faces, colours = _extract_slots(lambda *out: _check(load().vfn_tsdf_count(*vol, *out), "vfn_tsdf_count"),
-                                              lambda *out: _check(load().vfn_tsdf_emit(*vol, *box, *out), "vfn_tsdf_emit"),
-                                              (nx - 1) * (ny - 1) * (nz - 1), dev, "TSDF extraction", per_slot=colours_of)
-    return vertices, faces, colours if colours is not None else torch.empty(0, 3, dtype=torch.float64, device=dev)
+    return _tsdf_dense_extract(tsdf, weight, colour, origin, voxel_length)
 
 
 # the block-sparse volume (include/vfn.h: "A block-sparse TSDF volume"; tsdf.SparseTSDFVolume owns the numbering and the tables)
@@ -1814,9 +1829,8 @@ def tsdf_sparse_mark(marks: torch.Tensor, origin: Sequence[float], voxel_length:
         raise VfnError("the views and the marks live on different devices")
     with torch.cuda.device(marks.device):
         _check(load().vfn_tsdf_sparse_mark(_ptr(marks, "marks", torch.uint8), *(C.c_int32(n) for n in marks.shape),
-                                           *(C.c_float(float(o)) for o in origin), C.c_float(float(voxel_length)), C.c_float(float(sdf_trunc)),
-                                           _ptr(depth, "depth"), C.c_int32(h), C.c_int32(w), _ptr(cameras, "cameras", torch.float64),
-                                           C.c_int32(v), _stream()), "vfn_tsdf_sparse_mark")
+                                           *_f32s(*origin, voxel_length, sdf_trunc), _ptr(depth, "depth"), C.c_int32(h), C.c_int32(w),
+                                           _ptr(cameras, "cameras", torch.float64), C.c_int32(v), _stream()), "vfn_tsdf_sparse_mark")
 
 
 def _tsdf_sparse_args(tsdf: torch.Tensor, weight: torch.Tensor, block_coords: torch.Tensor, dims: Sequence[int], block_of=None, colour=None):
@@ -1846,48 +1860,29 @@ def tsdf_sparse_integrate(tsdf: torch.Tensor, weight: torch.Tensor, colour: Opti
         raise VfnError("colour and rgb go together")
     n, d3 = _tsdf_sparse_args(tsdf, weight, block_coords, dims, colour=colour)
     v, h, w = _tsdf_view_args(tsdf, depth, intrinsics, extrinsics, rgb)
-    box = tuple(C.c_float(float(o)) for o in origin) + (C.c_float(float(voxel_length)), C.c_float(float(sdf_trunc)))
+    box = _f32s(*origin, voxel_length, sdf_trunc)
     views = (C.c_int32(h), C.c_int32(w), _ptr(intrinsics, "intrinsics"), _ptr(extrinsics, "extrinsics"), C.c_int32(v), _stream())
+    name = "vfn_tsdf_sparse_integrate" if colour is None else "vfn_tsdf_sparse_integrate_rgb"
     with torch.cuda.device(tsdf.device):
-        if colour is None:
-            _check(load().vfn_tsdf_sparse_integrate(_ptr(tsdf, "tsdf"), _ptr(weight, "weight"), _ptr(block_coords, "block_coords", torch.int32),
-                                                    C.c_int32(n), *d3, *box, _ptr(depth, "depth"), *views), "vfn_tsdf_sparse_integrate")
-        else:
-            _check(load().vfn_tsdf_sparse_integrate_rgb(_ptr(tsdf, "tsdf"), _ptr(weight, "weight"), _ptr(colour, "colour"),
-                                                        _ptr(block_coords, "block_coords", torch.int32), C.c_int32(n), *d3, *box,
-                                                        _ptr(depth, "depth"), _ptr(rgb, "rgb", torch.uint8), *views),
-                   "vfn_tsdf_sparse_integrate_rgb")
+        _check(getattr(load(), name)(_ptr(tsdf, "tsdf"), _ptr(weight, "weight"), *(() if colour is None else (_ptr(colour, "colour"),)),
+                                     _ptr(block_coords, "block_coords", torch.int32), C.c_int32(n), *d3, *box, _ptr(depth, "depth"),
+                                     *(() if rgb is None else (_ptr(rgb, "rgb", torch.uint8),)), *views), name)
 
 
 def tsdf_sparse_extract(tsdf: torch.Tensor, weight: torch.Tensor, colour: Optional[torch.Tensor], block_of: torch.Tensor,
                         block_coords: torch.Tensor, dims: Sequence[int], origin: Sequence[float], voxel_length: float):
-    """The zero level set of the blocks through ``_extract_slots`` -> (vertices, faces) or, with ``colour``, (vertices, faces, colours):
+    """The zero level set of the blocks through ``_tsdf_extract`` -> (vertices, faces) or, with ``colour``, (vertices, faces, colours):
     the dense extraction's vertex bits, blocks in id order and cells in local C order."""
     n, d3 = _tsdf_sparse_args(tsdf, weight, block_coords, dims, block_of=block_of, colour=colour)
     dev = tsdf.device
     vol = (_ptr(tsdf, "tsdf"), _ptr(weight, "weight"))
     tables = (_ptr(block_of, "block_of", torch.int32), _ptr(block_coords, "block_coords", torch.int32), C.c_int32(n)) + d3
-    box = tuple(C.c_float(float(o)) for o in origin) + (C.c_float(float(voxel_length)),)
-
-    def colours_of(scanned, ids, n_vert):
-        n_slots = ids.shape[0]
-        tri_cols = torch.empty(n_slots, 3, dtype=torch.float64, device=dev)
-        _check(load().vfn_tsdf_sparse_emit_colours(*vol, _ptr(colour, "colour"), *tables, *scanned, _ptr(tri_cols, "tri_cols", torch.float64),
-                                                   _stream()), "vfn_tsdf_sparse_emit_colours")
-        first = torch.empty(max(n_vert, 1), dtype=torch.int32, device=dev)
-        out = torch.empty(n_vert, 3, dtype=torch.float64, device=dev)
-        _check(load().vfn_tsdf_vertex_colours(_ptr(ids, "ids", torch.int64), C.c_int64(n_slots), _ptr(tri_cols, "tri_cols", torch.float64),
-                                              _ptr(first, "first", torch.int32), C.c_int64(n_vert),
-                                              _ptr(out, "colours", torch.float64) if n_vert else None, _stream()), "vfn_tsdf_vertex_colours")
-        return out
-
-    vertices, faces, colours = _extract_slots(lambda *out: _check(load().vfn_tsdf_sparse_count(*vol, *tables, *out), "vfn_tsdf_sparse_count"),
-                                              lambda *out: _check(load().vfn_tsdf_sparse_emit(*vol, *tables, *box, *out), "vfn_tsdf_sparse_emit"),
-                                              n * TSDF_BLOCK ** 3, dev, "sparse TSDF extraction",
-                                              per_slot=colours_of if colour is not None else None)
-    if colour is None:
-        return vertices, faces
-    return vertices, faces, colours if colours is not None else torch.empty(0, 3, dtype=torch.float64, device=dev)
+    box = _f32s(*origin, voxel_length)
+    per_slot = None if colour is None else _tsdf_slot_colours(
+        lambda *out: _check(load().vfn_tsdf_sparse_emit_colours(*vol, _ptr(colour, "colour"), *tables, *out), "vfn_tsdf_sparse_emit_colours"), dev)
+    return _tsdf_extract(lambda *out: _check(load().vfn_tsdf_sparse_count(*vol, *tables, *out), "vfn_tsdf_sparse_count"),
+                         lambda *out: _check(load().vfn_tsdf_sparse_emit(*vol, *tables, *box, *out), "vfn_tsdf_sparse_emit"),
+                         n * TSDF_BLOCK ** 3, dev, "sparse TSDF extraction", per_slot)
 
 
 # ------------------------------------------------------------------------------------------------

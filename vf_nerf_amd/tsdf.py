@@ -50,11 +50,15 @@ SDF_TRUNC = 0.04                  # :625
 DEPTH_SCALE, DEPTH_TRUNC = 1000.0, 10.0
 
 
-def _check_dims(dims) -> Tuple[int, int, int]:
+def _three_dims(dims) -> Tuple[int, int, int]:
     d = tuple(dims)
     if len(d) != 3 or any(isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 1 for n in d):
         raise ValueError(f"dims must be three positive integers, got {dims!r}")
-    d = tuple(int(n) for n in d)
+    return tuple(int(n) for n in d)
+
+
+def _check_dims(dims) -> Tuple[int, int, int]:
+    d = _three_dims(dims)
     if d[0] * d[1] * d[2] >= LIMIT:
         raise ValueError(f"a volume of {d[0]} x {d[1]} x {d[2]} voxels exceeds the 2^31 limit")
     return d
@@ -66,10 +70,7 @@ DIM_LIMIT = 1 << 24               # a lattice index is exact as float32 up to he
 
 def _check_sparse_dims(dims) -> Tuple[int, int, int]:
     """``_check_dims`` for the block-sparse volume: no bound on the voxels; each dim <= 2^24 and fewer than 2^31 blocks of 8^3."""
-    d = tuple(dims)
-    if len(d) != 3 or any(isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 1 for n in d):
-        raise ValueError(f"dims must be three positive integers, got {dims!r}")
-    d = tuple(int(n) for n in d)
+    d = _three_dims(dims)
     if max(d) > DIM_LIMIT:
         raise ValueError(f"a sparse volume of {d[0]} x {d[1]} x {d[2]} voxels exceeds 2^24 voxels along an axis")
     nb = lib.tsdf_block_lattice(d)
@@ -178,14 +179,11 @@ def reference_depth(depth_map, depth_scale: float = DEPTH_SCALE, depth_trunc: fl
     return torch.where(out >= depth_trunc, torch.zeros_like(out), out)
 
 
-class TSDFVolume:
-    """A dense TSDF volume of ``dims = (nx, ny, nz)`` voxels of ``voxel_length`` whose first voxel's corner is ``origin``: voxel (i, j, k)
-    has its centre at origin + (index + 0.5) voxel_length.  ``tsdf`` / ``weight`` are float32 [nx,ny,nz] device tensors, zero until a
-    view has been integrated.  ``colour=True`` adds ``colour`` float32 [nx,ny,nz,3] in byte units (else None): every ``integrate`` then
-    needs the views' images."""
+class _LatticeVolume:
+    """What both volumes share: the lattice arguments, taken as float32, and the checks of a call's views.  ``dims`` arrive checked."""
 
-    def __init__(self, origin, dims, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC, device=None, colour: bool = False):
-        self.dims = _check_dims(dims)
+    def __init__(self, origin, dims, voxel_length, sdf_trunc, device):
+        self.dims = dims
         self.voxel_length = geomargs.positive32(voxel_length, "voxel_length")
         self.sdf_trunc = geomargs.positive32(sdf_trunc, "sdf_trunc")
         o = np.asarray(origin.detach().cpu() if isinstance(origin, torch.Tensor) else origin, dtype=np.float64).reshape(-1)
@@ -193,6 +191,29 @@ class TSDFVolume:
             raise ValueError(f"origin must be three finite numbers, got {origin!r}")
         self.origin = tuple(float(x) for x in o.astype(np.float32))
         self.device = geomargs.device(device, "TSDF fusion")
+
+    def _views(self, depth, intrinsics, pose, rgb, need_rgb: bool = True):
+        """The arguments of ``integrate`` checked -> (depth maps [V,H,W] where they live, images as given or None, float32 fx fy cx cy
+        [V,4] and extrinsic rows [V,12] on the host): what ``_integrate_prepared`` takes."""
+        d = _stack_depths(depth)
+        v = d.shape[0]
+        if need_rgb and (rgb is None) != (self.colour is None):
+            raise ValueError("rgb is required by a volume with colour" if rgb is None else "rgb was given to a volume without colour")
+        c = None if rgb is None else _stack_rgb(rgb, d.shape)
+        k = split_intrinsics(intrinsics, v)
+        e = extrinsics_from_poses(pose, v)
+        _check_depth_values(d, "depth")
+        return d, c, k, e
+
+
+class TSDFVolume(_LatticeVolume):
+    """A dense TSDF volume of ``dims = (nx, ny, nz)`` voxels of ``voxel_length`` whose first voxel's corner is ``origin``: voxel (i, j, k)
+    has its centre at origin + (index + 0.5) voxel_length.  ``tsdf`` / ``weight`` are float32 [nx,ny,nz] device tensors, zero until a
+    view has been integrated.  ``colour=True`` adds ``colour`` float32 [nx,ny,nz,3] in byte units (else None): every ``integrate`` then
+    needs the views' images."""
+
+    def __init__(self, origin, dims, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC, device=None, colour: bool = False):
+        super().__init__(origin, _check_dims(dims), voxel_length, sdf_trunc, device)
         self.tsdf = torch.zeros(self.dims, dtype=torch.float32, device=self.device)
         self.weight = torch.zeros(self.dims, dtype=torch.float32, device=self.device)
         self.colour = torch.zeros(self.dims + (3,), dtype=torch.float32, device=self.device) if colour else None
@@ -208,20 +229,17 @@ class TSDFVolume:
         [3,3] / [4,4] shared or per view and camera-to-world poses [4,4] / [V,4,4].  The V views are fused in index order by ONE kernel
         that reads and writes the volume once: the bits of V single-view calls.  ``rgb`` — required exactly when the volume has colour —
         is the views' images, uint8 [V,H,W,3] / [H,W,3], or float32 in [0, 1] sent through ``metrics2d.quantize_rgb8``."""
-        d = _stack_depths(depth)
-        v = d.shape[0]
-        if (rgb is None) != (self.colour is None):
-            raise ValueError("rgb is required by a volume with colour" if rgb is None else "rgb was given to a volume without colour")
-        c = None if rgb is None else _stack_rgb(rgb, d.shape)
-        k = split_intrinsics(intrinsics, v)
-        e = extrinsics_from_poses(pose, v)
-        _check_depth_values(d, "depth")
-        d = d.to(self.device, torch.float32).contiguous()
+        self._integrate_prepared(*self._views(depth, intrinsics, pose, rgb))
+
+    def _integrate_prepared(self, d, c, k, e) -> None:
+        """``integrate`` of views that ``_views`` (or a caller with the same checks) has passed."""
+        dev = self.device
+        d = d.to(dev, torch.float32).contiguous()
         if c is None:
-            lib.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel_length, self.sdf_trunc, d, k.to(self.device), e.to(self.device))
+            lib.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel_length, self.sdf_trunc, d, k.to(dev), e.to(dev))
         else:
-            lib.tsdf_integrate_rgb(self.tsdf, self.weight, self.colour, self.origin, self.voxel_length, self.sdf_trunc, d,
-                                   _rgb_bytes(c, self.device), k.to(self.device), e.to(self.device))
+            lib.tsdf_integrate_rgb(self.tsdf, self.weight, self.colour, self.origin, self.voxel_length, self.sdf_trunc, d, _rgb_bytes(c, dev),
+                                   k.to(dev), e.to(dev))
 
     def extract_mesh(self):
         """-> (vertices float64 [n,3], faces int64 [m,3], 0-based) on the device; two empty tensors when nothing crosses zero."""
@@ -250,7 +268,7 @@ def mark_cameras(k: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
     return torch.from_numpy(out)
 
 
-class SparseTSDFVolume:
+class SparseTSDFVolume(_LatticeVolume):
     """A block-sparse TSDF volume over the lattice of ``TSDFVolume(origin, dims, voxel_length)``: the same ``origin`` / ``dims`` /
     ``voxel_length`` taken as float32, voxel (i, j, k) centred at origin + ((float)index + 0.5f) voxel_length with the GLOBAL index — so
     every voxel it holds carries the bits of the dense volume over the same lattice — but only blocks of ``BLOCK``^3 = 8^3 voxels near
@@ -273,14 +291,7 @@ class SparseTSDFVolume:
     that was zero until the call that opened the block."""
 
     def __init__(self, origin, dims, voxel_length: float = VOXEL_LENGTH, sdf_trunc: float = SDF_TRUNC, device=None, colour: bool = False):
-        self.dims = _check_sparse_dims(dims)
-        self.voxel_length = geomargs.positive32(voxel_length, "voxel_length")
-        self.sdf_trunc = geomargs.positive32(sdf_trunc, "sdf_trunc")
-        o = np.asarray(origin.detach().cpu() if isinstance(origin, torch.Tensor) else origin, dtype=np.float64).reshape(-1)
-        if o.shape != (3,) or not np.isfinite(o.astype(np.float32)).all():
-            raise ValueError(f"origin must be three finite numbers, got {origin!r}")
-        self.origin = tuple(float(x) for x in o.astype(np.float32))
-        self.device = geomargs.device(device, "TSDF fusion")
+        super().__init__(origin, _check_sparse_dims(dims), voxel_length, sdf_trunc, device)
         self.block_dims = lib.tsdf_block_lattice(self.dims)
         self._has_colour = bool(colour)
         self.reset()
@@ -302,17 +313,6 @@ class SparseTSDFVolume:
     def memory_bytes(self) -> int:
         """The bytes of the state: table, coordinates and voxel arrays."""
         return sum(t.numel() * t.element_size() for t in (self.block_of, self.block_coords, self.tsdf, self.weight, self.colour) if t is not None)
-
-    def _views(self, depth, intrinsics, pose, rgb, need_rgb: bool):
-        d = _stack_depths(depth)
-        v = d.shape[0]
-        if need_rgb and (rgb is None) != (self.colour is None):
-            raise ValueError("rgb is required by a volume with colour" if rgb is None else "rgb was given to a volume without colour")
-        c = None if rgb is None else _stack_rgb(rgb, d.shape)
-        k = split_intrinsics(intrinsics, v)
-        e = extrinsics_from_poses(pose, v)
-        _check_depth_values(d, "depth")
-        return d.to(self.device, torch.float32).contiguous(), c, k, e
 
     def _allocate(self, d: torch.Tensor, k: torch.Tensor, e: torch.Tensor) -> int:
         marks = torch.zeros(self.block_dims, dtype=torch.uint8, device=self.device)
@@ -336,18 +336,23 @@ class SparseTSDFVolume:
     def allocate(self, depth, intrinsics, pose) -> int:
         """Opens the blocks near the back-projected points of the views (arguments as ``integrate``) -> the number of new blocks."""
         d, _, k, e = self._views(depth, intrinsics, pose, None, False)
-        return self._allocate(d, k, e)
+        return self._allocate(d.to(self.device, torch.float32).contiguous(), k, e)
 
     def integrate(self, depth, intrinsics, pose, rgb=None, allocate: bool = True) -> None:
         """``TSDFVolume.integrate``'s arguments.  First opens the blocks of all its views (unless ``allocate=False``), then applies all
         its views, in index order, to EVERY block allocated so far — one pass over the blocks, whatever V is."""
-        d, c, k, e = self._views(depth, intrinsics, pose, rgb, True)
+        self._integrate_prepared(*self._views(depth, intrinsics, pose, rgb), allocate=allocate)
+
+    def _integrate_prepared(self, d, c, k, e, allocate: bool = True) -> None:
+        """``integrate`` of views that ``_views`` (or a caller with the same checks) has passed."""
+        dev = self.device
+        d = d.to(dev, torch.float32).contiguous()
         if allocate:
             self._allocate(d, k, e)
         if self.n_blocks == 0:
             return
         lib.tsdf_sparse_integrate(self.tsdf, self.weight, self.colour, self.block_coords, self.dims, self.origin, self.voxel_length,
-                                  self.sdf_trunc, d, None if c is None else _rgb_bytes(c, self.device), k.to(self.device), e.to(self.device))
+                                  self.sdf_trunc, d, None if c is None else _rgb_bytes(c, dev), k.to(dev), e.to(dev))
 
     def extract_mesh(self):
         """-> (vertices float64 [n,3], faces int64 [m,3], 0-based) on the device: blocks in id order, cells in local C order, vertices
@@ -460,19 +465,9 @@ def _fuse_maps(depths, colours, intrinsics, poses, bounds, voxel_length, sdf_tru
         if found is None:
             return geomargs.empty_mesh(dev) + (() if c is None else (torch.empty(0, 3, dtype=torch.float64, device=dev),))
         box = bounds_box((found[0].numpy() - tr, found[1].numpy() + tr), vl, sparse)
-    if sparse:
-        vol = SparseTSDFVolume(box[0], box[1], voxel_length=vl, sdf_trunc=tr, device=dev, colour=c is not None)
-        vol._allocate(d, k, e)
-        if vol.n_blocks:
-            lib.tsdf_sparse_integrate(vol.tsdf, vol.weight, vol.colour, vol.block_coords, vol.dims, vol.origin, vol.voxel_length, vol.sdf_trunc, d,
-                                      None if c is None else _rgb_bytes(c, dev), k.to(dev), e.to(dev))
-        return vol.extract_mesh() if c is None else vol.extract_coloured_mesh()
-    vol = TSDFVolume(box[0], box[1], voxel_length=vl, sdf_trunc=tr, device=dev, colour=c is not None)
-    if c is None:
-        lib.tsdf_integrate(vol.tsdf, vol.weight, vol.origin, vol.voxel_length, vol.sdf_trunc, d, k.to(dev), e.to(dev))
-        return vol.extract_mesh()
-    lib.tsdf_integrate_rgb(vol.tsdf, vol.weight, vol.colour, vol.origin, vol.voxel_length, vol.sdf_trunc, d, _rgb_bytes(c, dev), k.to(dev), e.to(dev))
-    return vol.extract_coloured_mesh()
+    vol = (SparseTSDFVolume if sparse else TSDFVolume)(box[0], box[1], voxel_length=vl, sdf_trunc=tr, device=dev, colour=c is not None)
+    vol._integrate_prepared(d, c, k, e)                        # (the views were checked above, under this function's argument names)
+    return vol.extract_mesh() if c is None else vol.extract_coloured_mesh()
 
 
 @torch.no_grad()
