@@ -25,7 +25,11 @@
 //  * with one wave per SIMD nothing else hides the epilogue, the DMA issue or the ring hand-over, so the chunk loop is
 //    software-pipelined by hand over the K steps of a tile (see layer16): epilogue of the previous tile in the first
 //    half, vmcnt(0) + s_barrier in the middle, DMA pieces of chunk c+2 in the second half, bias and first fragments of
-//    chunk c+1 in the last step;
+//    chunk c+1 in the last two steps.  In the inference modes every gap between two MFMAs of that loop has a stated share
+//    (VFN16_GAP_*): a register fragment ring two K steps deep lets one fragment read stand behind an MFMA of its own, the
+//    pending pair's VALU is spread over the step's three gaps, and a DMA piece stands alone behind the step's last MFMA with
+//    its scalar set-up behind the first (profiles/r25/mlp16_gap_budget.md prices every gap; the training modes keep a ring
+//    one step deep and the schedule they had);
 //  * the layer sequence is the shipped one (confs/vf_nerf.conf:13-37) and compiled in: straight-line code, every chunk's
 //    place in the pack, its size and its ring slot are immediates; other geometries return VFN_ERR_UNSUPPORTED and
 //    callers use the fp32 kernels;
@@ -57,8 +61,16 @@ constexpr int VFN16_SAVE_AUX = 2;       // cache policy bits of the training-mod
                                         // +33 %), 0 = default write-back
 constexpr int VFN16_HANDOVER_NUM = 8;   // ring hand-over after K step NKB * n / 16
 constexpr int VFN16_DMA_STEPS = 16;     // the DMA pieces of chunk c+2 are spread over at most this many K steps after it
-constexpr int VFN16_EPI_PER_MFMA = 6;   // VALU instructions of the pending epilogue scheduled behind each MFMA
+constexpr int VFN16_EPI_PER_MFMA = 6;   // VALU instructions of the pending epilogue scheduled behind each MFMA: the most any gap gets
 constexpr int VFN16_EPI_PER_MFMA2 = 9;  // the same for the two-product tiles of the colour branch (two MFMAs per K step)
+// A v_mfma_f32_32x32x16 holds issue for 8 of its 32 cycles: 24 cycles of other issue hide behind it (a GAP).  Shares of a gap in the
+// inference modes' steady state (layer16; priced by tools/mlp16_instruction_mix.py --gaps, profiles/r25/mlp16_gap_budget.md):
+constexpr int VFN16_GAP_PAIR = 3;       // VALU of a plain epilogue pair (7 instructions) behind each of the step's first two MFMAs, the rest
+                                        // behind the third; a pair that completes an operand block (+ 8 v_accvgpr_write_b32) gets
+                                        // VFN16_EPI_PER_MFMA, VFN16_EPI_PER_MFMA - 1 and the rest
+constexpr int VFN16_GAP_PAIR2 = 4;      // two-product tiles: behind the first of the step's two MFMAs (8 with an operand block)
+constexpr int VFN16_GAP_REST = 10;      // "the rest": an upper bound, the last group of a step takes what is left
+constexpr int VFN16_PIECE_SALU = 2;     // scalar instructions that set up one LDS-DMA piece (s_mov_b32 m0, s_add_i32): behind an MFMA AHEAD of the piece's own
 #define VFN16_MAX_CHUNK_KB 39     // (16 act + 3 aux) K-blocks x 2 planes + 1 bias block
 #define VFN16_STATS_WORDS 64      // tail of a pack (256 bytes): per-entry weight statistics, see Pack16Args::stats
 
@@ -299,7 +311,9 @@ enum : int { M16_FEAT = 1, M16_RENDER = 2, M16_TRAIN = 4, M16_BLKOUT = 8, M16_BL
              M16_VF_VEC = 0, M16_FUSED = M16_FEAT | M16_RENDER, M16_VF_BLK = M16_FEAT | M16_BLKOUT, M16_RN_BLK = M16_RENDER | M16_BLKIN,
              M16_VF_VEC_TRAIN = M16_TRAIN, M16_VF_FULL_TRAIN = M16_FEAT | M16_TRAIN, M16_FUSED_TRAIN = M16_FUSED | M16_TRAIN };
 
-constexpr int VFN16_FDEPTH = 2;   // A-fragment ring: K steps in registers (1 ahead)
+constexpr int VFN16_FDEPTH = 3;   // A-fragment ring of the inference modes: K steps in registers (2 ahead: a fragment read stands behind an
+                                  // MFMA of step st - 2, at most one read per gap beside other work); the training modes keep 2 (1 ahead)
+constexpr int fdepth_of(int mode) { return (mode & 4 /* M16_TRAIN */) ? 2 : VFN16_FDEPTH; }
 #define VFN16_SLOT (VFN16_MAX_CHUNK_KB * 64)   // uint4 elements per LDS ring slot
 #define VFN16_WAVES 4
 #define VFN16_PTS 128                          // points per workgroup (32 per wave)
@@ -464,6 +478,7 @@ struct Carry16 {
     f32x16 pend;
     f32x16 bias;
     half8 fh0, fl0;
+    half8 fh1, fl1;      // fragment ring two steps deep: the next chunk's second K step
     uint32_t lm[4];      // training: sign bits of the layer being produced, 16 per finished tile (tile t -> half t & 1 of dword t >> 1)
     unsigned long long sat;   // lanes (as a wave mask, kept in scalar registers) whose ReLU output reached VFN16_CLAMP: the clamp acted
 };
@@ -514,16 +529,58 @@ __device__ __forceinline__ void dma_chunk(const Pipe16& p, int wave, int lane) {
     }
 }
 
+// Chunk C is readable only behind the s_barrier of the hand-over that published it: both halves below are called at or after the K
+// step that follows it (layer16 asserts that), or behind the prologue's barrier.
 template <int MODE, int C>
-__device__ __forceinline__ void prefetch_chunk(Carry16& cy, const Pipe16& p, int lane) {
+__device__ __forceinline__ void prefetch_bias(Carry16& cy, const Pipe16& p, int lane) {
     constexpr ChunkD d = chunk_of(MODE, C);
     const uint4* cb = p.lds + slot_base(MODE, C);
     const f32x4v* bb = reinterpret_cast<const f32x4v*>(cb + (mode_one(MODE) ? (d.kb - 1) / 2 : d.kb - 1) * 64) + (lane >> 5) * 4;
     const f32x4v b0 = bb[0], b1 = bb[1], b2 = bb[2], b3 = bb[3];
 #pragma unroll
     for (int q = 0; q < 4; ++q) { cy.bias[q] = b0[q]; cy.bias[4 + q] = b1[q]; cy.bias[8 + q] = b2[q]; cy.bias[12 + q] = b3[q]; }
+}
+// the fragments of the chunk's first fdepth_of(MODE) - 1 K steps, the planes layer16 reads there and no others
+constexpr int chunk_nkb(int mode, int c) { return (chunk_of(mode, c).kb - 1) / 2; }
+constexpr bool chunk_reads_lo(int mode, int c, int st) {
+    return !mode_one(mode) && (!chunk_two(mode, c) || st >= chunk_nkb(mode, c) - chunk_of(mode, c).aux);
+}
+constexpr int chunk_first_reads(int mode, int c) {      // how many ds_read_b128 prefetch_frags issues
+    int n = 1 + chunk_reads_lo(mode, c, 0);
+    if (fdepth_of(mode) > 2 && chunk_nkb(mode, c) > 1) n += 1 + chunk_reads_lo(mode, c, 1);
+    return n;
+}
+template <int MODE, int C>
+__device__ __forceinline__ void prefetch_frags(Carry16& cy, const Pipe16& p, int lane) {
+    const uint4* cb = p.lds + slot_base(MODE, C);
+    constexpr int FB = mode_one(MODE) ? 1 : 2;
     cy.fh0 = __builtin_bit_cast(half8, cb[0 * 64 + lane]);
-    if (!chunk_two(MODE, C) && !mode_one(MODE)) cy.fl0 = __builtin_bit_cast(half8, cb[1 * 64 + lane]);     // (no two-product chunk starts with an encoding block)
+    if constexpr (chunk_reads_lo(MODE, C, 0)) cy.fl0 = __builtin_bit_cast(half8, cb[1 * 64 + lane]);     // (no two-product chunk starts with an encoding block)
+    if constexpr (fdepth_of(MODE) > 2 && chunk_nkb(MODE, C) > 1) {
+        cy.fh1 = __builtin_bit_cast(half8, cb[FB * 64 + lane]);
+        if constexpr (chunk_reads_lo(MODE, C, 1)) cy.fl1 = __builtin_bit_cast(half8, cb[3 * 64 + lane]);
+    }
+}
+template <int MODE, int C>
+__device__ __forceinline__ void prefetch_chunk(Carry16& cy, const Pipe16& p, int lane) {
+    prefetch_bias<MODE, C>(cy, p, lane);
+    prefetch_frags<MODE, C>(cy, p, lane);
+}
+
+// `n` instructions of class MASK (LLVM's SchedGroupMask) at this place of the step's issue order; n is a constant once the K loop is unrolled
+template <int MASK>
+__device__ __forceinline__ void gap_share(int n) {
+    switch (n) {
+        case 1: __builtin_amdgcn_sched_group_barrier(MASK, 1, 0); break;
+        case 2: __builtin_amdgcn_sched_group_barrier(MASK, 2, 0); break;
+        case 3: __builtin_amdgcn_sched_group_barrier(MASK, 3, 0); break;
+        case 4: __builtin_amdgcn_sched_group_barrier(MASK, 4, 0); break;
+        case 5: __builtin_amdgcn_sched_group_barrier(MASK, 5, 0); break;
+        case 6: __builtin_amdgcn_sched_group_barrier(MASK, 6, 0); break;
+        case 8: __builtin_amdgcn_sched_group_barrier(MASK, 8, 0); break;
+        case 10: __builtin_amdgcn_sched_group_barrier(MASK, 10, 0); break;
+        default: break;
+    }
 }
 
 // Two accumulator values -> (hi, lo) halves of element pair (j, j+1) of an operand block.
@@ -677,6 +734,18 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
     // training: the sign-bit collection of the pending tile in MPARTS pieces over the steps [H, H + MPARTS) in front of its stores
     // (the epilogue pairs are done by step E <= H; 0: in one piece at the first store step)
     constexpr int MPARTS = (TRAIN && E <= H) ? (DEND - H >= 4 ? 4 : (DEND - H >= 2 ? 2 : (DEND - H >= 1 ? 1 : 0))) : 0;
+    // Inference modes, tiles of 16 K steps and more: every gap of the steady state gets its share (see VFN16_GAP_*).  Per K step:
+    //   epilogue steps   the pending pair's VALU over the step's gaps, the two fragment reads (for step st + 2) behind the 1st and 3rd MFMA;
+    //   DMA steps        H .. NKB-2 (the last step is kept for the next chunk's fragments): one piece ALONE behind the step's last MFMA, its
+    //                    s_mov m0 / s_add behind the first, the fragment reads behind the first two; where a step has two pieces, each
+    //                    stands alone behind the 2nd and the 3rd MFMA and both reads behind the first;
+    //   step NKB-2       the next chunk's bias block; step NKB-1 its first fragments (two K steps of them).
+    // The first VF layer's tiles (3 K steps: 9 MFMAs for a whole epilogue and up to 10 pieces) and the training modes keep the
+    // schedule they had.
+    constexpr int FD = fdepth_of(MODE);
+    constexpr bool PLACED = !TRAIN && !mode_one(MODE) && FD == 3 && E >= 8 && NKB - 2 >= H;
+    constexpr int DSTI = PLACED ? NKB - 1 - H : 1;
+    static_assert(NKB - 1 >= H, "the next chunk's bias and fragments are read behind the hand-over");
     static_for<NCH>([&](auto ich) {
         constexpr int ch = decltype(ich)::value;
         constexpr int C = C0 + ch;
@@ -698,32 +767,42 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
         const uint4* cb = p.lds + slot_base(MODE, C);
         constexpr int FB = P1 ? 1 : 2;                      // blocks per K step in the slot (compact hi planes / hi + lo)
         f32x16 acc = cy.bias;
-        half8 fh[VFN16_FDEPTH], fl[VFN16_FDEPTH];
+        half8 fh[FD], fl[FD];
         fh[0] = cy.fh0;
         if (!P1 && (!W2 || ACT == 0)) fl[0] = cy.fl0;
+        if constexpr (FD > 2 && NKB > 1) {
+            fh[1] = cy.fh1;
+            if (!P1 && (!W2 || 1 >= ACT)) fl[1] = cy.fl1;
+        }
+        static_assert(chunk_reads_lo(MODE, C, 0) == (!P1 && (!W2 || ACT == 0)) && chunk_nkb(MODE, C) == NKB, "prefetch_frags and layer16 disagree");
         half8 ehi[2], elo[2];
         [[maybe_unused]] int gmax = 0;               // the pending tile's largest pre-activation (bit pattern); lives for E steps of this tile
         [[maybe_unused]] unsigned mbits = 0;
 #pragma unroll
         for (int st = 0; st < NKB; ++st) {
-            constexpr int AHEAD = VFN16_FDEPTH - 1;
+            constexpr int AHEAD = FD - 1;      // (reads of THIS chunk only: st + AHEAD < NKB; the next chunk's come through cy, behind the hand-over)
+            [[maybe_unused]] int n_read = 0, n_piece = 0, n_valu = 0;     // this step's fragment reads, DMA pieces and epilogue VALU (PLACED)
+            [[maybe_unused]] bool blockdone = false;
             if (st + AHEAD < NKB) {
-                fh[(st + AHEAD) % VFN16_FDEPTH] = __builtin_bit_cast(half8, cb[(FB * (st + AHEAD)) * 64 + lane]);
-                if (!P1 && (!W2 || st + AHEAD >= ACT)) fl[(st + AHEAD) % VFN16_FDEPTH] = __builtin_bit_cast(half8, cb[(2 * (st + AHEAD) + 1) * 64 + lane]);
+                fh[(st + AHEAD) % FD] = __builtin_bit_cast(half8, cb[(FB * (st + AHEAD)) * 64 + lane]);
+                n_read = 1;
+                if (!P1 && (!W2 || st + AHEAD >= ACT)) { fl[(st + AHEAD) % FD] = __builtin_bit_cast(half8, cb[(2 * (st + AHEAD) + 1) * 64 + lane]); n_read = 2; }
             }
-            const half8 a_hi = fh[st % VFN16_FDEPTH];
+            const half8 a_hi = fh[st % FD];
             const half8 x_hi = st < ACT ? xin.hi[st < ACT ? st : 0] : aux.hi[st >= ACT ? st - ACT : 0];
             const half8 x_lo = st < ACT ? xin.lo[st < ACT ? st : 0] : aux.lo[st >= ACT ? st - ACT : 0];
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, x_hi, acc, 0, 0, 0);
             if constexpr (!P1) {
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, x_lo, acc, 0, 0, 0);
-                if (!W2 || st >= ACT) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fl[st % VFN16_FDEPTH], x_hi, acc, 0, 0, 0);
+                if (!W2 || st >= ACT) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fl[st % FD], x_hi, acc, 0, 0, 0);
             }
             // -- first half: epilogue pairs of the pending tile
             if (st < E && (ch > 0 || PEPI >= 0)) {
 #pragma unroll
                 for (int pr = st * 8 / E; pr < (st + 1) * 8 / E; ++pr) {
                     const int sblk = pr >> 2, j = (pr & 3) * 2;
+                    n_valu += 7 + (pr == 7);
+                    if ((pr & 3) == 3) blockdone = true;
                     if (ch > 0) epi_pair<EPI, TRAIN, !P1>(cy.pend, gmax, pr, ehi[sblk], elo[sblk], j);
                     else epi_pair<(PEPI >= 0 ? PEPI : 0), TRAIN, !P1>(cy.pend, gmax, pr, ehi[sblk], elo[sblk], j);
                     // the range guard of the pending tile, once its last pair has gone by: one integer compare into the SCALAR mask
@@ -740,7 +819,7 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
                         else { xpend.hi[PKB + sblk] = ehi[sblk]; if constexpr (!P1) xpend.lo[PKB + sblk] = elo[sblk]; }
                     }
                 }
-                if constexpr (!P1) {
+                if constexpr (!P1 && !PLACED) {
                 // one MFMA, then its share of the epilogue in that MFMA's shadow
                 __builtin_amdgcn_sched_group_barrier(0x100, W2 ? 1 : 2, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -771,9 +850,15 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
                 __builtin_amdgcn_s_barrier();
             }
             // -- second half: this step's share of the DMA pieces of chunk c+2
-            if (st >= H && st < H + DST && ddma.kb > 0) {
+            // (PLACED: the next chunk's bias block, read in front of this step's piece — see the issue order below)
+            if constexpr (PLACED) {
+                if (st == NKB - 2 && dnext.kb > 0) { prefetch_bias<MODE, (dnext.kb > 0 ? C + 1 : C)>(cy, p, lane); n_read += 4; }
+            }
+            constexpr int NPC = (DPIECES + VFN16_WAVES - 1) / VFN16_WAVES;      // pieces this wave issues for the chunk
+            if (st >= H && st < H + (PLACED ? DSTI : DST) && ddma.kb > 0) {
 #pragma unroll
-                for (int i = (st - H) * PM / DST; i < (st - H + 1) * PM / DST; ++i) {
+                for (int i = (PLACED ? (st - H) * NPC / DSTI : (st - H) * PM / DST); i < (PLACED ? (st - H + 1) * NPC / DSTI : (st - H + 1) * PM / DST); ++i) {
+                    if (VFN16_WAVES * i < DPIECES) ++n_piece;
                     if (VFN16_WAVES * i + VFN16_WAVES <= DPIECES) dma_piece<ddma.net, ddma.off_kb, slot_base(MODE, C + RING - 1)>(p, piece_blk(wave + VFN16_WAVES * i), lane, P1 ? wave + VFN16_WAVES * i : -1);
                     else if (VFN16_WAVES * i < DPIECES) {
                         // the last, partial round of pieces (a 33-block chunk: its bias block): EVERY wave issues one — the waves past the end
@@ -815,7 +900,35 @@ __device__ __forceinline__ void layer16(const X16& xin, const A16& aux, X16& xou
                 else store_blocks<PKB / 2>(p, xpend);
             }
             // -- last step: the next chunk's bias and first fragments
+            if constexpr (PLACED) {
+                if (st == NKB - 1 && dnext.kb > 0) { prefetch_frags<MODE, (dnext.kb > 0 ? C + 1 : C)>(cy, p, lane); n_read += chunk_first_reads(MODE, dnext.kb > 0 ? C + 1 : C); }
+                // -- this step's issue order, gap by gap: MFMA, then [piece set-up] [fragment reads] [piece] [epilogue VALU]
+                const int nm = (!W2 || st >= ACT) ? 3 : 2;
+                int salu[3] = {0, 0, 0}, rd[3] = {0, 0, 0}, pc[3] = {0, 0, 0}, va[3] = {0, 0, 0};
+                // (a piece writes LDS: hipcc keeps every LDS read of the step that precedes it in the source in front of it, so the piece
+                //  of a one-piece step stands behind the step's LAST MFMA and the reads behind the first two)
+                if (nm == 3) {
+                    if (n_piece == 0) { rd[0] = (n_read + 1) / 2; rd[n_valu > 0 ? 2 : 1] = n_read / 2; }
+                    else if (n_piece == 1) { salu[0] = VFN16_PIECE_SALU; rd[0] = (n_read + 1) / 2; rd[1] = n_read / 2; pc[2] = 1; }
+                    else { salu[0] = VFN16_PIECE_SALU; rd[0] = n_read; pc[1] = 1; salu[2] = VFN16_PIECE_SALU; pc[2] = 1; }
+                    if (n_valu > 0) { va[0] = blockdone ? VFN16_EPI_PER_MFMA : VFN16_GAP_PAIR; va[1] = blockdone ? VFN16_EPI_PER_MFMA - 1 : VFN16_GAP_PAIR; va[2] = VFN16_GAP_REST; }
+                } else {
+                    if (n_piece == 0) rd[0] = n_read;
+                    else if (n_piece == 1) { salu[0] = VFN16_PIECE_SALU; rd[0] = n_read; pc[1] = 1; }
+                    else { salu[0] = VFN16_PIECE_SALU; rd[0] = n_read; pc[0] = 1; salu[1] = VFN16_PIECE_SALU; pc[1] = 1; }
+                    if (n_valu > 0) { va[0] = blockdone ? 2 * VFN16_GAP_PAIR2 : VFN16_GAP_PAIR2; va[1] = VFN16_GAP_REST; }
+                }
+#pragma unroll
+                for (int gp = 0; gp < nm; ++gp) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    gap_share<0x004>(salu[gp]);
+                    gap_share<0x100>(rd[gp]);
+                    gap_share<0x010>(pc[gp]);
+                    gap_share<0x002>(va[gp]);
+                }
+            } else {
             if (st == NKB - 1 && dnext.kb > 0) prefetch_chunk<MODE, (dnext.kb > 0 ? C + 1 : C)>(cy, p, lane);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
         if (EPI == EPI_RELU || EPI == EPI_TANH) {
