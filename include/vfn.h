@@ -855,6 +855,83 @@ int vfn_nn_nearest_list(const double* queries, int64_t n, const double* targets,
                         int64_t* index, double* sqdist, void* stream);
 
 /* =============================================================================================
+ * The closest point ON a triangle mesh (csrc/vfn_proximity.hip, csrc/vfn_proximity_core.h): for every query the distance to the
+ * surface, the point of the surface that attains it, and the face that point lies on.  A SPECIFICATION of ours, following the
+ * closest-point queries of trimesh and Open3D as remembered; verified against neither.  Everything is float64, evaluated without
+ * contraction in the association written here; no result depends on the order in which workgroups arrive; no floating-point atomics.
+ * `info` as above: zero-filled by the caller and only ever OR-ed into, bit 1 = a non-finite coordinate of a query or of a vertex that
+ * a face names, bit 2 = a face index outside [0, n_vertices), through which nothing is read.  1 <= n, n_vertices, n_faces < 2^31.
+ *
+ * THE PAIR ROUTINE  vfn_closest_on_triangle: (q, A, B, C) -> (c[3], d2)  (csrc/vfn_proximity_core.h, one text for device and host), a
+ * pure function of its twelve inputs.  With dot(a, b) = (a0 b0 + a1 b1) + a2 b2, cross(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2,
+ * a0 b1 - a1 b0), every difference, product, sum and quotient rounded once:
+ *   box        lo_k = min(A_k, B_k, C_k), hi_k = max(A_k, B_k, C_k) per axis, by comparisons (lo = A; if B < lo: lo = B; if C < lo:
+ *              lo = C), so that a bound is one of the inputs in its own bits.
+ *   segment(P, Q)   d = Q - P, w = q - P, dd = dot(d, d), t = dot(w, d) / dd.  dd == 0 or t <= 0: P itself (its bits); otherwise
+ *              t >= 1: Q itself; otherwise P + t d per component.
+ *   candidates 1, 2, 3   segment(A, B), segment(B, C), segment(C, A).
+ *   candidate 4     n = cross(B - A, C - A), nn = dot(n, n); only when nn > 0: s = dot(q - A, n) / nn, p = q - s n per component, and
+ *              the three edge functions side(P1, P2) = dot(cross(P2 - P1, p - P1), n) for (A, B), (B, C), (C, A).  p is offered when
+ *              all three are >= 0 (a foot ON an edge's line, side == 0, counts as inside; a NaN side does not).
+ *   candidates 5, 6, 7   A, B, C themselves.
+ *   clamp      every candidate x is replaced per component by: if not (x >= lo) then lo; then if not (x <= hi) then hi.  In exact
+ *              arithmetic this changes nothing; in floating point it moves a component by a rounding error at most; a NaN component
+ *              (possible only where a product of finite inputs overflowed) becomes lo.
+ *   d2         of a clamped candidate x: (dx dx + dy dy) + dz dz with dx = q_x - x_x, ... — vfn_nn_sqdist's expression.
+ *   result     the candidate with the least (d2, candidate number) in lexicographic order: c = that clamped candidate, d2 = its d2.
+ * Candidates 5-7 are NOT in the form this routine was first drawn up in (candidates 1-4 only), which has a flaw: a segment's interior
+ * a vertex is a candidate there only when some segment's t leaves (0, 1).  For a query far above a corner of the triangle, its foot
+ * just inside, both adjacent segments answer with a rounded interior point and candidate 4 with a rounded foot; the true gain over
+ * the corner is far below the rounding of d2, so every one of the four d2 can exceed the corner's by an ulp — and P4 below fails.
+ * With the vertices offered in their own bits P4 holds by construction; tests/test_proximity_host.py records such a pair, and finds
+ * more, on which candidates 1-4 alone break P4.
+ * Properties (tests/test_proximity_host.py holds each):
+ *   P1  finite inputs give a finite c, and no NaN anywhere in (c, d2), for degenerate triangles too (A = B, three collinear points,
+ *       A = B = C: nn > 0 fails or dd == 0 answers).  d2 is finite as long as no difference q - c overflows; beyond that it is +inf,
+ *       never NaN.
+ *   P2  lo <= c <= hi per component, exactly.
+ *   P3  d2 is exactly the point-to-point expression on c.
+ *   P4  d2 <= the point-to-point expression on A, on B and on C, as a bit-exact inequality.
+ *   P5  where every intermediate is exactly representable, c and d2 are the true ones.
+ *
+ * THE SEARCH.  For every query i, over ALL faces j whose three indices lie in [0, n_vertices), the minimum of (d2(q_i, face_j), j) in
+ * lexicographic order: face[i] = the lowest face index that attains the least d2, closest[i, 3] = its c, sqdist[i] = its d2; face[i]
+ * = -1, sqdist[i] = +inf and closest[i] = +inf three times when no face has d2 < +inf (a NaN query).  The definition does not mention a
+ * grid and the grid changes no bit (the argument is in csrc/vfn_proximity.hip; it rests on P2, P3 and the argument of
+ * csrc/vfn_nn.hip).  The grid: box[7] (HOST memory) = o[3], e[3], h as for vfn_nn_nearest, with o / e the componentwise minimum /
+ * maximum over the vertices that some face names, and h, nx, ny, nz under vfn_nn_nearest's limits; cell() is vfn_nn_radius's.
+ *   vfn_tri_cell_ranges  one lane per face j: tri[j, 9] = A, B, C; per axis cell_lo[j, k] = cell(lo_k), cell_hi[j, k] = cell(hi_k);
+ *                     ncells[j] = the product of (cell_hi - cell_lo + 1) >= 1.  A face with an index outside [0, n_vertices):
+ *                     info |= 2, tri[j] = 0, ncells[j] = 0 — no later kernel evaluates a face with ncells = 0.
+ *   vfn_tri_cell_pairs   a face with 1 <= ncells[j] <= big_face_cells writes (key, j) for each of its cells, x outermost, at
+ *                     offset[j] .. offset[j] + ncells[j] (offset = the exclusive prefix sums of the ncells of exactly those faces,
+ *                     n_pairs their total; the caller's, as is the stable sort by key and cell_start afterwards); key as for
+ *                     vfn_nn_radius.  Faces with ncells[j] > big_face_cells are LARGE: the caller lists them in ascending order.
+ *                     big_face_cells changes the time only.  Tables that contradict each other: info |= 2, nothing is written.
+ *   vfn_tri_nearest   one lane per query: first every face of large[n_large], then the rings of vfn_nn_nearest over
+ *                     pair_face[n_pairs] (the faces of the pairs in sorted order) and cell_start[nx ny nz + 1], with ITS stop rule —
+ *                     the same s, w, lb and guards, with best = the least d2 so far, large faces included — and its max_rings,
+ *                     order[n], leftover[n] and leftover_count.  A face met in several cells is evaluated again or skipped; either
+ *                     way the result is the same.  n_pairs = 0 (pair_face may be NULL) and n_large = 0 (large may be NULL) are valid.
+ *   vfn_tri_nearest_list  the same minimum for the count queries of list[count] (1 <= count <= n) by all faces in their ORIGINAL
+ *                     order, one wave per query, skipping ncells[j] = 0.  With every query listed this is the all-pairs search.
+ * Both search kernels set bit 1 for a non-finite query coordinate; vfn_tri_cell_ranges for a non-finite named vertex.
+ * ============================================================================================= */
+int vfn_tri_cell_ranges(const double* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces, const double* box,
+                        int32_t nx, int32_t ny, int32_t nz, double* tri, int32_t* cell_lo, int32_t* cell_hi, int32_t* ncells,
+                        int64_t* info, void* stream);
+int vfn_tri_cell_pairs(const int32_t* cell_lo, const int32_t* cell_hi, const int32_t* ncells, const int64_t* offset, int64_t n_faces,
+                       int64_t big_face_cells, int32_t nx, int32_t ny, int32_t nz, int64_t n_pairs, int32_t* key, int32_t* face,
+                       int64_t* info, void* stream);
+int vfn_tri_nearest(const double* queries, int64_t n, const double* tri, int64_t n_faces, const int32_t* pair_face, int64_t n_pairs,
+                    const int32_t* cell_start, const int64_t* large, int64_t n_large, const double* box, int32_t nx, int32_t ny,
+                    int32_t nz, int32_t max_rings, const int64_t* order, int64_t* face, double* closest, double* sqdist,
+                    int64_t* leftover, int64_t* leftover_count, int64_t* info, void* stream);
+int vfn_tri_nearest_list(const double* queries, int64_t n, const double* tri, const int32_t* ncells, int64_t n_faces,
+                         const int64_t* list, int64_t count, int64_t* face, double* closest, double* sqdist, int64_t* info,
+                         void* stream);
+
+/* =============================================================================================
  * Scoring rendered views (csrc/vfn_image.hip): the image half of evaluation/methods.py:549-610 (metrics) — utils/utils.py:235-245
  * (get_psnr), :248-289 (get_ssim), :312-325 (get_l1_cm) and the save_rgb -> PNG -> load_rgb round trip (:73-108).  A float64
  * SPECIFICATION of the reference's formulas (the reference evaluates them in float32).  Everything is float64, evaluated without

@@ -12,6 +12,8 @@ mesh tools/bench_simplify.py uses: the room scene fused at --res^3 (512) from --
     clustering         meshops.simplify_to_faces at the same target (its 16 vertex clusterings), in the same process
     chamfer            metrics3d.chamfer_distance (grid search) between --samples (10^6) samples of the original and of each simplified mesh,
                        from one seed: collapse against clustering at about equal face count
+    surface_deviation  metrics3d.surface_deviation beside it: the one-sided mean / rms / max / median distance from --samples samples of each
+                       simplified mesh to the SURFACE of the original (the closest point on its faces, not on samples of it)
 
 HIP events around each call, one warm-up call, --reps timed calls, the median reported (all repeats are listed).  No test asserts a time.
 
@@ -122,6 +124,11 @@ def main():
         g.manual_seed(23)
         return list(metrics3d.chamfer_distance(mesh, (verts, faces), num_points=args.samples, generator=g, search="grid"))
 
+    def deviation(mesh):
+        g = torch.Generator(device=dev)
+        g.manual_seed(23)
+        return metrics3d.surface_deviation(mesh, (verts, faces), num_points=args.samples, generator=g)
+
     for divisor in args.divisors:
         target = max(1, int(m / divisor))
         line = {"divisor": divisor, "target_faces": target}
@@ -129,11 +136,11 @@ def main():
         line["collapse"] = dict(rounded(t, all_t), faces_out=int(c.faces.shape[0]), vertices_out=int(c.vertices.shape[0]), rounds=c.rounds,
                                 collapsed=c.collapsed, reached=c.reached, seconds_per_round=round(t / max(c.rounds, 1), 6),
                                 largest_absorbed_cost=float(c.cost.max().cpu()) if c.cost.shape[0] else 0.0,
-                                chamfer_mean_median_min_max=chamfer((c.vertices, c.faces)))
+                                chamfer_mean_median_min_max=chamfer((c.vertices, c.faces)), surface_deviation=deviation((c.vertices, c.faces)))
         if not args.no_clustering:
             t, all_t, (s, size) = timed(lambda: meshops.simplify_to_faces((verts, faces), target), args.reps)
             line["clustering"] = dict(rounded(t, all_t), faces_out=int(s.faces.shape[0]), vertices_out=int(s.vertices.shape[0]), voxel_size=size,
-                                      chamfer_mean_median_min_max=chamfer((s.vertices, s.faces)))
+                                      chamfer_mean_median_min_max=chamfer((s.vertices, s.faces)), surface_deviation=deviation((s.vertices, s.faces)))
             line["collapse_over_clustering_seconds"] = round(line["collapse"]["seconds"] / line["clustering"]["seconds"], 3)
         result["targets"].append(line)
         print(json.dumps(line), flush=True)

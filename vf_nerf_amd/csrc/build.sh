@@ -9,7 +9,7 @@ OUT=${VFN_OUT:-libvfn.so}
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=${ARCH} -Wall -Wno-unused-function"
 # vfn_mlp16 / vfn_bwd16: accumulators in arch VGPRs (all AGPRs hold activations), full unrolling of the K loops
 MFMA16="-mllvm -amdgpu-mfma-vgpr-form -mllvm -pragma-unroll-threshold=10000000"
-UNITS="vfn_pack vfn_mlp vfn_mlp_bwd vfn_dw16 vfn_dwf vfn_unfold vfn_bwd16 vfn_mlp16 vfn_rays vfn_grid vfn_bstat vfn_adam vfn_render vfn_wgrad vfn_loss vfn_train vfn_mesh vfn_metrics vfn_tsdf vfn_raster vfn_icp vfn_nn vfn_image vfn_normals vfn_voxel vfn_cc vfn_orient vfn_simplify vfn_collapse vfn_kmeans"
+UNITS="vfn_pack vfn_mlp vfn_mlp_bwd vfn_dw16 vfn_dwf vfn_unfold vfn_bwd16 vfn_mlp16 vfn_rays vfn_grid vfn_bstat vfn_adam vfn_render vfn_wgrad vfn_loss vfn_train vfn_mesh vfn_metrics vfn_tsdf vfn_raster vfn_icp vfn_nn vfn_image vfn_normals vfn_voxel vfn_cc vfn_orient vfn_simplify vfn_collapse vfn_kmeans vfn_proximity"
 
 extra_flags() {
   case "$1" in
@@ -17,7 +17,7 @@ extra_flags() {
     vfn_mlp16)  echo "$MFMA16 ${VFN_MLP16_EXTRA:-}" ;;
     vfn_bwd16)  echo "$MFMA16 ${VFN_BWD16_EXTRA:-}" ;;
     vfn_dw16)   echo "${VFN_DW16_EXTRA:-}" ;;
-    vfn_rays|vfn_grid|vfn_mesh|vfn_metrics|vfn_tsdf|vfn_raster|vfn_icp|vfn_nn|vfn_image|vfn_normals|vfn_voxel|vfn_cc|vfn_orient|vfn_collapse|vfn_simplify|vfn_kmeans) echo "-ffp-contract=off" ;;
+    vfn_rays|vfn_grid|vfn_mesh|vfn_metrics|vfn_tsdf|vfn_raster|vfn_icp|vfn_nn|vfn_proximity|vfn_image|vfn_normals|vfn_voxel|vfn_cc|vfn_orient|vfn_collapse|vfn_simplify|vfn_kmeans) echo "-ffp-contract=off" ;;
     *) v="VFN_$(echo "${1#vfn_}" | tr a-z A-Z)_EXTRA"; echo "${!v:-}" ;;      # (any other unit: VFN_<UNIT>_EXTRA, e.g. tools/build_unit_variant.sh)
   esac
 }

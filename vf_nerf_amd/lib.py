@@ -49,6 +49,7 @@ EXPORTS = (
     "vfn_raster_depth", "vfn_smooth_laplacian_step",
     "vfn_transform_points", "vfn_nn_radius", "vfn_icp_accumulate_workspace_bytes", "vfn_icp_accumulate",
     "vfn_nn_nearest", "vfn_nn_nearest_list",
+    "vfn_tri_cell_ranges", "vfn_tri_cell_pairs", "vfn_tri_nearest", "vfn_tri_nearest_list",
     "vfn_image_quantize8", "vfn_image_scores_workspace_bytes", "vfn_image_scores", "vfn_image_abs_err",
     "vfn_face_normals", "vfn_vertex_normals", "vfn_normal_dots",
     "vfn_voxel_keys", "vfn_voxel_means",
@@ -1584,6 +1585,109 @@ def nn_nearest(queries: torch.Tensor, grid, max_rings: int, order: Optional[torc
                                           _ptr(leftover, "leftover", torch.int64), C.c_int64(left), _ptr(index, "index", torch.int64),
                                           _ptr(sqdist, "sqdist", torch.float64), _stream()), "vfn_nn_nearest_list")
     return index, sqdist, left
+
+
+# ------------------------------------------------------------------------------------------------
+# the closest point on a triangle mesh (csrc/vfn_proximity.hip; vf_nerf_amd/metrics3d.py is the public surface)
+# ------------------------------------------------------------------------------------------------
+def proximity_check(status: int, nv: int) -> None:
+    if status & GEOM_STATUS_INDEX:
+        raise VfnError(f"closest point: a face index lies outside [0, {nv})")
+    if status & GEOM_STATUS_NONFINITE:
+        raise VfnError("closest point: a non-finite coordinate in the queries or in a vertex that a face names")
+
+
+def tri_cell_ranges(vertices: torch.Tensor, faces: torch.Tensor, box, dims, info: torch.Tensor):
+    """vertices[V,3] float64, faces[F,3] int64, the grid's box (7 floats) and dims -> (tri[F,9], cell_lo[F,3] int32, cell_hi[F,3] int32,
+    ncells[F] int32) of include/vfn.h: vfn_tri_cell_ranges.  ``info`` (int64 [1], zero-filled by the caller) collects the status bits."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise VfnError(f"tri_cell_ranges: vertices must be [V,3] and faces [F,3], got {tuple(vertices.shape)} / {tuple(faces.shape)}")
+    nv, nf, dev = vertices.shape[0], faces.shape[0], faces.device
+    tri = torch.empty(nf, 9, dtype=torch.float64, device=dev)
+    cell_lo = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    cell_hi = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    ncells = torch.empty(nf, dtype=torch.int32, device=dev)
+    _check(load().vfn_tri_cell_ranges(_ptr(vertices, "vertices", torch.float64), C.c_int64(nv), _ptr(faces, "faces", torch.int64), C.c_int64(nf),
+                                      (C.c_double * 7)(*box), C.c_int32(dims[0]), C.c_int32(dims[1]), C.c_int32(dims[2]),
+                                      _ptr(tri, "tri", torch.float64), _ptr(cell_lo, "cell_lo", torch.int32), _ptr(cell_hi, "cell_hi", torch.int32),
+                                      _ptr(ncells, "ncells", torch.int32), _ptr(info, "info", torch.int64), _stream()), "vfn_tri_cell_ranges")
+    return tri, cell_lo, cell_hi, ncells
+
+
+def tri_cell_pairs(cell_lo: torch.Tensor, cell_hi: torch.Tensor, ncells: torch.Tensor, offset: torch.Tensor, big_face_cells: int, dims,
+                   n_pairs: int, info: torch.Tensor):
+    """-> (key[n_pairs] int32, face[n_pairs] int32), unsorted (include/vfn.h: vfn_tri_cell_pairs).  ``n_pairs`` >= 1."""
+    nf = ncells.shape[0]
+    if tuple(cell_lo.shape) != (nf, 3) or tuple(cell_hi.shape) != (nf, 3) or tuple(offset.shape) != (nf,):
+        raise VfnError("tri_cell_pairs: cell_lo / cell_hi must be [F,3] and offset [F] for ncells [F]")
+    key = torch.empty(n_pairs, dtype=torch.int32, device=ncells.device)
+    face = torch.empty(n_pairs, dtype=torch.int32, device=ncells.device)
+    _check(load().vfn_tri_cell_pairs(_ptr(cell_lo, "cell_lo", torch.int32), _ptr(cell_hi, "cell_hi", torch.int32), _ptr(ncells, "ncells", torch.int32),
+                                     _ptr(offset, "offset", torch.int64), C.c_int64(nf), C.c_int64(big_face_cells), C.c_int32(dims[0]),
+                                     C.c_int32(dims[1]), C.c_int32(dims[2]), C.c_int64(n_pairs), _ptr(key, "key", torch.int32),
+                                     _ptr(face, "face", torch.int32), _ptr(info, "info", torch.int64), _stream()), "vfn_tri_cell_pairs")
+    return key, face
+
+
+def tri_nearest_list(queries: torch.Tensor, tri: torch.Tensor, ncells: torch.Tensor, listed: torch.Tensor, count: int, face: torch.Tensor,
+                     closest: torch.Tensor, sqdist: torch.Tensor, info: torch.Tensor) -> None:
+    """The all-pairs search for the first ``count`` queries of ``listed``, into the rows of face / closest / sqdist they name
+    (include/vfn.h: vfn_tri_nearest_list)."""
+    n, nf = queries.shape[0], tri.shape[0]
+    if (tuple(tri.shape) != (nf, 9) or tuple(ncells.shape) != (nf,) or listed.shape[0] < count or tuple(face.shape) != (n,)
+            or tuple(closest.shape) != (n, 3) or tuple(sqdist.shape) != (n,)):
+        raise VfnError("tri_nearest_list: tri must be [F,9], ncells [F], the list at least count long, and face / closest / sqdist the queries' rows")
+    _check(load().vfn_tri_nearest_list(_ptr(queries, "queries", torch.float64), C.c_int64(n), _ptr(tri, "tri", torch.float64),
+                                       _ptr(ncells, "ncells", torch.int32), C.c_int64(nf), _ptr(listed, "list", torch.int64), C.c_int64(count),
+                                       _ptr(face, "face", torch.int64), _ptr(closest, "closest", torch.float64),
+                                       _ptr(sqdist, "sqdist", torch.float64), _ptr(info, "info", torch.int64), _stream()), "vfn_tri_nearest_list")
+
+
+def tri_nearest(queries: torch.Tensor, grid, max_rings: Optional[int], n_vertices: int, order: Optional[torch.Tensor] = None,
+                info: Optional[torch.Tensor] = None, serve_leftovers: bool = True):
+    """-> (face[n] int64, closest[n,3], sqdist[n], leftover_count) of every query's closest point over ALL faces, ties to the lowest face
+    (include/vfn.h: vfn_tri_nearest).  ``grid`` = (tri[F,9], ncells[F] int32, pair_face[n_pairs] int32, cell_start[cells+1] int32,
+    large[n_large] int64, box: 7 floats, dims: 3 ints).  ``max_rings`` None: no ring search at all, every query goes through the
+    all-pairs kernel (vfn_tri_nearest_list).  Otherwise the ring search leaves the queries that have not stopped after ring
+    ``max_rings`` on a list; ONE host read — the list's length and the status word — and a second launch serves them by all pairs.
+    No bit of the result depends on ``max_rings``, ``order`` or the grid.  With the caller's zero-filled ``info`` (int64 [1]) the status
+    bits are left there for the caller; without it a set bit raises (``proximity_check``).  ``serve_leftovers=False`` stops after the
+    ring launch: the rows of the ``leftover_count`` unsettled queries are then NOT written (tools/bench_proximity.py counts the queries
+    each ring settles that way; nothing else should)."""
+    tri, ncells, pair_face, cell_start, large, box, dims = grid
+    n, nf, dev = queries.shape[0], tri.shape[0], queries.device
+    if max_rings is not None and (isinstance(max_rings, bool) or not isinstance(max_rings, int) or max_rings < 0):
+        raise VfnError(f"tri_nearest: max_rings must be None or a non-negative integer, got {max_rings!r}")
+    if queries.dim() != 2 or queries.shape[1] != 3 or tuple(tri.shape) != (nf, 9) or tuple(ncells.shape) != (nf,):
+        raise VfnError(f"tri_nearest: queries must be [n,3], tri [F,9] and ncells [F], got {tuple(queries.shape)} / {tuple(tri.shape)} / {tuple(ncells.shape)}")
+    if cell_start.shape[0] != dims[0] * dims[1] * dims[2] + 1 or (order is not None and order.shape[0] != n):
+        raise VfnError("tri_nearest: cell_start / order do not have the lengths the grid and the queries give")
+    face = torch.empty(n, dtype=torch.int64, device=dev)
+    closest = torch.empty(n, 3, dtype=torch.float64, device=dev)
+    sqdist = torch.empty(n, dtype=torch.float64, device=dev)
+    own = info is None
+    if own:
+        info = torch.zeros(1, dtype=torch.int64, device=dev)
+    if max_rings is None:
+        listed, left = torch.arange(n, dtype=torch.int64, device=dev), n
+    else:
+        listed = torch.empty(n, dtype=torch.int64, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        n_pairs, n_large = pair_face.shape[0], large.shape[0]
+        _check(load().vfn_tri_nearest(_ptr(queries, "queries", torch.float64), C.c_int64(n), _ptr(tri, "tri", torch.float64), C.c_int64(nf),
+                                      _ptr(pair_face, "pair_face", torch.int32) if n_pairs else None, C.c_int64(n_pairs),
+                                      _ptr(cell_start, "cell_start", torch.int32), _ptr(large, "large", torch.int64) if n_large else None,
+                                      C.c_int64(n_large), (C.c_double * 7)(*box), C.c_int32(dims[0]), C.c_int32(dims[1]), C.c_int32(dims[2]),
+                                      C.c_int32(min(max_rings, 2 ** 31 - 1)), _ptr(order, "order", torch.int64), _ptr(face, "face", torch.int64),
+                                      _ptr(closest, "closest", torch.float64), _ptr(sqdist, "sqdist", torch.float64),
+                                      _ptr(listed, "leftover", torch.int64), _ptr(count, "leftover_count", torch.int64),
+                                      _ptr(info, "info", torch.int64), _stream()), "vfn_tri_nearest")
+        left = min(int(count.cpu()), n)                                          # the one read between the two launches
+    if left and serve_leftovers:
+        tri_nearest_list(queries, tri, ncells, listed, left, face, closest, sqdist, info)
+    if own:
+        proximity_check(int(info.cpu()), n_vertices)
+    return face, closest, sqdist, left
 
 
 def icp_accumulate(queries: torch.Tensor, transform, targets: torch.Tensor, index: torch.Tensor, sqdist: torch.Tensor, anchor,

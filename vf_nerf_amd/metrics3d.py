@@ -20,6 +20,15 @@ threshold — without copying either mesh to the host.
   comes with its index from the grid search, the dots from csrc/vfn_normals.hip, the sums along the fixed tree.
   ``score_mesh(..., normals=True)`` adds it to the entry as "normal consistency" from the same samples and searches.
 
+* ``closest_point`` — every point's nearest point ON a mesh, its distance and the face it lies on (csrc/vfn_proximity.hip, include/vfn.h:
+  ``vfn_closest_on_triangle``, ``vfn_tri_nearest``): exact point-to-triangle, on a uniform grid of the faces with ``nearest``'s ring bound,
+  bit-equal to testing every face.  ``triangle_grid`` builds the grid once; ``surface_distances`` returns the distances alone;
+  ``surface_deviation`` the one-sided mean / rms / max / median from one surface to another — what a mesh operation moved.
+* ``surface="mesh"`` on ``chamfer_distance``, ``score_mesh`` and ``normal_consistency`` (and ``refuse.metrics_3d``) measures the samples of
+  each surface against the other MESH instead of against its samples: no sampling floor under the score, and the neighbour's normal is
+  its face's.  The default ``"samples"`` leaves every call, key and bit as it was.  A specification of ours that follows trimesh's and
+  Open3D's closest-point queries as remembered, verified against neither.
+
 Inputs are numpy arrays or torch tensors on any device; a mesh is a ``mesh.Mesh`` (its ``vertices_scaled`` are used) or a
 ``(vertices, faces)`` pair.  No CPU fallback: ``lib.VfnError`` when no device is visible.
 
@@ -39,16 +48,18 @@ csrc/vfn_voxel.hip): one point per occupied voxel, the mean of the voxel's point
 ``score_mesh(..., min_component_faces=, keep_largest=)`` first culls the small detached pieces of the pred mesh
 (``meshops.filter_components``, csrc/vfn_cc.hip: connected components by shared edges), so that floaters draw no samples.
 
-Out of scope: scale in ICP, and the ``evaluate_3d_reconstruction`` package's cropping, histograms and coloured error clouds.
+Out of scope: scale in ICP, and the ``evaluate_3d_reconstruction`` package's cropping, histograms and coloured error clouds; of the
+closest point: its barycentric coordinates and attribute interpolation, signed distance and inside / outside, ray queries.
 Trimesh's vertex merging is ``meshops.weld``, PLY reading / writing ``vf_nerf_amd.ply``.
 The random numbers are torch's, not
 numpy's: a sampled point set is distributed as trimesh's, it is not the same set.
 """
 from __future__ import annotations
 
+import dataclasses
 import functools
 import math
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -359,16 +370,21 @@ def _rotate(normals: torch.Tensor, transformation: np.ndarray) -> torch.Tensor:
 
 
 def normal_consistency(pred_mesh, ref_mesh, num_points: int = 1000000, generator: Optional[torch.Generator] = None, uniforms=None,
-                       device=None) -> dict:
+                       device=None, surface: str = "samples") -> dict:
     """{"pred_to_ref", "ref_to_pred", "mean"}: ``num_points`` samples of each surface (pred first, then ref, from the same generator, or
     the same ``uniforms`` for both), every sample with the unit normal of its face; per direction the mean of |n(p) . n(q)| over the
     samples p of one surface with q the nearest sample of the other (ties to the lowest index), and the mean of the two means.  The
-    absolute value because neither mesh's winding is trusted.  Sums along the fixed tree (``lib.reduce_stats``), divided on the host."""
+    absolute value because neither mesh's winding is trusted.  Sums along the fixed tree (``lib.reduce_stats``), divided on the host.
+    ``surface="mesh"``: q is the nearest point of the other MESH and n(q) the unit normal of the face it lies on (``closest_point``)."""
+    surface = _check_surface(surface)
     pv, pf = _check_mesh(pred_mesh, "pred_mesh")
     rv, rf = _check_mesh(ref_mesh, "ref_mesh")
     num_points = geomargs.positive_int(num_points, "num_points")
     pred_points, pred_face = sample_surface(pv, pf, num_points, generator=generator, uniforms=uniforms, device=device)
     ref_points, ref_face = sample_surface(rv, rf, num_points, generator=generator, uniforms=uniforms, device=device)
+    if surface == "mesh":
+        return _both_directions_mesh(pred_points, ref_points, (pv, pf), (rv, rf), 0.0, _sample_normals(pv, pf, pred_face),
+                                     _sample_normals(rv, rf, ref_face))[1]
     return _both_directions_normals(pred_points, _sample_normals(pv, pf, pred_face), ref_points, _sample_normals(rv, rf, ref_face), 0.0)[1]
 
 
@@ -381,15 +397,20 @@ def chamfer_from_points(pred_points, ref_points, device=None, search: str = "all
 
 
 def chamfer_distance(pred_mesh, ref_mesh, num_points: int = 2500000, generator: Optional[torch.Generator] = None, device=None,
-                     search: str = "all_pairs"):
+                     search: str = "all_pairs", surface: str = "samples"):
     """``utils.get_chamfer_distance``: ``num_points`` samples of each surface (pred first, then ref, from the same generator), then
-    ``chamfer_from_points`` (``search`` goes there)."""
+    ``chamfer_from_points`` (``search`` goes there).  ``surface="mesh"``: the same samples, each set measured against the other MESH
+    (``closest_point``) instead of the other set, combined in the same way; ``search`` is then not used."""
     search = _check_search(search)
+    surface = _check_surface(surface)
     pv, pf = _check_mesh(pred_mesh, "pred_mesh")
     rv, rf = _check_mesh(ref_mesh, "ref_mesh")
     num_points = geomargs.positive_int(num_points, "num_points")
     pred_points, _ = sample_surface(pv, pf, num_points, generator=generator, device=device)
     ref_points, _ = sample_surface(rv, rf, num_points, generator=generator, device=device)
+    if surface == "mesh":
+        rows, _ = _both_directions_mesh(pred_points, ref_points, (pv, pf), (rv, rf), 0.0)
+        return _chamfer(rows[0], rows[1])
     return chamfer_from_points(pred_points, ref_points, device=device, search=search)
 
 
@@ -419,7 +440,7 @@ def precision_recall_fscore(pred_points, ref_points, threshold: float, device=No
 
 def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: float = 0.05, generator: Optional[torch.Generator] = None,
                uniforms=None, device=None, icp_align: bool = False, icp_threshold: Optional[float] = None, search: str = "all_pairs",
-               normals: bool = False, voxel_size=None, min_component_faces=None, keep_largest=None) -> dict:
+               normals: bool = False, voxel_size=None, min_component_faces=None, keep_largest=None, surface: str = "samples") -> dict:
     """One entry of the reference's ``3d-metrics.json`` (methods.py:794-801): {"chamfer distance": {mean, median, min, max}, "precision",
     "recall", "fscore"} (plus the two counts), from ONE sampling of each mesh and ONE nearest-neighbour search per direction shared
     by both metrics.  ``uniforms`` ([num_points,3]) is used for BOTH meshes when given.
@@ -448,8 +469,19 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
     connectivity; ``min_faces=min_component_faces``, ``keep_largest`` ranked by faces) — before the sampling, so that detached pieces of
     a fused mesh ("floaters") draw no samples — and the entry gains "components": {"connectivity", "found", "kept", "faces_removed",
     "area_removed"} (``area_removed``: the correctly rounded sum of the removed components' areas).  ``ValueError`` if nothing is left.
-    With both None nothing changes: the same keys, bits and draws from the generator as without the keywords."""
+    With both None nothing changes: the same keys, bits and draws from the generator as without the keywords.
+
+    ``surface="mesh"``: the samples of each surface are measured against the other MESH (``closest_point``), not against its samples:
+    the pred samples against the ref mesh (chamfer's pred -> ref half, precision), the ref samples against the pred mesh — the one
+    after the culling — (the ref -> pred half, recall).  A surface scored against itself then scores 0 up to rounding, whatever
+    ``num_points``.  Sampling, ICP, ``voxel_size`` and the culling act as above on the sample sets and the pred mesh.  With
+    ``icp_align`` the moved pred samples are measured against the ref mesh, and the ref samples are moved by the INVERSE of the
+    result ([R^T | -R^T t]) before they are measured against the pred mesh, which stays where it is; with ``normals=True`` the
+    neighbour's normal is the unit normal of the face found (``meshops.face_normals`` at ``face[i]``), and the ref normals are rotated
+    by R^T with their samples.  ``search`` is not used: the grid search serves both directions.  The entry gains "surface": "mesh".
+    With ``surface="samples"`` (the default) nothing changes."""
     search = _check_search(search)
+    surface = _check_surface(surface)
     if not isinstance(normals, (bool, np.bool_)):
         raise ValueError(f"normals must be a bool, got {normals!r}")
     voxel_size = _check_voxel(voxel_size)
@@ -477,7 +509,19 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
         pred_points = icp.transform_points(pred_points, aligned.transformation, device=pred_points.device)
         if normals:
             pred_normals = _rotate(pred_normals, aligned.transformation)
-    if normals:
+    if surface == "mesh":
+        ref_there = ref_points            # the ref samples in the pred mesh's frame
+        if aligned is not None:
+            inverse = _rigid_inverse(aligned.transformation)
+            ref_there = icp.transform_points(ref_points, inverse, device=ref_points.device)
+        if voxel_size is not None:
+            pred_points, ref_there, voxel_entry = _voxel_pair(pred_points, ref_there, voxel_size, pred_points.device)
+        ref_there_normals = None
+        if normals:
+            ref_there_normals = ref_normals if aligned is None else _rotate(ref_normals, inverse)
+        rows, consistency = _both_directions_mesh(pred_points, ref_there, (pv, pf), (rv, rf), threshold,
+                                                  pred_normals if normals else None, ref_there_normals)
+    elif normals:
         rows, consistency = _both_directions_normals(pred_points, pred_normals, ref_points, ref_normals, threshold)
     elif voxel_size is not None:
         pred_points, ref_points, voxel_entry = _voxel_pair(pred_points, ref_points, voxel_size, pred_points.device)
@@ -487,6 +531,8 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
     mean, median, mn, mx = _chamfer(rows[0], rows[1])
     out = {"chamfer distance": {"mean": mean, "median": median, "min": mn, "max": mx}}
     out.update(_prf(rows[1], rows[0]))
+    if surface == "mesh":
+        out["surface"] = "mesh"
     if normals:
         out["normal consistency"] = consistency
     if voxel_size is not None:
@@ -497,3 +543,252 @@ def score_mesh(pred_mesh, ref_mesh, num_points: int = 1000000, distance_thresh: 
         out["icp"] = {"transformation": aligned.transformation.tolist(), "fitness": aligned.fitness, "inlier_rmse": aligned.inlier_rmse,
                       "iterations": aligned.iterations}
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the closest point ON a mesh (csrc/vfn_proximity.hip; include/vfn.h: vfn_tri_nearest)
+# ---------------------------------------------------------------------------------------------------------------------------------
+SURFACES = ("samples", "mesh")
+BIG_FACE_CELLS = 64                # a face whose box touches more cells is tested by every query instead of registered (speed only)
+
+
+class ClosestPoint(NamedTuple):
+    """``closest_point``'s result, device tensors: the point of the surface nearest to every query, its squared distance (the kernel's
+    number), the distance (its square root, rounded once) and the face the point lies on (the lowest index among equals)."""
+    points: torch.Tensor               # [n,3] float64
+    sqdist: torch.Tensor               # [n] float64
+    distance: torch.Tensor             # [n] float64
+    face: torch.Tensor                 # [n] int64
+
+
+@dataclasses.dataclass
+class TriangleGrid:
+    """The faces of a mesh registered in the cells of a uniform grid (include/vfn.h: vfn_tri_cell_ranges, vfn_tri_cell_pairs)."""
+    n_vertices: int
+    tri: torch.Tensor                  # [F,9] float64: every face's three vertices
+    ncells: torch.Tensor               # [F] int32: the cells its box touches (0: a face with a bad index, never evaluated)
+    pair_face: torch.Tensor            # [n_pairs] int32: the faces of the (cell, face) pairs in ascending cell key
+    cell_start: torch.Tensor           # [cells + 1] int32
+    large: torch.Tensor                # [n_large] int64: the faces with ncells > big_face_cells, ascending
+    box: Tuple[float, ...]             # min[3], max[3] over the vertices that some face names, cell edge
+    dims: Tuple[int, int, int]
+    big_face_cells: int
+
+    @property
+    def n_faces(self) -> int:
+        return int(self.tri.shape[0])
+
+    @property
+    def n_pairs(self) -> int:
+        return int(self.pair_face.shape[0])
+
+    @property
+    def n_large(self) -> int:
+        return int(self.large.shape[0])
+
+    def args(self):
+        return self.tri, self.ncells, self.pair_face, self.cell_start, self.large, self.box, self.dims
+
+
+def _check_surface(surface) -> str:
+    if surface not in SURFACES:
+        raise ValueError(f"surface must be one of {SURFACES}, got {surface!r}")
+    return surface
+
+
+def _check_big_face_cells(big_face_cells) -> int:
+    if big_face_cells is None:
+        return BIG_FACE_CELLS
+    if isinstance(big_face_cells, bool) or not isinstance(big_face_cells, (int, np.integer)) or int(big_face_cells) < 0:
+        raise ValueError(f"big_face_cells must be None or a non-negative integer, got {big_face_cells!r}")
+    return int(big_face_cells)
+
+
+def _check_pair_count(n_pairs: int, dims, big_face_cells: int) -> int:
+    if n_pairs >= LIMIT:
+        raise ValueError(f"the faces touch {n_pairs} cells of the {dims[0]} x {dims[1]} x {dims[2]} grid, beyond the 2^31 limit of one pair "
+                         f"list: lower `cells` (fewer cells a face) or `big_face_cells` = {big_face_cells} (more faces on the large list)")
+    return n_pairs
+
+
+def _triangle_grid(v: torch.Tensor, f: torch.Tensor, cells: Optional[int], big_face_cells: int, pairs: bool = True,
+                   info: Optional[torch.Tensor] = None) -> TriangleGrid:
+    """Device vertices [V,3] float64 and faces [F,3] int64 -> their ``TriangleGrid``.  The kernels compute the faces' cell ranges and write
+    the pairs; the plumbing between them is torch's, as for points (``icp.build_grid``): the box over the named vertices (six values
+    cross to the host), the exclusive prefix sums, a stable sort by cell key, the table of first positions.  One more host read: the
+    number of pairs with the status word.  ``pairs=False`` leaves the pair list empty and every face off the large list (what the
+    all-pairs search needs: ``tri`` and ``ncells``).  With the caller's zero-filled ``info`` the status bits stay there; without it a
+    set bit raises."""
+    dev, nv, nf = v.device, v.shape[0], f.shape[0]
+    named = f[((f >= 0) & (f < nv)).all(dim=1)].reshape(-1)
+    if named.shape[0] == 0:
+        lib.proximity_check(lib.GEOM_STATUS_INDEX, nv)
+    named = v[named]
+    box = torch.cat((named.min(dim=0).values, named.max(dim=0).values)).cpu().tolist()
+    if not all(math.isfinite(b) for b in box):
+        lib.proximity_check(lib.GEOM_STATUS_NONFINITE, nv)
+    extent = [box[3 + k] - box[k] for k in range(3)]
+    if not all(math.isfinite(e) for e in extent):
+        raise lib.VfnError("closest point: the mesh's bounding box overflows float64")
+    cap = lib.icp_grid_limits()[0]
+    h = grid_edge(extent, nf, cells)
+    dims = tuple(min(cap, int(math.floor(e / h)) + 1) for e in extent)
+    box = tuple(box) + (h,)
+    own = info is None
+    if own:
+        info = torch.zeros(1, dtype=torch.int64, device=dev)
+    tri, cell_lo, cell_hi, ncells = lib.tri_cell_ranges(v, f, box, dims, info)
+    n_cells = dims[0] * dims[1] * dims[2]
+    pair_face = torch.empty(0, dtype=torch.int32, device=dev)
+    cell_start = torch.zeros(n_cells + 1, dtype=torch.int32, device=dev)
+    large = torch.empty(0, dtype=torch.int64, device=dev)
+    if pairs:
+        count = ncells.to(torch.int64)
+        is_large = count > big_face_cells
+        small = torch.where(is_large, torch.zeros_like(count), count)
+        inclusive = torch.cumsum(small, dim=0)
+        n_pairs, status = (int(x) for x in torch.stack((inclusive[-1], info[0])).cpu())
+        if own:
+            lib.proximity_check(status, nv)
+        _check_pair_count(n_pairs, dims, big_face_cells)
+        large = torch.nonzero(is_large).reshape(-1).contiguous()
+        if n_pairs:
+            key, face = lib.tri_cell_pairs(cell_lo, cell_hi, ncells, (inclusive - small).contiguous(), big_face_cells, dims, n_pairs, info)
+            sorted_key, perm = torch.sort(key, stable=True)
+            pair_face = face[perm].contiguous()
+            cell_start = torch.searchsorted(sorted_key, torch.arange(n_cells + 1, dtype=torch.int32, device=dev)).to(torch.int32).contiguous()
+    elif own:
+        lib.proximity_check(int(info.cpu()), nv)
+    return TriangleGrid(nv, tri, ncells, pair_face, cell_start, large, box, dims, big_face_cells)
+
+
+def triangle_grid(mesh, cells: Optional[int] = None, big_face_cells: Optional[int] = None, device=None) -> TriangleGrid:
+    """mesh -> the ``TriangleGrid`` that ``closest_point`` builds for it, to search the same mesh several times: every face registered in
+    each cell its bounding box touches, on a uniform grid with ``cells`` cells along the longest axis of the box of the vertices the
+    faces name (None: ``grid_edge``'s default for the number of faces; at most 128).  A face that touches more than ``big_face_cells``
+    cells (None: 64) is kept on a list of its own that every query tests.  ``n_pairs``, ``n_large`` and ``dims`` tell how it came out;
+    both keywords change the time only.  ``ValueError`` (it names ``cells``) when the pair list would reach 2^31 entries: the count comes
+    from the range kernel, so that launch and the [F,9] table (72 bytes a face) precede the refusal; the pair kernel, the sort and every
+    search come after it."""
+    v, f = _check_mesh(mesh, "mesh")
+    cells, big_face_cells = _check_cells(cells), _check_big_face_cells(big_face_cells)
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        return _triangle_grid(_dev_points(v, dev), f.to(dev, torch.int64).contiguous(), cells, big_face_cells)
+
+
+def _closest(q: torch.Tensor, grid: TriangleGrid, max_rings: Optional[int], info: Optional[torch.Tensor] = None):
+    """Device queries and a grid -> ``lib.tri_nearest``'s (face, closest, sqdist, leftover_count); ``max_rings`` None = all pairs."""
+    with torch.cuda.device(q.device):
+        order = None if max_rings is None else torch.argsort(icp._cells(q, grid.box, grid.dims, q.device)).contiguous()
+        return lib.tri_nearest(q, grid.args(), max_rings, grid.n_vertices, order=order, info=info)
+
+
+def closest_point(mesh, points, search: str = "grid", max_rings: int = MAX_RINGS, cells: Optional[int] = None,
+                  big_face_cells: Optional[int] = None, device=None) -> ClosestPoint:
+    """mesh (or a ``triangle_grid`` of it), points[n,3] -> a ``ClosestPoint`` on the device: for every point the nearest point of the
+    SURFACE (not of a sample of it), over ALL faces; the squared distance to it, the distance, and the face it lies on — among faces
+    at the same squared distance the lowest index.  The pair routine is include/vfn.h's ``vfn_closest_on_triangle``: float64, a
+    fixed order of operations, exact for a vertex, never NaN for a degenerate face.  ``search="grid"`` walks a uniform grid of the faces
+    ring by ring and ends a query's search by an exact lower bound; a query not ended after ``max_rings`` rings is served by all pairs,
+    as ``nearest`` serves its leftovers.  ``search="all_pairs"`` tests every face for every query.  ``search``, ``max_rings``, ``cells``
+    and ``big_face_cells`` change the time, never a bit.  A NaN / inf coordinate or a face index outside the vertices raises
+    ``lib.VfnError``.  A specification of ours, following trimesh's ``proximity.closest_point`` and Open3D's
+    ``RaycastingScene.compute_closest_points`` as remembered; verified against neither."""
+    grid = mesh if isinstance(mesh, TriangleGrid) else None
+    if grid is None:
+        v, f = _check_mesh(mesh, "mesh")
+    q = _check_points(points, "points")
+    search, max_rings = _check_search(search), _check_max_rings(max_rings)
+    if grid is not None and (cells is not None or big_face_cells is not None):
+        raise ValueError("cells and big_face_cells are the grid's own: give them to triangle_grid")
+    cells, big_face_cells = _check_cells(cells), _check_big_face_cells(big_face_cells)
+    dev = grid.tri.device if grid is not None else _device(device)
+    with torch.cuda.device(dev):
+        if grid is None:
+            grid = _triangle_grid(_dev_points(v, dev), f.to(dev, torch.int64).contiguous(), cells, big_face_cells, pairs=search == "grid")
+        face, closest, sqdist, _ = _closest(_dev_points(q, dev), grid, max_rings if search == "grid" else None)
+    return ClosestPoint(closest, sqdist, torch.sqrt(sqdist), face)
+
+
+def surface_distances(points, mesh, search: str = "grid", device=None) -> torch.Tensor:
+    """points[n,3], mesh -> float64 [n] on the device: every point's distance to the surface (``closest_point``'s ``distance``)."""
+    return closest_point(mesh, points, search=search, device=device).distance
+
+
+def _deviation(dist: torch.Tensor) -> dict:
+    """Distances [n] on the device -> {"mean", "rms", "max", "median"}: sums and the maximum along the fixed tree (``lib.reduce_stats``),
+    the median from the two middle values; one read."""
+    n = dist.shape[0]
+    host = torch.cat((lib.reduce_stats(dist, math.inf)[:3], lib.reduce_stats(dist * dist, math.inf)[:1], _median_pair(dist))).cpu().numpy()
+    return {"mean": float(host[0] / n), "rms": float(math.sqrt(host[3] / n)), "max": float(host[2]), "median": float((host[4] + host[5]) / 2.0)}
+
+
+def surface_deviation(mesh_a, mesh_b, num_points: int = 1000000, generator: Optional[torch.Generator] = None, uniforms=None,
+                      vertices: bool = False, search: str = "grid", device=None) -> dict:
+    """{"mean", "rms", "max", "median"} of the distances from surface ``a`` to surface ``b``: ONE-SIDED — ``num_points`` area-weighted
+    samples of ``a`` (``sample_surface``; ``uniforms`` replaces the random numbers), or with ``vertices=True`` the vertices of ``a`` that
+    its faces name, in ascending index, each measured against the surface of ``b`` itself (``closest_point``).  What a mesh operation
+    moved: ``surface_deviation(simplified, original)``.  rms = sqrt(sum d^2 / n); the median is np.median's."""
+    av, af = _check_mesh(mesh_a, "mesh_a")
+    bv, bf = _check_mesh(mesh_b, "mesh_b")
+    if not isinstance(vertices, (bool, np.bool_)):
+        raise ValueError(f"vertices must be a bool, got {vertices!r}")
+    search = _check_search(search)
+    if not vertices:
+        num_points = geomargs.positive_int(num_points, "num_points")
+    dev = _device(device)
+    if vertices:
+        named = torch.unique(af.to(dev, torch.int64).reshape(-1))
+        if int(named[0]) < 0 or int(named[-1]) >= av.shape[0]:
+            lib.proximity_check(lib.GEOM_STATUS_INDEX, av.shape[0])
+        points = _dev_points(av, dev)[named].contiguous()
+    else:
+        points, _ = sample_surface(av, af, num_points, generator=generator, uniforms=uniforms, device=dev)
+    return _deviation(closest_point((bv, bf), points, search=search, device=dev).distance)
+
+
+def _rigid_inverse(transformation: np.ndarray) -> np.ndarray:
+    """[4,4] rigid -> its inverse [R^T | -R^T t] in float64 (numpy on the host)."""
+    m = np.asarray(transformation, dtype=np.float64)
+    inverse = np.eye(4)
+    inverse[:3, :3] = m[:3, :3].T
+    inverse[:3, 3] = -(m[:3, :3].T @ m[:3, 3])
+    return inverse
+
+
+def _mesh_direction(q: torch.Tensor, qn: Optional[torch.Tensor], mesh, threshold: float, info: torch.Tensor, ninfo: torch.Tensor) -> torch.Tensor:
+    """One direction against a MESH -> device [7] as ``_direction``; with the queries' normals ``qn`` [8]: then the sum of
+    |qn . n(face[i])| with n = ``meshops.face_normals`` of the mesh."""
+    v, f = mesh
+    dev = q.device
+    with torch.cuda.device(dev):
+        v, f = _dev_points(v, dev), f.to(dev, torch.int64).contiguous()
+        grid = _triangle_grid(v, f, None, BIG_FACE_CELLS, info=info)
+        face, _, sq, _ = _closest(q, grid, MAX_RINGS, info=info)
+    row = _direction(torch.sqrt(sq), threshold)
+    if qn is None:
+        return row
+    dots = lib.normal_dots(qn, lib.face_normals(v, f, True, info=ninfo), face, info=ninfo)
+    return torch.cat((row, lib.reduce_stats(dots, math.inf)[:1]))
+
+
+def _both_directions_mesh(pred_points: torch.Tensor, ref_points: torch.Tensor, pred_mesh, ref_mesh, threshold: float,
+                          pred_normals: Optional[torch.Tensor] = None, ref_normals: Optional[torch.Tensor] = None):
+    """``surface="mesh"``: the ref points against the pred MESH (row 0), the pred points against the ref MESH (row 1) -> (host [2,7] as
+    ``_both_directions``, the "normal consistency" entry or None).  The points arrive in the frame of the mesh they are measured
+    against.  One read of the results."""
+    dev = pred_points.device
+    info = torch.zeros(1, dtype=torch.int64, device=dev)
+    ninfo = torch.zeros(1, dtype=torch.int64, device=dev)
+    one = _mesh_direction(ref_points, ref_normals, pred_mesh, threshold, info, ninfo)
+    two = _mesh_direction(pred_points, pred_normals, ref_mesh, threshold, info, ninfo)
+    k = one.shape[0]
+    host = torch.cat((one, two, info.to(torch.float64), ninfo.to(torch.float64))).cpu().numpy()
+    lib.proximity_check(int(host[2 * k]), max(pred_mesh[0].shape[0], ref_mesh[0].shape[0]))
+    lib.normals_check(int(host[2 * k + 1]), "normal consistency")
+    rows = np.stack((host[0:7], host[k:k + 7]))
+    if pred_normals is None:
+        return rows, None
+    a, b = float(host[k + 7] / pred_points.shape[0]), float(host[7] / ref_points.shape[0])
+    return rows, {"pred_to_ref": a, "ref_to_pred": b, "mean": (a + b) / 2.0}

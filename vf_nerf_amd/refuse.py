@@ -123,7 +123,7 @@ def reconstruction_meshes(tsdf_mesh, intrinsics, poses, height: int, width: int,
 def metrics_3d(tsdf_mesh, gt_mesh, intrinsics, poses, height: int, width: int, num_points: int = 1000000, distance_thresh: float = 0.01,
                generator: Optional[torch.Generator] = None, uniforms=None, iterations: int = ITERATIONS, lam: float = LAM,
                icp_align: bool = False, icp_threshold: Optional[float] = None, search: str = "all_pairs", normals: bool = False, voxel_size=None,
-               min_component_faces=None, keep_largest=None, **refuse_args) -> Dict[str, dict]:
+               min_component_faces=None, keep_largest=None, surface: str = "samples", **refuse_args) -> Dict[str, dict]:
     """The dictionary the reference writes to ``3d-metrics.json`` (methods.py:732-741): keys ``tsdf``, ``refused_tsdf``,
     ``tsdf_smoothed``, ``refused_tsdf_smoothed``, each ``metrics3d.score_mesh(mesh, gt_mesh)`` — {"chamfer distance": {mean, median,
     min, max}, "precision", "recall", "fscore", ...} — scored in that order with the one ``generator`` (or the same ``uniforms``).  ``icp_align`` / ``icp_threshold`` go to
@@ -131,8 +131,11 @@ def metrics_3d(tsdf_mesh, gt_mesh, intrinsics, poses, height: int, width: int, n
     through the grid kernel, the same dictionary to the bit), ``normals`` (True: every entry gains "normal consistency") and
     ``voxel_size`` (a value: every entry is scored on the voxel-down-sampled clouds and gains "voxel"; None changes nothing).
     ``min_component_faces`` / ``keep_largest`` go there too (a value: every one of the four meshes is scored without its small detached
-    pieces, ``meshops.filter_components``, and every entry gains "components"; both None change nothing)."""
+    pieces, ``meshops.filter_components``, and every entry gains "components"; both None change nothing).  ``surface`` goes there as
+    well ("mesh": every one of the four meshes and ``gt_mesh`` are measured as surfaces, ``metrics3d.closest_point``, not through
+    their samples, and every entry gains "surface": "mesh"; "samples", the default, changes nothing)."""
     search = metrics3d._check_search(search)
+    surface = metrics3d._check_surface(surface)
     voxel_size = metrics3d._check_voxel(voxel_size)
     if voxel_size is not None and normals:
         raise ValueError("voxel_size together with normals=True: a voxel's normal for normal consistency is not defined here")
@@ -142,5 +145,6 @@ def metrics_3d(tsdf_mesh, gt_mesh, intrinsics, poses, height: int, width: int, n
     dev = meshes["tsdf"][0].device
     return {name: metrics3d.score_mesh(meshes[name], gt_mesh, num_points=num_points, distance_thresh=distance_thresh, generator=generator,
                                        uniforms=uniforms, device=dev, icp_align=icp_align, icp_threshold=icp_threshold, search=search,
-                                       **({"normals": True} if normals else {}), **({} if voxel_size is None else {"voxel_size": voxel_size}), **components_kw)
+                                       **({"normals": True} if normals else {}), **({} if voxel_size is None else {"voxel_size": voxel_size}), **components_kw,
+                                       **({} if surface == "samples" else {"surface": surface}))
             for name in MESH_NAMES}
