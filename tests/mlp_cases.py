@@ -8,7 +8,7 @@ encoding arguments x 2^k are exact, so the float64 values are those of the very 
 layer by 0.70710678f, one ulp from 1 / float32 sqrt(2): below every yardstick here.)  tests/test_mlp_host.py holds the restatement to
 the oracle (oracle/vfnerf_oracle.py: vf_mlp, render_mlp) run in float64.
 
-Networks (``build_net``), all 256 wide:
+Networks (``build_net``), 256 wide but the narrow one:
   c1_det, trained_256, trained_far            fixtures as stored (every running_mean 0, every running_var 1)
   <fixture>+stats                             the same with BatchNorm statistics drawn per output row (``randomise_statistics``):
                                               running_var log-uniform in [1e-3, 4], gamma such that gamma / sqrt(var + eps) is uniform in
@@ -26,6 +26,8 @@ Networks (``build_net``), all 256 wide:
                                               skip at layer 7, the last position vfn_make_plan accepts
   rn_<h>h_m<L>                                rendering nets with h = 1, 3 hidden layers and multires L = 0, 2, 5 (6 + 3 + 6 L <= 40 columns
                                               of the encoding tile: 5 is the largest)
+  vf_4h_w64                                   a narrow vector field: 4 hidden layers of 64, skip at 2, multires 6, 32 features, BatchNorm.  The
+                                              fused kernels have no such geometry: it runs layer by layer (vf_nerf_amd/batchstat.py)
   Fresh nets keep torch's default initialisation with the hidden weights times GAIN (synthetic.scale_hidden_weights) and randomised
   statistics where they have BatchNorm.  They run on the exact-fp32 kernels only (the f16x3 kernels are specialised for the shipped
   geometry).
@@ -53,6 +55,23 @@ yardstick is 1 and the bound on the colours of that family says nothing; every o
 Yardstick: the float32 oracle on the host against float64, scored the same way on the same cases and pooled as the worst over the cases
 of the family (``yardstick``).  A kernel may differ from float64 by its factor times that (test_hip_mlp.py; 8 at the most, the project's
 factor for exact-fp32 kernels).
+
+Gradients (``vf_grad_case`` / ``rn_grad_case``, nets GRAD_VF and GRAD_RN).  The pool rows of a net at coordinate scale 1 that keep every
+pre-activation KINK_MARGIN away from zero (fewer than KINK_CAP of the pool may fail that; c1_det+stats and the hot net do and stay
+out), a fixed random ``coef``, and float64 autograd of the restatement of sum(out * coef): every parameter and, from the same backward,
+every input (``input_grads``).  A case of M rows (GRAD_M) is the first M kink-free rows with the first M rows of ``coef``.
+Scoring (``grad_score``), per parameter tensor and never by the tensor alone:
+  rows      a weight matrix per output row; an input gradient [M, c] per sample row
+  blocks    a weight that reads raw inputs, per named block of input columns (``column_blocks``): xyz and each sin / cos triple of the
+            vector field's first layer; the hidden block, then the same, of its skip layer; points, each view-direction block, normals
+            and features of the rendering net's first layer
+  elems     a bias, gamma or beta per element
+  each figure max |err| over the row, block or element / max(largest |float64 entry| there, GRAD_FLOOR x the tensor's largest
+  |entry|): a condition, not a measurement, and nothing is rejected; a row below one percent of its tensor is held in absolute terms at
+  that percent, so the figure is exactly relative above it and never more than 100 x stricter than max |err| / max |ref| over the
+  tensor ('tensor', helpers.grad_rel_err, printed beside it).
+Yardstick (``grad_yardstick``): the float32 restatement under float32 autograd on the host, on the same rows and ``coef``, scored the
+same way, pooled as the worst over GRAD_M per net, tensor kind (``grad_kind``) and figure.
 
 ``emulate_f16x3``: the split arithmetic of csrc/vfn_mlp16.hip in float64 with exact sums, for the host test's question whether the
 scoring tells a right kernel from a subtly wrong one: weights folded in float32 as the pack kernel folds them and split as
@@ -90,6 +109,9 @@ HOT_TARGET = 500.0
 GAIN = 2.0
 KINK_MARGIN = 1e-4
 GRAD_ROWS = 513
+GRAD_M = (1, 31, 33, 257, None)                            # rows of a gradient case; None: all its rows (at most GRAD_ROWS).  _groups(m) of
+                                                           # both backward paths is 1 below 512 rows and 2 from there on
+GRAD_FLOOR = 1e-2
 MAX_FACTOR = 8.0
 
 FIXTURES = ("c1_det", "trained_256", "trained_far")
@@ -98,12 +120,15 @@ HOT = "c1_det+stats+hot"
 FRESH_VF = {"vf_2h": dict(hidden=2, skip=None, multires=0, feats=0, bn=False),
             "vf_4h_skip1": dict(hidden=4, skip=1, multires=3, feats=256, bn=True),
             "vf_8h_skip7": dict(hidden=8, skip=7, multires=6, feats=256, bn=True)}
+NARROW_VF = {"vf_4h_w64": dict(hidden=4, skip=2, multires=6, feats=32, bn=True, width=64)}      # layer-at-a-time kernels only
 FRESH_RN = {f"rn_{h}h_m{mr}": dict(hidden=h, multires=mr) for h in (1, 3) for mr in (0, 2, 5)}
 GRAD_NETS = ("trained_256+stats", "trained_far+stats")     # stand-alone gradient cases (c1_det+stats: 50.5 % of its rows sit within
                                                            # the margin of a kink in the vector-field net, above the cap of one half)
 KINK_CAP = 0.5
 SHIPPED_NETS = FIXTURES + STATS + (HOT,)                   # both kernels
 ALL_NETS = SHIPPED_NETS + tuple(FRESH_VF) + tuple(FRESH_RN)
+GRAD_VF = GRAD_NETS + tuple(FRESH_VF) + tuple(NARROW_VF)   # nets whose vector field / rendering net has gradient cases
+GRAD_RN = GRAD_NETS + tuple(FRESH_RN)
 
 
 F16X3_CLAMP = 937.5            # csrc/vfn_mlp16.hip: VFN16_CLAMP / 2^6
@@ -240,8 +265,8 @@ def randomise_statistics(mod, gen: torch.Generator) -> None:
         bn.bias.copy_((0.2 * torch.randn(n, generator=gen, dtype=F64)).float())
 
 
-def _fresh_vf(hidden: int, skip, multires: int, feats: int, bn: bool):
-    cfg = settings.VFNetConfig(input_dims=3, output_dims=3, dimensions=[256] * hidden, feature_vector_dims=feats, embedder_multires=multires,
+def _fresh_vf(hidden: int, skip, multires: int, feats: int, bn: bool, width: int = 256):
+    cfg = settings.VFNetConfig(input_dims=3, output_dims=3, dimensions=[width] * hidden, feature_vector_dims=feats, embedder_multires=multires,
                                weight_norm=False, batch_norm=bn, skip_connection_in=[skip] if skip is not None else [], bias_init=0.0,
                                dropout=False, dropout_probability=0.0, xavier_init=False, init="")
     return networks.VectorFieldNetwork(cfg)
@@ -293,10 +318,10 @@ def _heat(mod, forward, target: float) -> float:
 @functools.lru_cache(maxsize=None)
 def build_net(name: str) -> Net:
     gen = torch.Generator().manual_seed(_seed("net|" + name))
-    if name in FRESH_VF or name in FRESH_RN:
+    if name in FRESH_VF or name in FRESH_RN or name in NARROW_VF:
         torch.manual_seed(_seed("init|" + name))
-        if name in FRESH_VF:
-            mod = _fresh_vf(**FRESH_VF[name])
+        if name not in FRESH_RN:
+            mod = _fresh_vf(**{**FRESH_VF, **NARROW_VF}[name])
             synthetic.scale_hidden_weights(mod, _NOTHING, GAIN)
             net = Net(name, mod, None)
         else:
@@ -575,6 +600,7 @@ class GradCase:
     out: torch.Tensor                    # float64 output
     grads: Dict[str, torch.Tensor]       # float64: every parameter by its state_dict key, and 'feats' for the rendering net
     rejected: float                      # share of the pool's rows within the margin of a kink
+    input_grads: Dict[str, torch.Tensor]     # float64, from the same backward: 'points' (vector field); 'points', 'dirs', 'normals', 'feats'
 
 
 def _leaves(sd):
@@ -584,38 +610,184 @@ def _leaves(sd):
     return {k: v for k, v in sd.items() if v.requires_grad}
 
 
+def _rows_of(m: Optional[int], full: int) -> int:
+    return full if m is None else m
+
+
 @functools.lru_cache(maxsize=None)
-def vf_grad_case(name: str) -> GradCase:
+def _vf_grad_rows(name: str):
+    """(points, coef, rejected share) of the net's gradient case at its full row count: the pool's rows away from every kink."""
     fam, net = family(name, 1.0), build_net(name)
     trace = []
     with torch.no_grad():
         vf64(fam.points.to(F64), net.vf_sd(), trace=trace, **net.vf_args)
     ok = _away_from_kinks(trace)
     pts = fam.points[ok][:GRAD_ROWS].contiguous()
+    assert bool((pts[:3] == 0).all(dim=1).any()), f"{name}: the point (0, 0, 0) sits within the margin of a kink"
+    if not bool(((pts[:3, 0] == 0) & torch.signbit(pts[:3, 0])).any()):
+        # the pool's row that starts with -0.0 is within the margin of a kink: the first kink-free one of 64 drawn for it takes row 2
+        cand = (2.0 * torch.rand(64, 3, generator=torch.Generator().manual_seed(_seed("minus zero|" + name)), dtype=F64) - 1.0).float()
+        cand[:, 0] = -0.0
+        trace = []
+        with torch.no_grad():
+            vf64(cand.to(F64), net.vf_sd(), trace=trace, **net.vf_args)
+        cand = cand[_away_from_kinks(trace)]
+        pts = torch.cat([pts[:2], cand[:1], pts[2:]])[:GRAD_ROWS].contiguous()
     coef = torch.randn(pts.shape[0], 3 + net.vf._feature_dims(), generator=torch.Generator().manual_seed(_seed("vf coef|" + name)))
-    sd = net.vf_sd()
+    return pts, coef, 1.0 - float(ok.double().mean())
+
+
+def _vf_grads(name: str, m: Optional[int], dtype) -> GradCase:
+    net = build_net(name)
+    pts, coef, rejected = _vf_grad_rows(name)
+    m = _rows_of(m, pts.shape[0])
+    pts, coef = pts[:m].contiguous(), coef[:m].contiguous()
+    sd = net.vf_sd(dtype)
     leaves = _leaves(sd)
-    out = vf64(pts.to(F64), sd, **net.vf_args)
-    (out * coef.to(F64)).sum().backward()
-    return GradCase(dict(points=pts), coef, out.detach(), {k: v.grad for k, v in leaves.items()}, 1.0 - float(ok.double().mean()))
+    p = pts.to(dtype).requires_grad_(True)
+    out = vf64(p, sd, **net.vf_args)
+    (out * coef.to(dtype)).sum().backward()
+    return GradCase(dict(points=pts), coef, out.detach(), {k: v.grad for k, v in leaves.items()}, rejected, dict(points=p.grad))
 
 
 @functools.lru_cache(maxsize=None)
-def rn_grad_case(name: str) -> GradCase:
+def vf_grad_case(name: str, m: Optional[int] = None) -> GradCase:
+    """The first ``m`` kink-free rows (None: all, at most GRAD_ROWS) with the first m rows of ``coef``, float64 autograd of the restatement."""
+    return _vf_grads(name, m, F64)
+
+
+@functools.lru_cache(maxsize=None)
+def _rn_grad_rows(name: str):
     fam, net = family(name, 1.0), build_net(name)
-    mr = net.rn._multires()
     args = (fam.points, fam.normals_in, fam.dirs, fam.feats_in)
     trace = []
     with torch.no_grad():
-        rn64(*(a.to(F64) for a in args), net.rn_sd(), mr, trace=trace)
+        rn64(*(a.to(F64) for a in args), net.rn_sd(), net.rn._multires(), trace=trace)
     ok = _away_from_kinks(trace)
     pts, nrm, dirs, feats = (a[ok][:GRAD_ROWS].contiguous() for a in args)
     coef = torch.randn(pts.shape[0], 3, generator=torch.Generator().manual_seed(_seed("rn coef|" + name)))
-    sd = net.rn_sd()
+    return dict(points=pts, normals=nrm, dirs=dirs, feats=feats), coef, 1.0 - float(ok.double().mean())
+
+
+def _rn_grads(name: str, m: Optional[int], dtype) -> GradCase:
+    net = build_net(name)
+    rows, coef, rejected = _rn_grad_rows(name)
+    m = _rows_of(m, coef.shape[0])
+    rows, coef = {k: v[:m].contiguous() for k, v in rows.items()}, coef[:m].contiguous()
+    sd = net.rn_sd(dtype)
     leaves = _leaves(sd)
-    f64 = feats.to(F64).requires_grad_(True)
-    out = rn64(pts.to(F64), nrm.to(F64), dirs.to(F64), f64, sd, mr)
-    (out * coef.to(F64)).sum().backward()
+    x = {k: v.to(dtype).requires_grad_(True) for k, v in rows.items()}
+    out = rn64(x["points"], x["normals"], x["dirs"], x["feats"], sd, net.rn._multires())
+    (out * coef.to(dtype)).sum().backward()
     grads = {k: v.grad for k, v in leaves.items()}
-    grads["feats"] = f64.grad
-    return GradCase(dict(points=pts, normals=nrm, dirs=dirs, feats=feats), coef, out.detach(), grads, 1.0 - float(ok.double().mean()))
+    grads["feats"] = x["feats"].grad
+    return GradCase(rows, coef, out.detach(), grads, rejected, {k: v.grad for k, v in x.items()})
+
+
+@functools.lru_cache(maxsize=None)
+def rn_grad_case(name: str, m: Optional[int] = None) -> GradCase:
+    return _rn_grads(name, m, F64)
+
+
+def grad_case(name: str, which: str, m: Optional[int] = None) -> GradCase:
+    return vf_grad_case(name, m) if which == "vf" else rn_grad_case(name, m)
+
+
+# ------------------------------------------------------------------------------------------------
+# scoring of gradients: per output row, per input-column block, per element; never per tensor alone
+# ------------------------------------------------------------------------------------------------
+def grad_kind(key: str) -> str:
+    """'weight', 'bias' (of a Linear), 'gamma', 'beta' (of a BatchNorm), or the name of an input ('points', 'normals', 'feats', ...)."""
+    if not key.startswith("layers."):
+        return key
+    parts = key.split(".")                # layers.<i>.weight | layers.<i>.0.weight (Linear) | layers.<i>.1.weight (BatchNorm)
+    bn = len(parts) == 4 and parts[2] == "1"
+    return ("gamma" if bn else "weight") if key.endswith("weight") else ("beta" if bn else "bias")
+
+
+def _encoding_blocks(multires: int, first: int, tag: str) -> List[Tuple[str, int, int]]:
+    out = [(tag, first, first + 3)]
+    for k in range(multires):
+        out += [(f"{tag}.sin{k}", first + 3 + 6 * k, first + 6 + 6 * k), (f"{tag}.cos{k}", first + 6 + 6 * k, first + 9 + 6 * k)]
+    return out
+
+
+def column_blocks(key: str, net: Net, which: str) -> Optional[List[Tuple[str, int, int]]]:
+    """The named input-column blocks (name, first, end) of a weight that reads raw inputs; None for every other tensor."""
+    if grad_kind(key) != "weight":
+        return None
+    layer = int(key.split(".")[1])
+    if which == "vf":
+        mr = net.vf._multires()
+        pe = 3 + 6 * mr if mr > 0 else 3
+        if layer == 0:
+            return _encoding_blocks(mr, 0, "xyz")
+        if layer in net.vf.skip_connection_in:
+            n_prev = net.vf._linear(layer).in_features - pe
+            return [("hidden", 0, n_prev)] + _encoding_blocks(mr, n_prev, "xyz")
+        return None
+    if layer != 0:
+        return None
+    mr = net.rn._multires()
+    pe = 3 + 6 * mr if mr > 0 else 3
+    return [("points", 0, 3)] + _encoding_blocks(mr, 3, "dirs") + [("normals", 3 + pe, 6 + pe), ("feats", 6 + pe, net.rn._linear(0).in_features)]
+
+
+def _held(err: torch.Tensor, ref: torch.Tensor, top: float) -> float:
+    """max |err| over the group / max(largest |float64 entry| of the group, GRAD_FLOOR x the tensor's largest |entry|), worst group;
+    ``err`` and ``ref`` are [groups, entries]."""
+    scale = ref.abs().amax(dim=1).clamp_min(GRAD_FLOOR * top)
+    e = err.amax(dim=1)
+    if top == 0.0:
+        return 0.0 if float(e.max()) == 0.0 else float("inf")
+    return float((e / scale).max())
+
+
+def grad_score(got: torch.Tensor, ref: torch.Tensor, key: str, net: Net, which: str = "vf") -> Dict[str, float]:
+    """Figures of one gradient tensor against float64: 'tensor' (max |err| / max |ref|, what helpers.grad_rel_err gives) beside
+    'rows' (a weight matrix, per output row; an input gradient [M, c], per sample row), 'blocks' (a weight that reads raw inputs, per
+    named block of input columns) or 'elems' (a vector, per element).  A row, block or element below GRAD_FLOOR of its tensor's largest
+    entry is held in absolute terms at that share."""
+    got, ref = got.detach().to("cpu", F64), ref.detach().to("cpu", F64)
+    assert got.shape == ref.shape, (key, tuple(got.shape), tuple(ref.shape))
+    err, top = (got - ref).abs(), float(ref.abs().max())
+    out = {"tensor": _held(err.reshape(1, -1), ref.reshape(1, -1), top)}
+    if ref.dim() == 1:
+        out["elems"] = _held(err.reshape(-1, 1), ref.reshape(-1, 1), top)
+        return out
+    out["rows"] = _held(err, ref, top)
+    blocks = column_blocks(key, net, which)
+    if blocks is not None:
+        assert blocks[-1][2] == ref.shape[1] and all(a[2] == b[1] for a, b in zip(blocks, blocks[1:])), (key, blocks)
+        out["blocks"] = max(_held(err[:, a:b].reshape(1, -1), ref[:, a:b].reshape(1, -1), top) for _, a, b in blocks)
+    return out
+
+
+def grad_scores(got: Dict[str, torch.Tensor], ref: Dict[str, torch.Tensor], net: Net, which: str) -> Dict[str, Dict[str, float]]:
+    return {k: grad_score(v, ref[k], k, net, which) for k, v in got.items()}
+
+
+def pool_by_kind(scores: Dict[str, Dict[str, float]], pool: Optional[Dict[Tuple[str, str], float]] = None) -> Dict[Tuple[str, str], float]:
+    """{(tensor kind, figure): worst over the tensors of that kind}."""
+    pool = {} if pool is None else pool
+    for key, figs in scores.items():
+        for fig, v in figs.items():
+            k = (grad_kind(key), fig)
+            pool[k] = max(pool.get(k, 0.0), v)
+    return pool
+
+
+def _all_grads(case: GradCase) -> Dict[str, torch.Tensor]:
+    return {**case.grads, **case.input_grads}
+
+
+@functools.lru_cache(maxsize=None)
+def grad_yardstick(name: str, which: str = "vf") -> Dict[Tuple[str, str], float]:
+    """The float32 restatement under float32 autograd on the host against the float64 case, on the same rows and ``coef``, scored the
+    same way and pooled as the worst over GRAD_M: {(tensor kind, figure): value}."""
+    net, pool = build_net(name), {}
+    for m in GRAD_M:
+        ref = grad_case(name, which, m)
+        host = (_vf_grads if which == "vf" else _rn_grads)(name, m, torch.float32)
+        pool_by_kind(grad_scores(_all_grads(host), _all_grads(ref), net, which), pool)
+    return pool

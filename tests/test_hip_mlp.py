@@ -101,6 +101,38 @@ Bounds: MODE_TOL of tests/test_hip_backward.py, unchanged.  Measured worst param
   model.render           f16x3+f16act+f16dy 9.6e-04 (1e-3, rn.layers.1.0.weight, 2 units on the other side of zero), fp32 2.6e-05 (1e-4),
                          the two device runs against each other 9.6e-04 (1e-3); the same figures in two runs
 
+Gradients on every geometry, inputs included (test_*_gradients_exact, test_*_gradients_split, test_rendering_inputs_without_a_gradient).
+Cases, scoring (per output row, per named block of input columns, per element; an input gradient per sample row) and the yardstick
+(float32 autograd of the float32 restatement on the host, worst over GRAD_M per net, tensor kind and figure): tests/mlp_cases.py.
+Exact arithmetic (precision "fp32") is asserted at MAX_FACTOR = 8 x the yardstick in every figure at every M of GRAD_M, beside MODE_TOL
+per tensor.  "fused": only the parameters ask (vfn_vf_mlp_fwd_train, vfn_mlp_bwd_chain, _weight_grads, vfn_unfold_kernel); "rows": the
+layer-at-a-time kernels of batchstat.py with the running statistics and the exact products (the points ask too; the narrow net; the
+rendering net, with the normals' and the features' gradients).  Measured on an MI355X, worst over GRAD_M and over the tensors of a net,
+as a multiple of the yardstick:
+  net, path                                        per tensor        rows              blocks            elements
+  trained_256+stats / trained_far+stats vf, fused  2.7 / 2.0         1.4 / 1.1         2.3 / 1.1         2.1 / 1.8
+  the same, rows with the points                   1.6 / 1.3         1.4 / 1.0         1.2 / 1.6         1.3 / 1.2
+  vf_2h / vf_4h_skip1 / vf_8h_skip7, fused         1.4 / 1.5 / 2.3   1.1 / 1.1 / 1.7   0.7 / 0.9 / 1.3   1.2 / 1.5 / 1.7
+  vf_4h_skip1 / vf_8h_skip7, rows with the points  1.5 / 1.6         2.1 / 1.3         1.1 / 1.5         2.1 / 1.7
+  vf_4h_w64, rows (with and without the points)    2.0               2.2               1.2               1.7
+  trained_256+stats / trained_far+stats rn, rows   1.4 / 2.0         1.8 / 1.4         1.4 / 1.8         1.6 / 1.4
+  rn_1h_m0 / m2 / m5, rows                         2.0 / 1.9 / 2.0   1.8 / 1.5 / 1.3   1.1 / 0.9 / 1.5   1.2 / 1.1 / 1.7
+  rn_3h_m0 / m2 / m5, rows                         1.3 / 1.6 / 1.6   1.3 / 1.6 / 1.7   1.4 / 1.1 / 2.1   1.4 / 1.1 / 3.3
+  (worst: 3.3 x, one gamma element of rn_3h_m5 at M = 257, 4.3e-05 against 1.3e-05; the points' rows 1.0 .. 2.1 x, 4e-06 .. 1e-05)
+The 16- and 22-bit arithmetics at the full row count: per tensor inside MODE_TOL (the shipped nets: f16x3 8.4e-05 of 2e-4, default 16-bit
+storages 6.0e-04 of 1e-3; the fresh rendering nets on the split products 4.3e-05 of 2e-4) or, for what MODE_TOL has no entry for (the
+vector field layer by layer, the normals), inside the 2e-3 of batchstat._arith (worst 9.5e-05); the new figures are printed on MLPGRAD
+lines and not bounded.  As multiples of the yardstick:
+  fused f16x3 chain, shipped vf                    67 .. 78          7 .. 9            63 .. 72          20 .. 42
+  ... with the default 16-bit storages             393 .. 488        92 .. 121         259 .. 318        396 .. 605   (a gamma element 3.6e-02 off)
+  rows, split products, vf (5 nets)                75 .. 148         40 .. 143         58 .. 119         31 .. 82
+  rows, split products, rn (8 nets)                97 .. 163         81 .. 125         66 .. 111         45 .. 121
+Refused at the call, before any launch (REFUSED; the rendering net's inputs in test_rendering_inputs_without_a_gradient):
+  vf_2h with points that ask       the points' gradient comes from the layer-at-a-time kernels, which apply BatchNorm after every Linear
+                                   but the last; vf_2h has none (NotImplementedError).  Its parameters' gradients: the fused chain
+  rendering net, points or dirs    the backward has no gradient for them and the reference's trainer never asks (NotImplementedError,
+                                   naming the input); detach_normals=True leaves normals.grad None, as the reference's detach does
+
 What a wrong fold does to these tests (tried on an MI355X, not committed):
   vfn_pack.hip with b + mean for b - mean, and vfn_mlp16.hip's folded_weight without + 1e-5f      118 of the 161 forward tests fail:
       every family of a net with real statistics on the fp32 entry points, every family on the f16x3 ones
@@ -108,6 +140,7 @@ What a wrong fold does to these tests (tried on an MI355X, not committed):
       all three modes (every BatchNorm gamma off by 0.2 .. 2.3 of its largest entry; in the two f16x3 modes every weight and bias as well,
       4e-3 .. 6e-3) and the render test fails (gamma 2.3 .. 5.1); the rendering forward, which reads neither, passes
 """
+import copy
 import ctypes as C
 import functools
 
@@ -330,12 +363,22 @@ def _model(name, mode):
 GRAD_MODES = ("fp32", "f16x3", "f16x3+f16act+f16dy")
 
 
+def figures(tag, got, case, name, which):
+    """The per-row, per-block and per-element figures of ``got`` against float64 beside the host-float32 yardstick, on an MLPGRAD line
+    (printed for the 16- and 22-bit arithmetics, asserted for the exact one: test_*_gradients_exact).  -> {(kind, figure): (device, yardstick)}."""
+    scores = MC.grad_scores(got, {**case.grads, **case.input_grads}, MC.build_net(name), which)
+    yard = MC.grad_yardstick(name, which)
+    rows = {k: (v, yard[k]) for k, v in MC.pool_by_kind(scores).items()}
+    print(f"MLPGRAD {tag}: " + "  ".join(f"{k}.{f} {v:.2e} | {y:.2e} ({v / y:.1f} x)" for (k, f), (v, y) in sorted(rows.items())))
+    return scores, yard, rows
+
+
 @pytest.mark.parametrize("mode", GRAD_MODES)
 @pytest.mark.parametrize("name", MC.GRAD_NETS)
 def test_vector_field_forward_gradients(name, mode):
     """VectorFieldNetwork.forward (full row) under autograd on rows away from every ReLU kink, a fixed random linear functional of the
-    259 columns: every parameter's gradient, BatchNorm gamma and beta among them, against float64 autograd of the restatement.  (The
-    points get no gradient from this entry point.)"""
+    259 columns: every parameter's gradient, BatchNorm gamma and beta among them, against float64 autograd of the restatement, per
+    tensor; the per-row, per-block and per-element figures are printed.  (Points that ask: test_vector_field_gradients_exact.)"""
     case = MC.vf_grad_case(name)
     _, _, model = _model(name, mode)
     vf = model.vector_field_network
@@ -350,6 +393,7 @@ def test_vector_field_forward_gradients(name, mode):
           f"{max(v for k, v in errs.items() if '.1.' in k):.2e} (bound {MODE_TOL[mode]:g})")
     assert set(errs) == set(case.grads)
     assert all(v < MODE_TOL[mode] for v in errs.values()), {k: v for k, v in errs.items() if v >= MODE_TOL[mode]}
+    figures(f"{name} vector field params {mode} M={case.coef.shape[0]}", {k: p.grad for k, p in vf.named_parameters()}, case, name, "vf")
 
 
 @pytest.mark.parametrize("mode", ("fp32", "f16x3"))
@@ -372,6 +416,7 @@ def test_rendering_forward_gradients(name, mode):
     print(f"MLPGRAD {name} rendering forward {mode}: worst {errs[worst]:.2e} at {worst}; features {errs['feats']:.2e} (bound {MODE_TOL[mode]:g})")
     assert set(errs) == set(case.grads)
     assert all(v < MODE_TOL[mode] for v in errs.values()), {k: v for k, v in errs.items() if v >= MODE_TOL[mode]}
+    figures(f"{name} rendering {mode} M={case.coef.shape[0]}", {**{k: p.grad for k, p in rn.named_parameters()}, "feats": feats.grad}, case, name, "rn")
 
 
 def _open_units(model):
@@ -418,3 +463,172 @@ def test_render_gradients_with_real_statistics():
     worst = max(between, key=between.get)
     print(f"MLPGRAD {name} render, default storages against precision fp32: worst {between[worst]:.2e} at {worst}")
     assert all(v < MODE_TOL["f16x3+f16act+f16dy"] for v in between.values())
+
+
+# ------------------------------------------------------------------------------------------------
+# gradients on every geometry, inputs included: per row, block and element against float64
+# ------------------------------------------------------------------------------------------------
+SPLIT_TOL = 2e-3           # batchstat._arith: the documented bound of the layer-at-a-time split arithmetic (per tensor)
+# (net, what asks for a gradient) the backward refuses at the call, before any launch.  Never listed because its numbers were off:
+#   vf_2h, points   the points' gradient comes from the layer-at-a-time kernels, which apply BatchNorm after every Linear but the
+#                   last (batchstat._require_shape); vf_2h has none.  Its parameters' gradients come from the fused chain.
+REFUSED = {("vf_2h", "points"): NotImplementedError}
+VF_ASKS = [(n, a) for n in MC.GRAD_VF for a in ("params", "points")]
+RN_INPUTS = ("feats", "normals")
+aid = lambda c: f"{c[0]}-{c[1]}"      # noqa: E731
+
+
+def _module(name, which, precision):
+    """A fresh copy of the net's module on the device with the arithmetic ``precision`` ("fp32": exact products on both paths)."""
+    lib.load()
+    vf, rn = MC.build_net(name).on(dev())
+    mod = vf if which == "vf" else rn
+    mod.precision = precision
+    mod.config = copy.copy(mod.config)
+    return mod
+
+
+def _no_launch(monkeypatch):
+    """Every launch takes its stream from lib._stream: none may happen while this is in place."""
+    def stream():
+        raise AssertionError("a kernel was launched by a call that had to be refused")
+    monkeypatch.setattr(lib, "_stream", stream)
+
+
+def _vf_gradients(mod, case, points_ask):
+    for p in mod.parameters():
+        p.grad = None
+    pts = case.inputs["points"].to(dev()).requires_grad_(points_ask)
+    out = mod(pts)
+    (out * case.coef.to(dev())).sum().backward()
+    got = {k: p.grad for k, p in mod.named_parameters()}
+    if points_ask:
+        got["points"] = pts.grad
+    return out, got
+
+
+def _rn_gradients(mod, case, asks=RN_INPUTS):
+    for p in mod.parameters():
+        p.grad = None
+    g = {k: v.to(dev()).requires_grad_(k in asks) for k, v in case.inputs.items()}
+    out = mod(g["points"], g["normals"], g["dirs"], g["feats"])
+    (out * case.coef.to(dev())).sum().backward()
+    got = {k: p.grad for k, p in mod.named_parameters()}
+    got.update({k: g[k].grad for k in asks})
+    return out, got
+
+
+def grads_held(tag, out, got, case, name, which, factor, tol):
+    """Every delivered gradient against float64: the output first, then per tensor kind the worst figure beside its host-float32
+    yardstick on an MLPGRAD line; asserts ``tol(key)`` per tensor (the project's existing measure) and, where ``factor`` is given,
+    factor x yardstick for every figure.  -> {(kind, figure): (device, yardstick)}."""
+    missing = [k for k, v in got.items() if v is None]
+    assert not missing, f"{tag}: no gradient delivered for {missing}"
+    assert out.shape == case.out.shape and float((out.detach().cpu().double() - case.out).abs().max()) < 1e-4
+    scores, yard, rows = figures(tag, got, case, name, which)
+    over = {k: s["tensor"] for k, s in scores.items() if not s["tensor"] < tol(k)}
+    assert not over, f"{tag}: per tensor {over}"
+    if factor is not None:
+        bad = {(k, f): (v, factor * yard[(MC.grad_kind(k), f)]) for k, s in scores.items() for f, v in s.items()
+               if not v <= factor * yard[(MC.grad_kind(k), f)]}
+        assert not bad, f"{tag}: above {factor:g} x the host-float32 yardstick: {bad}"
+    return rows
+
+
+@pytest.mark.parametrize("ask", VF_ASKS, ids=aid)
+def test_vector_field_gradients_exact(ask, monkeypatch):
+    """VectorFieldNetwork.forward in eval mode with precision "fp32" on every gradient net at every M of GRAD_M.  "params": only the
+    parameters ask (the fused chain, vfn_mlp_bwd_chain with _weight_grads and vfn_unfold_kernel; the narrow net layer by layer).
+    "points": the points ask too, which sends the call through the layer-at-a-time kernels with the running statistics
+    (batchstat._VFTrainMode, embed_rows_bwd with the skip piece).  Every figure within MAX_FACTOR x the host-float32 yardstick, or the
+    listed refusal before a launch."""
+    name, what = ask
+    mod = _module(name, "vf", "fp32")
+    if ask in REFUSED:
+        case = MC.vf_grad_case(name, 33)
+        pts = case.inputs["points"].to(dev()).requires_grad_(True)
+        torch.cuda.synchronize()
+        _no_launch(monkeypatch)
+        with pytest.raises(REFUSED[ask]):
+            mod(pts)
+        return
+    for m in MC.GRAD_M:
+        case = MC.vf_grad_case(name, m)
+        out, got = _vf_gradients(mod, case, what == "points")
+        assert set(got) == set(case.grads) | ({"points"} if what == "points" else set())
+        grads_held(f"{name} vector field {what} fp32 M={case.coef.shape[0]}", out, got, case, name, "vf", MC.MAX_FACTOR, lambda k: MODE_TOL["fp32"])
+
+
+@pytest.mark.parametrize("name", MC.GRAD_RN)
+def test_rendering_gradients_exact(name):
+    """RenderingNetwork.forward in eval mode with precision "fp32" (the exact products of the layer-at-a-time path) and
+    detach_normals=False, at every M of GRAD_M: every parameter, the features and the normals, per row."""
+    mod = _module(name, "rn", "fp32")
+    mod.config.detach_normals = False
+    for m in MC.GRAD_M:
+        case = MC.rn_grad_case(name, m)
+        out, got = _rn_gradients(mod, case)
+        assert set(got) == set(case.grads) | set(RN_INPUTS)
+        grads_held(f"{name} rendering fp32 M={case.coef.shape[0]}", out, got, case, name, "rn", MC.MAX_FACTOR, lambda k: MODE_TOL["fp32"])
+
+
+@pytest.mark.parametrize("name", MC.GRAD_RN)
+def test_rendering_inputs_without_a_gradient(name, monkeypatch):
+    """detach_normals=True (the reference detaches): normals.grad stays None while the features get theirs.  Points or view directions
+    that ask are refused at the call, by name, before any launch: the backward has no gradient for them."""
+    mod = _module(name, "rn", "fp32")
+    case = MC.rn_grad_case(name, 33)
+    mod.config.detach_normals = True
+    _, got = _rn_gradients(mod, case)
+    assert got["normals"] is None and got["feats"] is not None
+    torch.cuda.synchronize()
+    _no_launch(monkeypatch)
+    for asked, word in (("points", "points"), ("dirs", "view_dirs")):
+        g = {k: v.to(dev()).requires_grad_(k == asked) for k, v in case.inputs.items()}
+        with pytest.raises(NotImplementedError, match=word):
+            mod(g["points"], g["normals"], g["dirs"], g["feats"])
+
+
+SPLIT_VF = [n for n in MC.GRAD_VF if (n, "points") not in REFUSED]
+
+
+@pytest.mark.parametrize("name", SPLIT_VF)
+def test_vector_field_gradients_split(name):
+    """The split products of the layer-at-a-time path (precision "f16x3" with points that ask) at the full row count: parameters and
+    points inside the path's documented per-tensor bound; the per-row, per-block and per-element figures are printed, not bounded (a
+    bound for 16- and 22-bit arithmetic has to come from an emulation of its roundings)."""
+    mod = _module(name, "vf", "f16x3")
+    case = MC.vf_grad_case(name)
+    out, got = _vf_gradients(mod, case, True)
+    grads_held(f"{name} vector field points split M={case.coef.shape[0]}", out, got, case, name, "vf", None, lambda k: SPLIT_TOL)
+
+
+@pytest.mark.parametrize("name", MC.GRAD_RN)
+def test_rendering_gradients_split(name):
+    """The rendering nets, fresh and shipped, on the split products with detach_normals=False: parameters and features inside
+    MODE_TOL["f16x3"] (as in test_rendering_forward_gradients), the normals, which MODE_TOL has no entry for, inside the path's 2e-3;
+    figures printed."""
+    mod = _module(name, "rn", "f16x3")
+    mod.config.detach_normals = False
+    case = MC.rn_grad_case(name)
+    out, got = _rn_gradients(mod, case)
+    grads_held(f"{name} rendering split M={case.coef.shape[0]}", out, got, case, name, "rn", None,
+               lambda k: SPLIT_TOL if k == "normals" else MODE_TOL["f16x3"])
+
+
+@pytest.mark.parametrize("scale", MC.SCALES)
+def test_narrow_vector_field_forward(scale):
+    """The narrow net (hidden width 64, 32 features, BatchNorm) in eval mode under no_grad, vf_forward_eval_rows with the exact
+    products: vector and feature rows and feature columns at every M against float64, MAX_FACTOR x the forward yardstick."""
+    name = next(iter(MC.NARROW_VF))
+    mod = _module(name, "vf", "fp32")
+    assert not mod.supports_fused()
+    g, yard = device_rows(name, scale), MC.yardstick(name, scale)
+    for m in MC.M_VALUES:
+        with torch.no_grad():
+            out = mod(g["points"][:m].contiguous())
+        assert out.shape == (m, 3 + mod._feature_dims())
+        scores = MC.score(dict(vector=out[:, :3], feats=out[:, 3:]), MC.case_reference(name, scale, m))
+        print(f"MLPTAB {name}-s{scale:g} rows fp32 M={m}: " + "  ".join(f"{k} {v:.2e} | {yard[k]:.2e}" for k, v in scores.items()))
+        for k, v in scores.items():
+            assert v <= MC.MAX_FACTOR * yard[k], f"{name} scale {scale:g} M={m} {k}: {v:.3e} on the device, {yard[k]:.3e} float32 on the host"

@@ -10,6 +10,15 @@ Measured here (``pytest -s`` prints them):
     with + 1e-5 dropped from the fold                                                            1 660 .. 10 100 x
     with b + mean for b - mean                                                                   290 000 .. 3 400 000 x
   rows within 1e-4 of a ReLU kink: vector-field net 38.5 % / 38.8 %, rendering net 25.2 % (c1_det+stats: 50.5 % / 22.3 %)
+    the fresh nets: vf_2h 9.0 %, vf_4h_skip1 26.2 %, vf_8h_skip7 44.3 %, vf_4h_w64 4.8 %, rn_1h_m* 5.5 .. 8.0 %, rn_3h_m* 21.0 .. 23.0 %
+  float64 gradient cases against float64 autograd of the oracle, every parameter and input at every M of GRAD_M      <= 1e-10 of the largest entry
+  gradient yardstick (float32 autograd on the host against float64, worst over GRAD_M), over the nets:
+    per tensor 1e-7 .. 3e-6      rows 6e-7 .. 6e-5      blocks 4e-7 .. 2e-6      elements 6e-6 .. 1e-4
+  plants on the float64 gradient, in the figure meant for each (per tensor beside it), as multiples of the yardstick:
+    the head's three vector rows x 1.002                          rows 2.0e-3, 35 .. 490 x        (per tensor 2.8e-4 .. 6.2e-4)
+    one view-direction block of the rendering net's layer 0 x 1.002   blocks 2.0e-3, 1 970 .. 3 720 x (per tensor 9.0e-4 .. 1.7e-3)
+    the skip layer's encoding block without its 1 / sqrt(2)       blocks 0.41, 190 000 .. 540 000 x
+    one gamma element (the median one) x 1.01                     elems 1.0e-2, 96 .. 1 010 x     (per tensor 1.8e-4 .. 5.1e-4)
 """
 import pytest
 import torch
@@ -113,25 +122,111 @@ def test_scoring_tells_a_right_kernel_from_a_wrong_one(name):
                 assert v > MC.MAX_FACTOR * yard[k], (plant, k, v, yard[k])
 
 
-@pytest.mark.parametrize("name", MC.GRAD_NETS)
+GRAD_CASES = [(n, "vf") for n in MC.GRAD_VF] + [(n, "rn") for n in MC.GRAD_RN]
+gid = lambda c: f"{c[0]}-{c[1]}"      # noqa: E731
+
+
+GRAD_NAMES = list(dict.fromkeys(MC.GRAD_VF + MC.GRAD_RN))
+
+
+@pytest.mark.parametrize("name", GRAD_NAMES)
 def test_gradient_cases_keep_away_from_kinks(name):
-    """Fewer than half of the pool's rows within the margin of a ReLU kink, at most 513 rows kept, and the float64 autograd of the
-    restatement equal to the float64 autograd of the oracle for every parameter, BatchNorm gamma and beta among them."""
+    """Fewer than half of the pool's rows within the margin of a ReLU kink, between 257 and 513 rows kept (so every M of GRAD_M is a
+    case of its own), the point (0, 0, 0) and the row that starts with -0.0 among the vector field's rows, and at every M the float64
+    autograd of the restatement equal to the float64 autograd of the oracle: every parameter, BatchNorm gamma and beta among them, and
+    every input."""
+    for which in [w for n, w in GRAD_CASES if n == name]:
+        _gradient_case_checks(name, which)
+
+
+def _gradient_case_checks(name, which):
     net = MC.build_net(name)
-    vf, rn = MC.vf_grad_case(name), MC.rn_grad_case(name)
-    print(f"{name}: rows within the margin of a kink: vector field {vf.rejected:.3f}, rendering {rn.rejected:.3f}; kept {vf.coef.shape[0]} / {rn.coef.shape[0]}")
-    for case in (vf, rn):
-        assert case.rejected < MC.KINK_CAP and 128 <= case.coef.shape[0] <= MC.GRAD_ROWS
-    sd = net.vf_sd()
-    leaves = MC._leaves(sd)
-    (O.vf_mlp(vf.inputs["points"].to(F64), sd, **net.vf_args) * vf.coef.to(F64)).sum().backward()
-    assert any(k.endswith(".1.weight") for k in leaves) and any(k.endswith(".1.bias") for k in leaves)
-    for k, v in leaves.items():
-        assert float((v.grad - vf.grads[k]).abs().max()) <= 1e-10 * float(v.grad.abs().max()), k
-    sd = net.rn_sd()
-    leaves = MC._leaves(sd)
-    f = rn.inputs["feats"].to(F64).requires_grad_(True)
-    out = O.render_mlp(rn.inputs["points"].to(F64), rn.inputs["normals"].to(F64), rn.inputs["dirs"].to(F64), f, sd, net.rn._multires())
-    (out * rn.coef.to(F64)).sum().backward()
-    for k, v in list(leaves.items()) + [("feats", f)]:
-        assert float((v.grad - rn.grads[k]).abs().max()) <= 1e-10 * float(v.grad.abs().max()), k
+    full = MC.grad_case(name, which)
+    print(f"{name} {which}: rows within the margin of a kink {full.rejected:.3f}; kept {full.coef.shape[0]}")
+    assert full.rejected < MC.KINK_CAP and 257 < full.coef.shape[0] <= MC.GRAD_ROWS
+    if which == "vf":
+        p = full.inputs["points"]
+        zero = (p == 0).all(dim=1)
+        minus = (p[:, 0] == 0) & torch.signbit(p[:, 0]) & ~zero
+        print(f"{name} vf: the point (0, 0, 0) is row {torch.nonzero(zero).reshape(-1).tolist()}, -0.0 starts row {torch.nonzero(minus).reshape(-1).tolist()}")
+        assert bool(zero[:3].any()) and bool(minus[:3].any()), "every case from 31 rows on holds both (placed where the pool's own row sits at a kink)"
+    for m in MC.GRAD_M:
+        case = MC.grad_case(name, which, m)
+        assert case.coef.shape[0] == (full.coef.shape[0] if m is None else m)
+        sd = (net.vf_sd if which == "vf" else net.rn_sd)()
+        leaves = MC._leaves(sd)
+        x = {k: v.to(F64).requires_grad_(True) for k, v in case.inputs.items()}
+        if which == "vf":
+            out = O.vf_mlp(x["points"], sd, **net.vf_args)
+        else:
+            out = O.render_mlp(x["points"], x["normals"], x["dirs"], x["feats"], sd, net.rn._multires())
+        (out * case.coef.to(F64)).sum().backward()
+        if net.name != "vf_2h":
+            assert any(MC.grad_kind(k) == "gamma" for k in leaves) and any(MC.grad_kind(k) == "beta" for k in leaves)
+        assert set(leaves) == set(k for k in case.grads if k.startswith("layers.")) and set(x) == set(case.input_grads)
+        for k, v in list(leaves.items()) + list(x.items()):
+            want = case.grads[k] if k in case.grads else case.input_grads[k]
+            assert float((v.grad - want).abs().max()) <= 1e-10 * float(v.grad.abs().max()), (k, m)
+
+
+@pytest.mark.parametrize("case_key", GRAD_CASES, ids=gid)
+def test_gradient_yardstick(case_key):
+    """The float32 restatement under float32 autograd against the float64 cases, pooled over GRAD_M: printed, every figure a float32
+    figure (below 1e-3: an element held at GRAD_FLOOR of its tensor is off by 100 x the tensor's 1e-6 at the most) and none zero
+    (a figure of zero would make the device's bound an equality)."""
+    name, which = case_key
+    yard = MC.grad_yardstick(name, which)
+    print(f"{name} {which} yardstick: " + "  ".join(f"{k}.{f} {v:.1e}" for (k, f), v in sorted(yard.items())))
+    kinds = {k for k, _ in yard}
+    assert {"weight", "bias", "points"} <= kinds and (("feats" in kinds and "normals" in kinds) if which == "rn" else True)
+    assert all(0.0 < v < 1e-3 for v in yard.values()), yard
+    assert {f for _, f in yard} == {"tensor", "rows", "blocks", "elems"}
+
+
+def _planted(case, key, change):
+    g = {k: v.clone() for k, v in case.grads.items()}
+    change(g[key])
+    return g
+
+
+PLANT_NETS = dict(head=MC.GRAD_NETS + ("vf_4h_skip1", "vf_8h_skip7", "vf_4h_w64"), dirs=MC.GRAD_RN,
+                  skip=MC.GRAD_NETS + ("vf_4h_skip1", "vf_8h_skip7", "vf_4h_w64"), gamma=tuple(n for n in MC.GRAD_VF if n != "vf_2h") + MC.GRAD_RN)
+
+
+@pytest.mark.parametrize("plant", sorted(PLANT_NETS))
+def test_gradient_scoring_tells_right_from_subtly_wrong(plant):
+    """One error planted in the float64 gradient itself, at the full row count; the figure meant for it must exceed MAX_FACTOR x the
+    host-float32 yardstick of that net, tensor kind and figure (the unplanted float32 host gradient is at most 1 x by construction).
+    The per-tensor figure is printed beside it: what helpers.grad_rel_err would have said.
+      head    the three vector rows of the vector field's last Linear x 1.002                      -> rows
+      dirs    one view-direction block (the last one) of the rendering net's first layer x 1.002   -> blocks
+      skip    the encoding columns of the vector field's skip layer without their 1 / sqrt(2)      -> blocks
+      gamma   one element of the first BatchNorm's gamma, the one of median size, x 1.01           -> elems"""
+    for name in PLANT_NETS[plant]:
+        net = MC.build_net(name)
+        which = "rn" if plant == "dirs" or (plant == "gamma" and net.vf is None) else "vf"
+        mod = net.vf if which == "vf" else net.rn
+        case, yard = MC.grad_case(name, which), MC.grad_yardstick(name, which)
+        if plant == "head":
+            key, fig = f"layers.{mod.num_layers - 1}.weight", "rows"
+            g = _planted(case, key, lambda t: t[:3].mul_(1.002))
+        elif plant == "dirs":
+            key, fig = "layers.0.0.weight", "blocks"
+            _, a, b = [blk for blk in MC.column_blocks(key, net, which) if blk[0].startswith("dirs")][-1]
+            g = _planted(case, key, lambda t: t[:, a:b].mul_(1.002))
+        elif plant == "skip":
+            layer = mod.skip_connection_in[0]
+            key, fig = f"layers.{layer}.0.weight", "blocks"
+            a = MC.column_blocks(key, net, which)[0][2]
+            g = _planted(case, key, lambda t: t[:, a:].mul_(MC.SQRT2_F32))
+        else:
+            key, fig = "layers.0.1.weight", "elems"
+            i = int(case.grads[key].abs().argsort()[case.grads[key].numel() // 2])
+            g = _planted(case, key, lambda t: t[i].mul_(1.01))
+        got = MC.grad_score(g[key], case.grads[key], key, net, which)
+        bound = MC.MAX_FACTOR * yard[(MC.grad_kind(key), fig)]
+        print(f"plant {plant} in {name} {which} {key}: {fig} {got[fig]:.2e} ({got[fig] / yard[(MC.grad_kind(key), fig)]:.0f} x its yardstick), "
+              f"per tensor {got['tensor']:.2e} ({got['tensor'] / yard[(MC.grad_kind(key), 'tensor')]:.0f} x)")
+        assert got[fig] > bound, (plant, name, key, got, bound)
+        clean = MC.grad_score(case.grads[key], case.grads[key], key, net, which)
+        assert all(v == 0.0 for v in clean.values())

@@ -18,7 +18,9 @@ def _flat3(t: torch.Tensor) -> torch.Tensor:
 
 
 def vf_forward(net, points: torch.Tensor, vector_only: bool = False) -> torch.Tensor:
-    if not net.supports_fused():       # a geometry the fused kernels are not specialised for: layer-at-a-time row kernels
+    # a geometry the fused kernels are not specialised for, or points that ask for their gradient (the fused backward has none for them):
+    # layer-at-a-time row kernels
+    if not net.supports_fused() or (torch.is_grad_enabled() and points.requires_grad):
         from .batchstat import vf_forward_eval_rows
         out = vf_forward_eval_rows(net, points)
         return out[:, :3].contiguous() if vector_only else out

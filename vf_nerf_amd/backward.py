@@ -800,6 +800,9 @@ def _offset_view(t: torch.Tensor, col0: int) -> _RawPointer:
 
 
 def vf_forward_autograd(net, points, vector_only):
+    if torch.is_grad_enabled() and points.requires_grad:
+        # _VFForward.backward has no gradient for its points: never a silent None (autograd.vf_forward sends such a call layer by layer)
+        raise NotImplementedError("vf_forward_autograd: no gradient with respect to 'points' from the fused backward")
     plist = getattr(net, "_param_list_cache", None)
     if plist is None:
         plist = net._param_list_cache = list(net.parameters())

@@ -247,6 +247,68 @@ def _groups(m: int) -> int:
     return max(1, min(256, m // 256))
 
 
+def _grad_blocks(n: int, k: int, split: bool):
+    """The pieces of dW = dZ^T X [n, k] the weight-gradient kernels have shapes for -> (row blocks (first row, rows, head shape?), column
+    blocks (kind, first column, columns)); NotImplementedError for a layer they have none for."""
+    row_blocks = []
+    if n % 256 != 0 and n % 256 <= 32 and n > 32 and split:
+        # 259 = 256 + 3: any partition of the rows is valid; this one keeps the wide block at column 0 of dZ (16-byte aligned rows: the
+        # bf16 product), the last three rows go through the narrow-head shape
+        row_blocks += [(r, 256, 0) for r in range(0, n - n % 256, 256)]
+        row_blocks.append((n - n % 256, n % 256, 2))
+    elif n % 256 != 0 and n % 256 <= 32 and n > 32:   # 259 = 3 + 256: rows 0..2 as the narrow head, the rest as one block
+        row_blocks.append((0, n % 256, 2))
+        row_blocks += [(r, 256, 0) for r in range(n % 256, n, 256)]
+    elif n <= 32:
+        row_blocks.append((0, n, 2))
+    else:
+        row_blocks += [(r, min(256, n - r), 0) for r in range(0, n, 256)]
+    # input columns: a 256-wide "act" block when there is one, and a <= 64-wide "aux" block for the rest
+    if k <= 64:
+        col_blocks = [("aux", 0, k)]
+    elif k == 256:
+        col_blocks = [("act", 0, 256)]
+    elif 256 < k <= 320 and split:
+        col_blocks = [("act", 0, 256), ("aux", 256, k - 256)]          # (any partition of the columns is valid: the aligned one)
+    elif 256 < k <= 320:
+        col_blocks = [("aux", 0, k - 256), ("act", k - 256, 256)]      # rendering net: [p, PE(d), n | 256 features]
+    else:
+        raise NotImplementedError(f"weight gradients for in_features={k}")
+    if any(head for _, _, head in row_blocks):
+        if k <= 64:
+            # a narrow head of a narrow net (25 x 64 in front of its skip layer): the head shape's [32][256] slab takes any k <= 256
+            # columns (vfn_weight_grad_partials shape 2 reads columns < k_valid, the un-fold columns < act_nc)
+            col_blocks = [("act", 0, k)]
+        elif any(kind != "act" for kind, _, _ in col_blocks):
+            raise NotImplementedError(f"weight gradients of a narrow head ({n} x {k}) reading more than 256 inputs")
+    return row_blocks, col_blocks
+
+
+def _require_backward(net) -> None:
+    """Refuses, before anything is launched, a net the layer-at-a-time backward cannot serve."""
+    _require_shape(net)
+    if len(_unfold_entries(net)) > UNFOLD_MAX:
+        raise NotImplementedError(f"weight gradients of {net.num_layers} layers in more than {UNFOLD_MAX} pieces")
+
+
+def _unfold_entries(net) -> list:
+    split = _split(net)
+    return [rb for i in range(net.num_layers) for rb in _grad_blocks(net._linear(i).out_features, net._linear(i).in_features, split)[0]]
+
+
+UNFOLD_MAX = 12       # csrc/vfn_unfold.hip: entries of one launch
+
+
+def _refuse_input_grads(**inputs) -> None:
+    """The rendering net's backward delivers the gradients of the features and (detach_normals=False) the normals; an input it has
+    none for must not get ``None`` in silence (the reference's trainer never asks for these)."""
+    if torch.is_grad_enabled():
+        for name, t in inputs.items():
+            if t is not None and t.requires_grad:
+                raise NotImplementedError(f"RenderingNetwork.forward: no gradient with respect to {name!r} on the HIP path "
+                                          f"(only the features and, with detach_normals=False, the normals)")
+
+
 class _ParamGrads:
     """Weight-gradient partial slabs of every layer, un-folded (summed) in one launch at the end."""
 
@@ -267,30 +329,7 @@ class _ParamGrads:
         n, k = lin.out_features, lin.in_features
         dev, G, m = dz.device, self.G, self.m
         split = _split(self.net)
-        row_blocks = []
-        if n % 256 != 0 and n % 256 <= 32 and n > 32 and split:
-            # 259 = 256 + 3: any partition of the rows is valid; this one keeps the wide block at column 0 of dZ (16-byte aligned rows: the
-            # bf16 product), the last three rows go through the narrow-head shape
-            row_blocks += [(r, 256, 0) for r in range(0, n - n % 256, 256)]
-            row_blocks.append((n - n % 256, n % 256, 2))
-        elif n % 256 != 0 and n % 256 <= 32 and n > 32:   # 259 = 3 + 256: rows 0..2 as the narrow head, the rest as one block
-            row_blocks.append((0, n % 256, 2))
-            row_blocks += [(r, 256, 0) for r in range(n % 256, n, 256)]
-        elif n <= 32:
-            row_blocks.append((0, n, 2))
-        else:
-            row_blocks += [(r, min(256, n - r), 0) for r in range(0, n, 256)]
-        # input columns: a 256-wide "act" block when there is one, and a <= 64-wide "aux" block for the rest
-        if k <= 64:
-            col_blocks = [("aux", 0, k)]
-        elif k == 256:
-            col_blocks = [("act", 0, 256)]
-        elif 256 < k <= 320 and split:
-            col_blocks = [("act", 0, 256), ("aux", 256, k - 256)]          # (any partition of the columns is valid: the aligned one)
-        elif 256 < k <= 320:
-            col_blocks = [("aux", 0, k - 256), ("act", k - 256, 256)]      # rendering net: [p, PE(d), n | 256 features]
-        else:
-            raise NotImplementedError(f"weight gradients for in_features={k}")
+        row_blocks, col_blocks = _grad_blocks(n, k, split)
         folded = x if isinstance(x, Folded) else None
         if folded is not None:
             foldable = split and k == 256 and all(not head for _, _, head in row_blocks) and folded.z.shape[1] >= 256
@@ -308,8 +347,6 @@ class _ParamGrads:
             for kind, c0, nc in col_blocks:
                 dzv, xv = Cols(dz, r0), Cols(x, c0)
                 if head:
-                    if kind != "act":
-                        raise NotImplementedError("a narrow head reading fewer than 256 inputs")
                     part = torch.empty(G, 32, 256, device=dev)
                     lib.weight_grad_partials(2, dzv, dzv.ld, rows, xv, xv.ld, nc, m, G, part, db_part if first else None)
                     u.update(dw_act=part, act_c0=c0, act_nc=nc)
@@ -436,6 +473,10 @@ class _VFTrainMode(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, points, want_jacobian, *params):
+        if any(ctx.needs_input_grad):
+            _require_backward(net)
+        else:
+            _require_shape(net)
         pts = points.detach().reshape(-1, 3).float().contiguous()
         m = pts.shape[0]
         st = _vf_forward_state(net, pts, batch_stats=net.training)
@@ -486,6 +527,7 @@ def vf_forward_eval_rows(net, points: torch.Tensor) -> torch.Tensor:
         raise lib.VfnError("the layer-at-a-time forward runs on the device (no CPU fallback)")
     if net.training:
         raise ValueError("vf_forward_eval_rows is the eval-mode path")
+    _require_shape(net)
     if torch.is_grad_enabled() and (points.requires_grad or any(p.requires_grad for p in net.parameters())):
         return _VFTrainMode.apply(net, points, False, *list(net.parameters()))
     pts = points.detach().reshape(-1, 3).float().contiguous()
@@ -509,6 +551,10 @@ class _RenderTrainMode(torch.autograd.Function):
         f = feats.shape[1]
         if k0 != 3 + pe + 3 + f:
             raise lib.VfnError(f"rendering net: first layer reads {k0} columns, inputs give {3 + pe + 3 + f}")
+        if any(ctx.needs_input_grad):
+            _require_backward(net)
+        else:
+            _require_shape(net)
         x0 = torch.zeros(m, _up8(k0), device=dev)
         lib.embed_rows(points.detach().reshape(-1, 3).float().contiguous(), m, 0, Cols(x0, 0))
         lib.embed_rows(view_dirs.detach().reshape(-1, 3).float().contiguous(), m, net._multires(), Cols(x0, 3))
@@ -538,6 +584,7 @@ class _RenderTrainMode(torch.autograd.Function):
 def render_forward_train_mode(net, points, normals, view_dirs, feats) -> torch.Tensor:
     if not points.is_cuda:
         raise lib.VfnError("the training-mode forward runs on the device (no CPU fallback)")
+    _refuse_input_grads(points=points, view_dirs=view_dirs)
     return _RenderTrainMode.apply(net, True, points, normals, view_dirs, feats.float(), *list(net.parameters()))
 
 
@@ -547,6 +594,7 @@ def render_forward_eval_autograd(net, points, normals, view_dirs, feats) -> torc
     statistics, gradients to the parameters and the features."""
     if not points.is_cuda:
         raise lib.VfnError("the differentiable rendering-net forward runs on the device (no CPU fallback)")
+    _refuse_input_grads(points=points, view_dirs=view_dirs)
     return _RenderTrainMode.apply(net, False, points, normals, view_dirs, feats.float(), *list(net.parameters()))
 
 

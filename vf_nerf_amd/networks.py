@@ -215,7 +215,8 @@ class VectorFieldNetwork(_PackedMLP):
 
     def forward(self, points: torch.Tensor, vector_only: bool = False, jacobian: bool = True) -> torch.Tensor:
         """points[M,3] -> [M, 3+F] (tanh'ed).  ``vector_only`` returns just the 3 vector columns and
-        skips the feature block of the last Linear (grid queries / proposal pass).
+        skips the feature block of the last Linear (grid queries / proposal pass).  ``points`` that require a gradient get it
+        from the layer-at-a-time kernels (autograd.vf_forward); a geometry those cannot serve is refused at the call.
         In training mode (vector_field_network.py:146-173): batch-statistics BatchNorm and nine more columns, the three
         ``autograd.grad`` rows -> [M, 3+F+9]; the reference marks ``points`` as requiring grad in place, which is not done
         here.  ``jacobian=False`` skips those columns (callers that drop them)."""
@@ -223,7 +224,7 @@ class VectorFieldNetwork(_PackedMLP):
             from .batchstat import vf_forward_train_mode
             out = vf_forward_train_mode(self, points, want_jacobian=jacobian and not vector_only)
             return out[:, :3].contiguous() if vector_only else out
-        if points.is_cuda and torch.is_grad_enabled():
+        if points.is_cuda and torch.is_grad_enabled() and not points.requires_grad:
             # points a sampler wrote into the open training step's supervision rows (stepengine.StepSession): the vector-only saving forward on
             # those rows; [:, :3] of the result is all the trainer reads (train/vector_field_nerf_train.py:201,213)
             from .stepengine import session_vf_forward
